@@ -5,7 +5,11 @@ One "step" = one pass of the whole hot path (sync scan -> OFDM transform + demap
 Viterbi -> ETI assembly) over one batch of B independent cu8 streams that are already resident in HBM
 (BASELINE.json configs[2]: batch=256, canonical 12 sub-channel 1136 kbit/s ensemble, full MSC).  ETI frames stay in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, stage times, guard counts of the timed step).
+--dump-outputs DIR: the ETI frames of the last timed step as .npy files (dump_outputs), inputs seeded, so two builds compare output for output.
+--full: after the timed steps, the side measurements and checks too (rooflines, variants, sessions, host-fed legs, payload, CPU baseline).
 
 N > 1: one process per GPU, every rank decodes its own 256 streams (weak scaling; ensembles are independent, so there is
 no data-path collective and no RCCL traffic at all).  Two ways to get the N ranks:
@@ -305,6 +309,37 @@ def workload_text(args):
             % (args.streams, args.tfs))
 
 
+DUMP_SEED = 20260
+DUMP_SAMPLE_BYTES = 40 << 20               # the float32 frame sample of all ranks together (the whole dump stays under 64 MB)
+
+
+def dump_outputs(dirname, eti_of, nstreams, rank=0, world=1):
+    """--dump-outputs: what the timed path handed its caller in its last step -- every stream's ETI frames (eti_of(b): uint8 [frames, 6144]) -- as .npy
+    files that two builds can be compared by: eti_frame_count (float64 [streams]), eti_frame_digest (float64 [frames of all streams, 2]: the byte sum and
+    a seeded weighted byte sum of every frame, both exact integers), and a seeded sample of whole frames, eti_frames_sample (float32 [k, 6144]) with
+    eti_frames_sample_index (float64 [k, 2]: stream, frame).  With N ranks every rank writes its own files, prefixed rank<r>_."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    weights = rng.integers(1, 1 << 16, size=6144).astype(np.float64)    # 6144 x 255 x 65535 < 2^53: the sums stay exact in float64
+    frames = [eti_of(b) for b in range(nstreams)]
+    counts = np.array([len(f) for f in frames], dtype=np.float64)
+    digest = np.concatenate([np.stack([f.sum(axis=1, dtype=np.float64), f.astype(np.float64) @ weights], axis=1) for f in frames])
+    k = min(len(digest), DUMP_SAMPLE_BYTES // (6144 * 4 * world))
+    rows = np.sort(np.random.default_rng(DUMP_SEED + 1 + rank).choice(len(digest), size=k, replace=False))
+    ends = np.cumsum(counts)
+    stream = np.searchsorted(ends, rows, side="right")
+    frame = rows - (ends - counts)[stream]
+    sample = np.zeros((k, 6144), dtype=np.float32)
+    for j, (s, i) in enumerate(zip(stream, frame)):
+        sample[j] = frames[s][int(i)]
+    prefix = os.path.join(dirname, "rank%d_" % rank if world > 1 else "")
+    np.save(prefix + "eti_frame_count.npy", counts)
+    np.save(prefix + "eti_frame_digest.npy", digest)
+    np.save(prefix + "eti_frames_sample.npy", sample)
+    np.save(prefix + "eti_frames_sample_index.npy", np.stack([stream, frame], axis=1).astype(np.float64))
+
+
 # ---- one rank -----------------------------------------------------------------------------------------------------
 def h2d_inclusive(dab, device, tensors, sizes, frames_resident, args):
     """The same workload with the IQ in HOST memory, PCIe included (never `value`): page-locked buffers (dabhip_host_alloc) through
@@ -587,7 +622,7 @@ def run_rank(args, coord):
                  "first_seed": shard.stream_seed(2, mine[0]), "host_threads": os.environ.get("DABHIP_HOST_THREADS", "auto"),
                  "visible_devices": os.environ.get("ROCR_VISIBLE_DEVICES"), "cpu_budget": dict(zip(("affinity", "cfs_quota"), shard.cpu_budget()))}
     prof = None
-    if rank == 0 and not args.dry_run and not args.profile_pass:
+    if rank == 0 and args.full and not args.dry_run and not args.profile_pass:
         prof = load_profile()                                              # fails loudly BEFORE any GPU time is spent
 
     ntf_rank = 0
@@ -659,11 +694,15 @@ def run_rank(args, coord):
         elapsed = time.perf_counter() - t0
         stage = {k: v / args.steps for k, v in stage.items() if not k.startswith("h2d")}   # (sync_fp64_calls: a count per step, not ms)
         ntf_rank = eng.guard_stats()[1] // 230400 if not (args.soft or args.no_parity_guard) else 0
+        if args.dump_outputs:                                              # before anything below decodes again on this engine
+            dump_outputs(args.dump_outputs, eng.eti, len(tensors), rank, world)
 
         fft = None
         fused_off = None
         extra = {}
         if rank == 0:
+            extra["data"] = (("synthetic (%d distinct ensembles per GPU tiled to %d streams, host modulator)" % (ndistinct, args.streams)) if args.host_synth
+                             else ("synthetic (%d distinct ensembles per GPU, device-side modulator, %.1f s)" % (args.streams, t_gen)))
             flagged, decisions = eng.guard_stats()
             level = 0 if (args.no_parity_guard or args.soft) else eng.parity_guard_level()
             extra["parity_guard"] = {"on": level > 0, "level": level, "level_is": {0: "off", 1: "measured band", 2: "proven band (rigorous forward-error bound: DESIGN.md section 3)"}[level],
@@ -671,6 +710,7 @@ def run_rank(args, coord):
                                      "decisions_per_step": decisions, "redecided_in_fp64_per_step": flagged,
                                      "note": "hard decisions whose fp32 margin lies inside the error band are re-decided in fp64 from the int8 samples "
                                              "(k_parity.hip); both levels audited on the shipping kernel: profiles/r06_decision_audit.json; price by level: profiles/r06_guard_levels.json"}
+        if rank == 0 and args.full:                                        # everything beyond the headline: runs of its own after the timed steps
             # K2 = ofdm_fft_kernel by itself, on the same resident IQ and the frame list of the step just timed
             fft = eng.fft_roofline(max(3, min(args.steps, 10)))
             try:
@@ -736,8 +776,6 @@ def run_rank(args, coord):
                     extra["single_ensemble"] = single_ensemble(dab, torch, dev, eng, tensors, args)
                 except Exception as e:                                        # a side measurement: never takes `value` down with it
                     extra["single_ensemble"] = {"error": "%s: %s" % (type(e).__name__, e)}
-            extra["data"] = (("synthetic (%d distinct ensembles per GPU tiled to %d streams, host modulator)" % (ndistinct, args.streams)) if args.host_synth
-                             else ("synthetic (%d distinct ensembles per GPU, device-side modulator, %.1f s)" % (args.streams, t_gen)))
             if args.snr < 100.0:
                 eng.decode_device(ptrs, sizes)
                 extra["payload"] = payload_stats(dab, eng, rank * args.streams, min(16, args.streams), args.tfs)
@@ -864,6 +902,8 @@ def run_in_process(args):
         torch.cuda.synchronize(d)
     elapsed = time.perf_counter() - t0
     value = frames * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, multi.eti, len(tensors))
     per_slice = []
     for i in range(n):
         st = multi.engine(i).stage_ms()
@@ -903,9 +943,15 @@ def main():
     ap.add_argument("--soft", action="store_true", help="soft-decision decoding (extension; default: hard = reference semantics)")
     ap.add_argument("--no-h2d", action="store_true", help="skip the host-fed measurement (h2d_inclusive: 6.4 GB of page-locked host memory at the default size)")
     ap.add_argument("--h2d-segment-tfs", type=int, default=8, help="segment length of the host-fed streaming session, in transmission frames")
-    ap.add_argument("--profile-pass", action="store_true", help="run under tools/refresh_profiles.sh: no profile-derived objects (they are being produced), emit profile_meta")
+    ap.add_argument("--profile-pass", action="store_true", help="run under tools/refresh_profiles.sh (with --full): no profile-derived objects (they are being produced), emit profile_meta")
     ap.add_argument("--in-process", action="store_true", help="drive the --gpus N devices from this one process through dabhip_multi instead of N rank processes")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check everything beyond the headline: rooflines (K2 alone, "
+                    "stream ceiling, tracked profile), guard-off / other-level / two-kernel variants, single ensemble, steady-state session, host-fed "
+                    "legs, payload check, CPU baseline (the --no-* options switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the ETI frames of the last timed step to DIR/*.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.in_process:
         run_in_process(args)

@@ -137,6 +137,37 @@ def test_torchrun_launch_two_ranks_gloo():
     _check(_one_json_line(out), 2, 2)
 
 
+def test_dump_outputs_is_exact_seeded_and_bounded(tmp_path):
+    """--dump-outputs: per-frame digests of every stream (exact integers), a seeded sample of whole frames that is the same from run to run,
+    all of it in float32 / float64 and under 64 MB; with N ranks each rank writes its own prefixed files within its share."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    counts = [196] * 37 + [0, 5, 196]
+    eti = [np.random.default_rng(100 + b).integers(0, 256, size=(n, 6144), dtype=np.uint8) for b, n in enumerate(counts)]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), lambda b: eti[b], len(eti))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["eti_frame_count.npy", "eti_frame_digest.npy", "eti_frames_sample.npy", "eti_frames_sample_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64 << 20
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        assert got[f[:-4]].dtype in (np.float32, np.float64)
+        assert np.array_equal(got[f[:-4]], np.load(tmp_path / "b" / f)), f
+    assert got["eti_frame_count"].tolist() == counts
+    allf = np.concatenate(eti)
+    assert np.array_equal(got["eti_frame_digest"][:, 0], allf.sum(axis=1))
+    w = np.random.default_rng(bench.DUMP_SEED).integers(1, 1 << 16, size=6144)
+    assert np.array_equal(got["eti_frame_digest"][:, 1], allf.astype(np.int64) @ w)
+    idx, sample = got["eti_frames_sample_index"].astype(np.int64), got["eti_frames_sample"]
+    assert len(sample) == bench.DUMP_SAMPLE_BYTES // (6144 * 4) and len({tuple(r) for r in idx}) == len(idx)
+    for (s, i), row in zip(idx, sample):
+        assert np.array_equal(row, eti[s][i])
+    bench.dump_outputs(str(tmp_path / "r"), lambda b: eti[b], len(eti), rank=1, world=4)
+    assert len(np.load(tmp_path / "r" / "rank1_eti_frames_sample.npy")) == bench.DUMP_SAMPLE_BYTES // (6144 * 4 * 4)
+
+
 def test_cpu_baseline_tool_small_sample(tmp_path):
     """tools/cpu_baseline.py (the child bench.py starts for its cpu_baseline object) on a small capture."""
     sys.path.insert(0, ROOT)

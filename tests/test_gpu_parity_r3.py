@@ -68,6 +68,40 @@ def test_config2_the_benchmark_workload_itself():
         b.free()
 
 
+def test_bench_dump_outputs_are_the_timed_paths_frames(tmp_path):
+    """`bench.py --dump-outputs DIR` at a reduced size, twice: a plain line (exactly --steps timed steps, ms_per_step, none of --full's objects),
+    the same files from both runs, and their contents are the frames an engine returns for the same seeded streams."""
+    import json
+    import subprocess
+    nstreams, ntf = 8, 20
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--streams", str(nstreams), "--tfs", str(ntf), "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(tmp_path / run)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["config"]["eti_frames_per_step"] == nstreams * 4 * (ntf - 15)
+        assert not {"roofline", "cpu_baseline", "h2d_inclusive", "two_kernel_ofdm_variant", "profile_meta"} & set(d)
+        dumps.append({f: np.load(tmp_path / run / f) for f in os.listdir(tmp_path / run)})
+    assert dumps[0].keys() == dumps[1].keys() and all(np.array_equal(dumps[0][f], dumps[1][f]) for f in dumps[0])
+    cfgs = [dab.synth_preset(0, seed=shard.stream_seed(2, g), cif_count0=(97 * g) % 5000) for g in range(nstreams)]
+    bufs = [dab.DeviceBuffer(dab.synth_bytes(c, ntf)) for c in cfgs]
+    dab.synth_generate_device(cfgs, ntf, [b.ptr for b in bufs], 0)
+    eng = dab.Engine(0)
+    eng.decode_device([b.ptr for b in bufs], [dab.synth_bytes(c, ntf) for c in cfgs])
+    eti = [eng.eti(b) for b in range(nstreams)]
+    eng.close()
+    for b in bufs:
+        b.free()
+    got = dumps[0]
+    assert got["eti_frame_count.npy"].tolist() == [len(e) for e in eti]
+    assert np.array_equal(got["eti_frame_digest.npy"][:, 0], np.concatenate(eti).sum(axis=1))
+    idx = got["eti_frames_sample_index.npy"].astype(np.int64)
+    assert len(idx) == nstreams * 4 * (ntf - 15)                              # a small output is dumped whole
+    for (s, i), row in zip(idx, got["eti_frames_sample.npy"]):
+        assert np.array_equal(row, eti[s][i]), (s, i)
+
+
 def test_parity_guard_list_overflow_degrades_to_a_full_fp64_decision():
     """More decisions inside the fp32 error band than the guard's list holds: the launch does not fail (it did before round 3), its frames
     are decided again in full from fp64 transforms -- same ETI bytes as the oracle, fused and two-kernel OFDM stages, and a streaming

@@ -5,7 +5,7 @@ GRAFT_REPO_ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}; export
 O=gpurun_out/quick; mkdir -p $O
 timeout 1500 python -m pytest tests -q -x -m gpu > $O/gpu_tests.log 2>&1; echo "gpu tests rc=$?"; tail -n 5 $O/gpu_tests.log
 for i in 1 2; do
-  timeout 600 python bench.py --steps 20 --no-cpu-baseline --no-h2d ${BENCH_EXTRA:-} > $O/bench_$i.json 2> $O/bench_$i.err || echo "bench rc=$?"
+  timeout 600 python bench.py --full --steps 20 --no-cpu-baseline --no-h2d ${BENCH_EXTRA:-} > $O/bench_$i.json 2> $O/bench_$i.err || echo "bench rc=$?"
   python - <<PY
 import json
 d = json.loads(open("$O/bench_$i.json").read().strip().splitlines()[-1])

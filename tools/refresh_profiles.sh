@@ -8,7 +8,7 @@ rm -rf "$O" && mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 B="$R/bench.py"
 # PMC passes (one decode = the set-up decode is tiny; warmup 1 + steps 2 = 3 full decodes + the K2 roofline launches)
-P="--no-cpu-baseline --no-variants --no-h2d --profile-pass --steps 2 --warmup 1"
+P="--full --no-cpu-baseline --no-variants --no-h2d --profile-pass --steps 2 --warmup 1"
 CLK="GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_WAVES"
 C1="GRBM_GUI_ACTIVE SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_INSTS_SALU"
 # dynamic instruction classes (beside the static mix of tools/fused_isa_mix.sh)
@@ -39,16 +39,16 @@ ROUND=$(python3 -c "import re,sys; print(re.search(r'profiles\", \"(r\d+)_pmc_su
 mkdir -p "$R/profiles"
 [ -f "$R/profiles/${ROUND}_pmc_summary.csv" ] && cp "$R/profiles/${ROUND}_pmc_summary.csv" "$O/pmc_summary_previous.csv"
 cp "$O/pmc_summary.csv" "$R/profiles/${ROUND}_pmc_summary.csv"
-python3 "$B" --steps 20 > "$O/bench.json" 2>> "$O/bench.err"
-python3 "$B" --steps 10 --snr 5 --soft > "$O/bench_soft5db.json" 2>> "$O/bench.err"
-python3 "$B" --steps 10 --snr 5 --no-cpu-baseline > "$O/bench_hard5db.json" 2>> "$O/bench.err"
-python3 "$B" --steps 10 --snr 7 --soft --no-cpu-baseline > "$O/bench_soft7db.json" 2>> "$O/bench.err"
-python3 "$B" --steps 10 --snr 7 --no-cpu-baseline > "$O/bench_hard7db.json" 2>> "$O/bench.err"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -- python3 "$B" --no-cpu-baseline --no-h2d --steps 10 > "$O/bench_under_rocprof.json" 2>> "$O/bench.err"
+python3 "$B" --full --steps 20 > "$O/bench.json" 2>> "$O/bench.err"
+python3 "$B" --full --steps 10 --snr 5 --soft > "$O/bench_soft5db.json" 2>> "$O/bench.err"
+python3 "$B" --full --steps 10 --snr 5 --no-cpu-baseline > "$O/bench_hard5db.json" 2>> "$O/bench.err"
+python3 "$B" --full --steps 10 --snr 7 --soft --no-cpu-baseline > "$O/bench_soft7db.json" 2>> "$O/bench.err"
+python3 "$B" --full --steps 10 --snr 7 --no-cpu-baseline > "$O/bench_hard7db.json" 2>> "$O/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -- python3 "$B" --full --no-cpu-baseline --no-h2d --steps 10 > "$O/bench_under_rocprof.json" 2>> "$O/bench.err"
 cp "$(find "$O/trace" -name '*kernel_stats.csv' | head -1)" "$O/bench_kernel_stats.csv"
 cp "$(find "$O/trace" -name '*domain_stats.csv' | head -1)" "$O/bench_domain_stats.csv" 2>/dev/null || true
 rm -rf "$O/trace"
-rocprofv3 --kernel-trace --output-format csv -d "$O/trace2" -- python3 "$B" --no-cpu-baseline --no-variants --no-h2d --steps 5 > /dev/null 2>> "$O/bench.err"
+rocprofv3 --kernel-trace --output-format csv -d "$O/trace2" -- python3 "$B" --full --no-cpu-baseline --no-variants --no-h2d --steps 5 > /dev/null 2>> "$O/bench.err"
 python3 "$R/tools/timeline.py" "$O/trace2" > "$O/step_timeline.txt"      # the default step (no variants after it)
 rm -rf "$O/trace2"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -w "$R/tools/ubench/valu_rates.hip" -o /tmp/valu_rates && /tmp/valu_rates > "$O/valu_rates.txt" 2>&1
