@@ -25,6 +25,10 @@ ETI_BYTES = 6144
 
 u8p = C.POINTER(C.c_uint8)
 
+# Viterbi decoder forms (dabhip.h: DABHIP_FORM_*): value = bit of the decoder_forms() report
+FORM_AUTO, FORM_WAVE, FORM_LANE, FORM_TWO, FORM_TWO_PLAIN, FORM_FOUR = -1, 0, 1, 2, 3, 4
+FORMS = {"auto": FORM_AUTO, "wave": FORM_WAVE, "lane": FORM_LANE, "two": FORM_TWO, "two-plain": FORM_TWO_PLAIN, "four": FORM_FOUR}
+
 
 class DabhipError(RuntimeError):
     pass
@@ -203,6 +207,10 @@ _SIGNATURES = {
     "dabhip_host_free": (None, [C.c_void_p]),
     "dabhip_synth_generate_device": (C.c_int, [C.POINTER(SynthCfg), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int]),
     "dabhip_dab_set_soft": (C.c_int, [C.c_void_p, C.c_int]),
+    "dabhip_dab_set_decoder_forms": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "dabhip_dab_decoder_forms": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "dabhip_engine_set_decoder_forms": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "dabhip_engine_decoder_forms": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "dabhip_engine_trace_nco": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "dabhip_multi_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dabhip_multi_slice_cpus": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]),
@@ -261,6 +269,23 @@ def last_error():
 
 def _p(a):
     return a.ctypes.data_as(u8p)
+
+
+def _form(f):
+    """A form given by name ("wave", "lane", "two", "two-plain", "four", "auto"), None (= auto) or by its number."""
+    if f is None:
+        return FORM_AUTO
+    return FORMS[f] if isinstance(f, str) else int(f)
+
+
+def _form_names(mask):
+    return {name for name, v in FORMS.items() if v >= 0 and mask >> v & 1}
+
+
+def _decoder_forms(fn, h):
+    m, f = C.c_uint32(0), C.c_uint32(0)
+    _need(fn(h, C.byref(m), C.byref(f)) == 0, "decoder_forms")
+    return m.value, f.value
 
 
 def _need(cond, what):
@@ -575,7 +600,7 @@ class Sdr:
 class Dab:
     """init_dab_state + dab_process_frame (dab.h:91-92) for one stream."""
 
-    def __init__(self, device=0, soft=False):
+    def __init__(self, device=0, soft=False, forms=None):
         self.frames = []
         self._cb = ETI_CALLBACK(lambda p: self.frames.append(np.frombuffer(C.string_at(p, ETI_BYTES), np.uint8)))
         self._h = lib().dabhip_dab_init(device, self._cb)
@@ -585,6 +610,17 @@ class Dab:
         if soft:       # extension: the hand-off carries signed 4-bit values (int8 views of the same arrays)
             _need(lib().dabhip_dab_set_soft(self._h, 1) == 0, "dab_set_soft")
             self.fic, self.msc = self.fic.view(np.int8), self.msc.view(np.int8)
+        if forms is not None:
+            self.set_decoder_forms(*forms)
+
+    def set_decoder_forms(self, msc=None, fic=None):
+        """Force the Viterbi form of the MSC / FIC decodes (names or FORM_* numbers; None = the default rule)."""
+        _need(lib().dabhip_dab_set_decoder_forms(self._h, _form(msc), _form(fic)) == 0, "dab_set_decoder_forms")
+
+    def decoder_forms(self, masks=False):
+        """The forms that ran in the last process_frame: ({MSC form names}, {FIC form names}), or the two bit masks."""
+        m, f = _decoder_forms(lib().dabhip_dab_decoder_forms, self._h)
+        return (m, f) if masks else (_form_names(m), _form_names(f))
 
     def process_frame(self):
         r = lib().dabhip_dab_process_frame(self._h)
@@ -638,6 +674,15 @@ class Engine:
     def set_soft(self, enable):
         """Soft-decision decoding (4-bit soft values into the Viterbi metrics); off = parity mode."""
         _need(lib().dabhip_engine_set_soft(self._h, 1 if enable else 0) == 0, "set_soft")
+
+    def set_decoder_forms(self, msc=None, fic=None):
+        """Force the Viterbi form of every MSC / FIC launch (names or FORM_* numbers; None = the default rule, engine.hpp)."""
+        _need(lib().dabhip_engine_set_decoder_forms(self._h, _form(msc), _form(fic)) == 0, "set_decoder_forms")
+
+    def decoder_forms(self, masks=False):
+        """The forms that ran since the last decode / stage_fic_decode began: ({MSC form names}, {FIC form names}), or the two bit masks."""
+        m, f = _decoder_forms(lib().dabhip_engine_decoder_forms, self._h)
+        return (m, f) if masks else (_form_names(m), _form_names(f))
 
     def set_subchannels(self, ids):
         """Decode and carry only these SubChIds (None / empty = all, the reference's frames)."""

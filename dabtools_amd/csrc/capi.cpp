@@ -48,6 +48,7 @@ struct dabhip_engine {
   {
     const auto t0 = std::chrono::steady_clock::now();
     const int nl = nstreams >= 64 ? static_cast<int>(lanes.size()) : 1;   // small batches: the split does not pay
+    for (auto& l : lanes) l->clear_forms_ran();                           // (lanes this decode leaves idle report nothing)
     lane_of.assign(nstreams, 0);
     local_of.assign(nstreams, 0);
     lane_frames.assign(lanes.size(), 0);
@@ -298,6 +299,22 @@ int dabhip_engine_set_soft(dabhip_engine* e, int enable)
   for (auto& l : e->lanes) l->set_soft(enable != 0);
   return 0;
 }
+int dabhip_engine_set_decoder_forms(dabhip_engine* e, int msc_form, int fic_form)
+{
+  if (!e) { set_error("set_decoder_forms: null handle"); return -1; }
+  for (auto& l : e->lanes)
+    if (!l->set_decoder_forms(msc_form, fic_form)) return -1;
+  return 0;
+}
+int dabhip_engine_decoder_forms(const dabhip_engine* e, uint32_t* msc_mask, uint32_t* fic_mask)
+{
+  if (!e) { set_error("decoder_forms: null handle"); return -1; }
+  uint32_t m = 0, f = 0;
+  for (const auto& l : e->lanes) { m |= l->msc_forms_ran(); f |= l->fic_forms_ran(); }
+  if (msc_mask) *msc_mask = m;
+  if (fic_mask) *fic_mask = f;
+  return 0;
+}
 static uint64_t subchannel_mask(const int32_t* ids, int n)
 {
   if (!ids || n <= 0) return ~0ull;
@@ -428,6 +445,7 @@ int dabhip_stage_decision_audit_fused(dabhip_engine* e, const uint8_t* frames, i
 int dabhip_stage_fic_decode(dabhip_engine* e, const uint8_t* fic, int nframes, uint8_t* fibs, uint8_t* crc_ok)
 {
   if (!e || !fic || !fibs || !crc_ok) { set_error("stage_fic_decode: null argument"); return -1; }
+  for (auto& l : e->lanes) l->clear_forms_ran();
   return e->first().stage_fic_decode(fic, nframes, fibs, crc_ok);
 }
 
@@ -567,6 +585,18 @@ int dabhip_dab_set_soft(dabhip_dab* d, int enable)
   d->eng.set_soft(enable != 0);
   return d->eng.reserve_tf_slots(kDabSlots) ? 0 : -1;
 }
+int dabhip_dab_set_decoder_forms(dabhip_dab* d, int msc_form, int fic_form)
+{
+  if (!d) { set_error("dab_set_decoder_forms: null handle"); return -1; }
+  return d->eng.set_decoder_forms(msc_form, fic_form) ? 0 : -1;
+}
+int dabhip_dab_decoder_forms(const dabhip_dab* d, uint32_t* msc_mask, uint32_t* fic_mask)
+{
+  if (!d) { set_error("dab_decoder_forms: null handle"); return -1; }
+  if (msc_mask) *msc_mask = d->eng.msc_forms_ran();
+  if (fic_mask) *fic_mask = d->eng.fic_forms_ran();
+  return 0;
+}
 int dabhip_dab_last_fibs(const dabhip_dab* d, uint8_t* fibs, uint8_t* crc_ok)
 {
   if (!d || !fibs || !crc_ok) return -1;
@@ -578,6 +608,7 @@ int dabhip_dab_last_fibs(const dabhip_dab* d, uint8_t* fibs, uint8_t* crc_ok)
 int dabhip_dab_process_frame(dabhip_dab* d)
 {
   if (!d) { set_error("dab_process_frame: null handle"); return -1; }
+  d->eng.clear_forms_ran();
   if (d->slot == kDabSlots) {        // keep the 4 most recent TFs (16 CIFs of interleaver history)
     if (!d->eng.recycle_tf_slots(kDabSlots, 4)) return -1;
     d->plane.rebase(4 * (kDabSlots - 4));

@@ -176,6 +176,20 @@ Engine::Engine(int device, int host_threads, std::vector<int> cpus) : device_(de
   ok_ = true;
 }
 
+bool Engine::set_decoder_forms(int msc_form, int fic_form)
+{
+  const bool msc_ok = msc_form >= DABHIP_FORM_AUTO && msc_form <= DABHIP_FORM_FOUR;
+  const bool fic_ok = fic_form == DABHIP_FORM_AUTO || fic_form == DABHIP_FORM_WAVE || fic_form == DABHIP_FORM_LANE || fic_form == DABHIP_FORM_FOUR;
+  if (!msc_ok || !fic_ok) {
+    set_error("set_decoder_forms: no such form (MSC " + std::to_string(msc_form) + ", FIC " + std::to_string(fic_form) +
+              "; the FIC decoder has AUTO, WAVE, LANE and FOUR)");
+    return false;
+  }
+  msc_form_ = msc_form;
+  fic_form_ = fic_form;
+  return true;
+}
+
 Engine::~Engine()
 {
   for (auto& e : ev_)
@@ -273,6 +287,7 @@ bool Engine::launch_decode_batch(const DecodeBatch& b, const uint32_t* bits, con
   if (!check(launch_regroup(soft_bits_, ids, ntiles, d_jobs_.get(), d_stream_cif_base, bits, d_grouped_.get(), stream_), "regroup launch")) return false;
   if (!record(ev_msc_[1], stream_)) return false;
   if (b.wave_form) {
+    msc_ran_ |= 1u << DABHIP_FORM_WAVE;
     // small batch: one wave per code word (k_vitwave.hip), all lengths in one launch (longest first); its decisions use the survivor-record buffer
     if (!check(launch_viterbi_wave(soft_bits_, d_groups_.get(), static_cast<int>(b.groups.size()), ids, d_plans_.get(), d_grouped_.get(), row_words,
                                    d_decisions_.get(), prbs, out, record_stride, stream_),
@@ -282,11 +297,17 @@ bool Engine::launch_decode_batch(const DecodeBatch& b, const uint32_t* bits, con
     return true;
   }
   // mid-size batches (hard decisions): two lanes per code word (engine.hpp: two_lanes_max_groups_; 1 = always)
-  const bool two_lanes = !soft_bits_ && two_lanes_max_groups_ > 0 && (two_lanes_max_groups_ == 1 || static_cast<int>(b.groups.size()) <= two_lanes_max_groups_);
-  const bool four_lanes = !soft_bits_ && four_lanes_max_groups_ > 0 && (four_lanes_max_groups_ == 1 || static_cast<int>(b.groups.size()) <= four_lanes_max_groups_);
+  // (a form set by set_decoder_forms replaces the rule; multi-lane forms are hard-only: a soft engine runs the lane form)
+  const bool forced = msc_form_ != DABHIP_FORM_AUTO;
+  const bool two_lanes = !soft_bits_ && (forced ? msc_form_ == DABHIP_FORM_TWO || msc_form_ == DABHIP_FORM_TWO_PLAIN
+                                                : two_lanes_max_groups_ > 0 && (two_lanes_max_groups_ == 1 || static_cast<int>(b.groups.size()) <= two_lanes_max_groups_));
+  const bool four_lanes = !soft_bits_ && (forced ? msc_form_ == DABHIP_FORM_FOUR
+                                                 : four_lanes_max_groups_ > 0 && (four_lanes_max_groups_ == 1 || static_cast<int>(b.groups.size()) <= four_lanes_max_groups_));
+  const bool plain = forced ? msc_form_ == DABHIP_FORM_TWO_PLAIN : two_lanes_plain_;
+  msc_ran_ |= 1u << (four_lanes ? DABHIP_FORM_FOUR : two_lanes ? (plain ? DABHIP_FORM_TWO_PLAIN : DABHIP_FORM_TWO) : DABHIP_FORM_LANE);
   for (size_t sl = 0; sl + 1 < b.slice_start.size(); ++sl) {
     const int g0 = b.slice_start[sl], n = b.slice_start[sl + 1] - g0;
-    if (four_lanes || (two_lanes && two_lanes_plain_)) {
+    if (four_lanes || (two_lanes && plain)) {
       if (!check(launch_viterbi_fused_lanes(four_lanes ? 4 : 2, d_groups_.get() + g0, n, ids, d_plans_.get(), d_grouped_.get(), row_words, d_decisions_.get(), prbs, out,
                                             record_stride, stream_),
                  "viterbi (lanes per code word) launch"))
@@ -430,10 +451,14 @@ bool Engine::fic_decode_slots_async(int first, int n, uint8_t* fibs_host, uint8_
   std::vector<int> ids(static_cast<size_t>(ntiles) * 64, -1);
   for (int i = 0; i < nblocks; ++i) ids[i] = 4 * first + i;
   std::vector<WaveGroup> groups;
-  const bool wave_form = nblocks <= wave_max_fic_blocks_;      // few blocks: one wave per block (k_vitwave.hip), rows per block and chunk of steps
+  // (fic_form_ from set_decoder_forms replaces the rule; four lanes are hard-only: a soft engine runs the lane form)
+  const bool forced = fic_form_ != DABHIP_FORM_AUTO;
+  const bool wave_form = forced ? fic_form_ == DABHIP_FORM_WAVE : nblocks <= wave_max_fic_blocks_;   // few blocks: one wave per block (k_vitwave.hip), rows per block and chunk of steps
   // more, but not enough to fill the device with one lane per block (774 dependent steps in front of the control plane): four lanes per block
   // (vit_four_lanes.hpp; same records, same arguments), up to 128 tiles = 32 streams x 64 TF (measured: nothing to gain above).
-  const bool fic_four_lanes = !wave_form && !soft_bits_ && fic_four_lanes_max_tiles_ > 0 && (fic_four_lanes_max_tiles_ == 1 || ntiles <= fic_four_lanes_max_tiles_);
+  const bool fic_four_lanes = !wave_form && !soft_bits_ &&
+                              (forced ? fic_form_ == DABHIP_FORM_FOUR : fic_four_lanes_max_tiles_ > 0 && (fic_four_lanes_max_tiles_ == 1 || ntiles <= fic_four_lanes_max_tiles_));
+  fic_ran_ |= 1u << (wave_form ? DABHIP_FORM_WAVE : fic_four_lanes ? DABHIP_FORM_FOUR : DABHIP_FORM_LANE);
   const int64_t dr = wave_form ? int64_t(64) * ((plan_table_[pid].nsteps + kWaveChunk - 1) / kWaveChunk) : (plan_table_[pid].nsteps + 7) / 8 * 8;
   for (int g = 0; g < ntiles; ++g) groups.push_back(WaveGroup{pid, 64 * g, std::min(64, nblocks - 64 * g), plan_table_[pid].nsteps, 0, g * dr});
   // The FIC kernels run on the side stream as well, behind what the main stream has queued so far (the FIC bits): 1008 waves of 774
@@ -490,7 +515,9 @@ bool Engine::msc_prepare(const std::vector<const JobList*>& stream_jobs, const s
     if (trace_host) std::fprintf(stderr, "[host]   msc_prepare %-14s %8.3f ms\n", what, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_in).count());
   };
   std::string error;
-  if (prepare_msc_work(plan_table_, *pool_, stream_jobs, planes, stream_row_base, stream_fib_base, kMaxDecisionRows, out, &error, mark, wave_max_codewords_)) return true;
+  // a forced form: every batch, or none, in the wave form (set_decoder_forms)
+  const int64_t wave_max = msc_form_ == DABHIP_FORM_AUTO ? wave_max_codewords_ : msc_form_ == DABHIP_FORM_WAVE ? INT64_MAX : 0;
+  if (prepare_msc_work(plan_table_, *pool_, stream_jobs, planes, stream_row_base, stream_fib_base, kMaxDecisionRows, out, &error, mark, wave_max)) return true;
   set_error(error);
   return false;
 }
@@ -689,6 +716,7 @@ bool Engine::guard_check()
 
 int64_t Engine::decode(const uint8_t* const* iq, const size_t* nbytes, int nstreams, bool on_device)
 {
+  clear_forms_ran();
   return decode_impl(iq, nbytes, nstreams, on_device, false);
 }
 
@@ -1474,6 +1502,7 @@ int Engine::stage_demap(const float* spectra, int nframes, uint8_t* fic, uint8_t
 
 int Engine::stage_fic_decode(const uint8_t* fic, int nframes, uint8_t* fibs, uint8_t* crc_ok)
 {
+  clear_forms_ran();
   if (!hard_only("stage_fic_decode")) return -1;
   if (!ok_) { set_error("engine not initialised (no GPU?)"); return -1; }
   if (nframes <= 0) return 0;

@@ -192,6 +192,13 @@ class Engine {
   // decode() / first segment of a session.  All ones (default) = the reference's frames.
   void set_subchannel_filter(uint64_t keep) { subch_keep_ = keep; }
   void set_soft(bool on) { soft_bits_ = on ? 4 : 0; tf_slots_ = 0; msc_rows_ = 0; }
+  // Viterbi decoder forms (include/dabhip.h: DABHIP_FORM_*; test plumbing): -1 = the rule of the knobs and defaults below, else that form for
+  // every MSC / FIC launch.  False for a form the decoder does not have (TWO, TWO_PLAIN for the FIC).  forms_ran: bit f = form f ran in a
+  // launch since clear_forms_ran() (a multi-lane form asked of a soft engine runs, and reports, the lane form).
+  bool set_decoder_forms(int msc_form, int fic_form);
+  void clear_forms_ran() { msc_ran_ = 0; fic_ran_ = 0; }
+  uint32_t msc_forms_ran() const { return msc_ran_.load(); }
+  uint32_t fic_forms_ran() const { return fic_ran_.load(); }
   // parity guard (k_parity.hip; default on): hard decisions whose fp32 margin lies inside the error band of the fp32 OFDM
   // transform are re-decided in fp64 from the int8 samples, so the demapped bits are those of exact arithmetic (what the
   // reference's fp64 FFTW path yields).  Inactive with soft decisions and with the software AFC (no reference semantics there).
@@ -339,6 +346,8 @@ class Engine {
   // FIC decodes of at most this many tiles of 64 blocks (above the wave form's range: 12 .. 32 streams x 64 TF) run four lanes per block: FIC stage 0.32 -> 0.24 ms
   // at 16 streams, 0.58 -> 0.50 at 32, nothing from 64 streams (256 tiles) on.  DABHIP_FIC_FOUR_LANES = 0 / 1 / N
   int fic_four_lanes_max_tiles_ = 128;
+  int msc_form_ = -1, fic_form_ = -1;          // set_decoder_forms: -1 = the rules above
+  std::atomic<uint32_t> msc_ran_{0}, fic_ran_{0};
   std::mutex* heavy_mu_ = nullptr;
   std::unique_ptr<ThreadPool> pool_;   // host threads for per-stream control-plane work
   std::unique_ptr<AsyncLane> host_lane_;   // the control-plane pass of a decode, beside its GPU work

@@ -94,6 +94,9 @@ uint32_t dabhip_dab_status(const dabhip_dab *d);
  * demapper's rule is dabhip_engine_set_soft's) and the FIC / MSC decoders use them as branch metrics.  Lets a test feed the
  * decoders the very values an independent restatement decodes (oracle/or_soft.c). */
 int dabhip_dab_set_soft(dabhip_dab *d, int enable);
+/* Decoder forms of this seam (dabhip_engine_set_decoder_forms, DABHIP_FORM_*; any time); the report covers the last dabhip_dab_process_frame. */
+int dabhip_dab_set_decoder_forms(dabhip_dab *d, int msc_form, int fic_form);
+int dabhip_dab_decoder_forms(const dabhip_dab *d, uint32_t *msc_mask, uint32_t *fic_mask);
 /* FIBs (12 x 32 bytes) and CRC flags (12) of the TF processed last (struct tf_fibs_t, dab.h:21-25). */
 int dabhip_dab_last_fibs(const dabhip_dab *d, uint8_t *fibs, uint8_t *crc_ok);
 
@@ -159,6 +162,29 @@ int dabhip_engine_set_afc(dabhip_engine *e, int enable);
  * parity mode (bit-exact with the reference).  With soft decisions the output equals the reference's wherever that decodes
  * without errors and is better (lower BER) at low SNR. */
 int dabhip_engine_set_soft(dabhip_engine *e, int enable);
+
+/* Viterbi decoder forms (test plumbing: which kernel decodes is otherwise chosen by batch size, engine.hpp; the bytes are the same in every form).
+ * MSC: DABHIP_FORM_WAVE       one wave per code word (k_vitwave.hip; the default up to 12,288 code words)
+ *      DABHIP_FORM_LANE       one lane per code word (viterbi_fused_kernel; the default above 1,536 groups of 64 code words)
+ *      DABHIP_FORM_TWO        two lanes per code word (vit_two_lanes.hpp; the default from 801 to 1,536 groups)
+ *      DABHIP_FORM_TWO_PLAIN  two lanes per code word, table-free (vit_four_lanes.hpp; otherwise only with DABHIP_VIT_LANES_PLAIN=1)
+ *      DABHIP_FORM_FOUR       four lanes per code word (vit_four_lanes.hpp; the default up to 800 groups)
+ * FIC: DABHIP_FORM_WAVE (default up to 3,072 blocks), DABHIP_FORM_LANE, DABHIP_FORM_FOUR (default up to 128 tiles of 64 blocks).
+ * dabhip_engine_set_decoder_forms sets the form of every MSC and every FIC launch of all of the engine's lanes, over the environment knobs
+ * (DABHIP_VIT_WAVE_MAX and its kin); DABHIP_FORM_AUTO restores the rule of the knobs and defaults.  -1 with error text for a
+ * form the decoder does not have (TWO and TWO_PLAIN for the FIC).  The multi-lane forms take hard decisions only: on a soft engine
+ * (dabhip_engine_set_soft) a forced TWO, TWO_PLAIN or FOUR runs the lane form, and the report says LANE.  A forced WAVE decodes every batch in one
+ * launch (the lane forms split a launch past 24 GiB of survivor records).
+ * dabhip_engine_decoder_forms: bit f of *msc_mask / *fic_mask is set when form f ran in at least one launch since the last
+ * dabhip_engine_decode or dabhip_stage_fic_decode began (0: no such launch, e.g. no MSC frame).  Either pointer may be NULL. */
+#define DABHIP_FORM_AUTO (-1)
+#define DABHIP_FORM_WAVE 0
+#define DABHIP_FORM_LANE 1
+#define DABHIP_FORM_TWO 2
+#define DABHIP_FORM_TWO_PLAIN 3
+#define DABHIP_FORM_FOUR 4
+int dabhip_engine_set_decoder_forms(dabhip_engine *e, int msc_form, int fic_form);
+int dabhip_engine_decoder_forms(const dabhip_engine *e, uint32_t *msc_mask, uint32_t *fic_mask);
 
 /* Parity guard (default ON).  The reference takes its hard decisions as sign tests on fp64 FFTW spectra (input_sdr.c:132-162);
  * the OFDM stage here transforms in fp32.  With the guard on, every decision whose |Re| or |Im| of cur*conj(prev) lies inside

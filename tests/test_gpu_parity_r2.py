@@ -122,7 +122,7 @@ def _profile_ensembles():
     return ensembles
 
 
-def test_all_uep_and_eep_profiles_through_process_frame():
+def test_all_uep_and_eep_profiles_through_process_frame(forms=None):
     """dab_process_frame (dab.c:35-98 -> create_eti misc.c:218-314 -> uep_/eep_depuncture depuncture.c:84-132) for ALL 64
     UEP profiles and 8 EEP levels x n in {1, 2, 8}: structured FIC, RANDOM MSC bits (so the decoder output is whatever
     the scalar viterbi.c decides, ties included).  HIP back end == the REAL reference objects, frame by frame."""
@@ -151,7 +151,7 @@ def test_all_uep_and_eep_profiles_through_process_frame():
         cb = CB(lambda p, u: frames_or.append(np.ctypeslib.as_array(p, (6144,)).copy()))
         od = O.or_dab_new(C.cast(cb, C.c_void_p), None)
         H = R.refh_new() if R is not None else None
-        d = dab.Dab(0)
+        d = dab.Dab(0, forms=forms)
         for t in range(16):
             fic = np.zeros(9216, np.uint8)
             for q in range(4):
@@ -168,7 +168,9 @@ def test_all_uep_and_eep_profiles_through_process_frame():
                 R.refh_process(H)
             d.fic[:] = fic
             d.msc[:] = msc
-            d.process_frame()
+            r = d.process_frame()
+            if forms is not None:        # (a caller that pinned the decoder forms: exactly those ran)
+                assert d.decoder_forms() == ({forms[0]} if r > 0 else set(), {forms[1]}), (ei, t)
         got = np.array(d.frames)
         assert got.shape == (12, 6144), (ei, got.shape)
         assert np.array_equal(got, np.array(frames_or)), "ensemble %d vs oracle" % ei

@@ -46,6 +46,7 @@ def test_config2_the_benchmark_workload_itself():
     eng = dab.Engine(0)
     ptrs, sizes = [b.ptr for b in bufs], [nbytes] * nstreams
     assert eng.decode_device(ptrs, sizes) == nstreams * 4 * (ntf - 15)
+    assert eng.decoder_forms() == ({"lane"}, {"lane"})                     # the default rule at 256 streams (engine.hpp)
     digests = []
     sample = list(range(0, nstreams, 17))[:15] + [255]                     # 16 streams
     kept = {}

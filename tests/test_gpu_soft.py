@@ -62,13 +62,13 @@ def _msc_values(rng, kind):
 
 
 @pytest.fixture(params=["wave per code word (k_vitwave.hip)", "lane per code word (viterbi_fused_kernel)"])
-def decoder_form(request, monkeypatch):
-    """Both forms of the decoder: small decodes run one wave per code word by default; DABHIP_VIT_WAVE_MAX=0 sends them to the batch form."""
-    if request.param.startswith("lane"):
-        monkeypatch.setenv("DABHIP_VIT_WAVE_MAX", "0")
-    else:
-        monkeypatch.delenv("DABHIP_VIT_WAVE_MAX", raising=False)
-    return request.param
+def decoder_form(request):
+    """Both forms of the decoder, MSC and FIC, pinned through set_decoder_forms (small decodes would run one wave per code word by default)."""
+    return "lane" if request.param.startswith("lane") else "wave"
+
+
+def _assert_forms(obj, form, msc_ran=True):
+    assert obj.decoder_forms() == ({form} if msc_ran else set(), {form}), form
 
 
 def test_soft_decoders_bit_exact_on_identical_values_all_shapes(decoder_form):
@@ -90,14 +90,14 @@ def test_soft_decoders_bit_exact_on_identical_values_all_shapes(decoder_form):
             covered.add((slform, idx, size))
         kind = kinds[ei % len(kinds)]
         od = ol.SoftDab(ol.SOFT_Q4)
-        d = dab.Dab(0, soft=True)
+        d = dab.Dab(0, soft=True, forms=(decoder_form, decoder_form))
         for t in range(16):
             fic = _fic_values(cfg, t, keep)
             msc = _msc_values(rng, kind)
             od.process(fic, msc)
             d.fic[:] = fic
             d.msc[:] = msc
-            d.process_frame()
+            _assert_forms(d, decoder_form, d.process_frame() > 0)
         got = np.array(d.frames)
         want = np.array(od.frames)
         assert got.shape == (12, 6144) and want.shape == (12, 6144), (ei, got.shape, want.shape)
@@ -112,7 +112,7 @@ def test_soft_fic_decoder_bit_exact_on_arbitrary_values(decoder_form):
     them, CRC or not -- the oracle's bytes exactly."""
     O = ol.oracle()
     rng = np.random.default_rng(43)
-    d = dab.Dab(0, soft=True)
+    d = dab.Dab(0, soft=True, forms=(decoder_form, decoder_form))
     for t, kind in enumerate(["full", "ties", "zero", "saturated", "full", "ties"]):
         fic = _msc_values(rng, kind)[:9216]
         want_fib = np.zeros((12, 32), np.uint8)
@@ -120,7 +120,7 @@ def test_soft_fic_decoder_bit_exact_on_arbitrary_values(decoder_form):
         O.or_fic_decode_soft(ol._ptr(fic.astype(np.float32), C.c_float), ol.SOFT_Q4, ol._ptr(want_fib), ol._ptr(want_ok))
         d.fic[:] = fic
         d.msc[:] = 0
-        d.process_frame()
+        _assert_forms(d, decoder_form, d.process_frame() > 0)
         fibs, ok = d.last_fibs()
         assert np.array_equal(fibs, want_fib), (t, kind)
         assert np.array_equal(ok, want_ok), (t, kind)
@@ -140,11 +140,13 @@ def test_soft_demapper_values_within_the_stated_tolerance_and_eti_given_those_va
     streams = _noisy_streams(snr)
     eng = dab.Engine(0)
     eng.set_soft(True)
+    eng.set_decoder_forms(msc=decoder_form, fic=decoder_form)
     report = {}
     for fused in (True, False):
         eng.set_fused(fused)
         total = eng.decode(streams)
         assert total > 0
+        _assert_forms(eng, decoder_form)
         for b, iq in enumerate(streams):
             eti_or, vals, ntf = ol.or_replay_soft(iq, ol.SOFT_Q4, values_tf=64)
             assert ntf == vals.shape[0] and ntf >= 16

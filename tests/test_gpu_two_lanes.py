@@ -1,28 +1,26 @@
 """The decoder with two and with four lanes per code word (vit_two_lanes.hpp, vit_four_lanes.hpp: mid-size batches, hard decisions) against the lane form and
 the oracle: the same bytes.  (The whole suite also runs with every lane-form decode forced through them: tools/gpu/two_lanes.sh, four_lanes.sh STAGE=suite.)"""
-import os
-
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
 
+# form -> (MSC, FIC) decoder forms: 0 = one lane per code word, 1 = two lanes (vit_two_lanes.hpp), 2 = two lanes without tables,
+# 4 = four lanes (vit_four_lanes.hpp); the FIC follows the lane form (0) or the four-lane form (4), and takes the lane form beside the two-lane ones
+FORMS = {0: ("lane", "lane"), 1: ("two", "lane"), 2: ("two-plain", "lane"), 4: ("four", "four")}
+
+
 def _engine(dab, form):
-    """form: 0 = one lane per code word, 1 = two lanes (vit_two_lanes.hpp), 2 = two lanes without tables, 4 = four lanes (vit_four_lanes.hpp)"""
-    old = {k: os.environ.get(k) for k in ("DABHIP_VIT_TWO_LANES", "DABHIP_VIT_FOUR_LANES", "DABHIP_VIT_LANES_PLAIN", "DABHIP_VIT_WAVE_MAX")}
-    os.environ["DABHIP_VIT_TWO_LANES"] = "1" if form in (1, 2) else "0"
-    os.environ["DABHIP_VIT_LANES_PLAIN"] = "1" if form == 2 else "0"
-    os.environ["DABHIP_VIT_FOUR_LANES"] = "1" if form == 4 else "0"
-    os.environ["DABHIP_VIT_WAVE_MAX"] = "0"                  # no wave-per-code-word form: the batch below is the lane form's or the two-lane form's
-    try:
-        return dab.Engine(0)                                  # (the knobs are read when an engine is made)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+    eng = dab.Engine(0)
+    eng.set_decoder_forms(*FORMS[form])
+    return eng
+
+
+def _decode(eng, caps, form):
+    n = eng.decode(caps)
+    assert eng.decoder_forms() == tuple({f} for f in FORMS[form]), form
+    return n
 
 
 @pytest.mark.parametrize("preset,streams,tfs", [(0, 10, 26), (1, 7, 21)])
@@ -34,7 +32,7 @@ def test_two_lanes_per_code_word_decode_what_the_lane_form_and_the_oracle_decode
     out = {}
     for mode in (0, 1, 2, 4):
         eng = _engine(dab, mode)
-        n = eng.decode(caps)
+        n = _decode(eng, caps, mode)
         out[mode] = [eng.eti(b) for b in range(streams)]
         assert n == sum(x.shape[0] for x in out[mode]) and n > 0
         eng.close()
@@ -53,8 +51,12 @@ def test_the_default_rule_takes_two_lanes_for_a_mid_size_batch_and_the_bytes_do_
     caps = [dab.synth_generate(dab.synth_preset(0, seed=7300 + b, snr_db=11.0), 24) for b in range(16)]
     ref = None
     for mode in (None, 0, 1, 4):
-        eng = dab.Engine(0) if mode is None else _engine(dab, mode)
-        eng.decode(caps)
+        if mode is None:
+            eng = dab.Engine(0)
+            eng.decode(caps)
+        else:
+            eng = _engine(dab, mode)
+            _decode(eng, caps, mode)
         got = np.concatenate([eng.eti(b) for b in range(16)])
         eng.close()
         if ref is None:
