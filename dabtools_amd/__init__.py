@@ -53,7 +53,7 @@ class SynthCfg(C.Structure):
                 ("cif_count0", C.c_int32), ("skip_samples", C.c_int32), ("amplitude", C.c_double),
                 ("snr_db", C.c_double), ("cfo_hz", C.c_double),
                 ("fib_patch_len", C.c_int32), ("fib_patch_from_cif", C.c_int32), ("fib_patch", C.c_uint8 * 32),
-                ("reconf", ReconfCfg * 2), ("channel", ChannelCfg)]
+                ("reconf", ReconfCfg * 2), ("channel", ChannelCfg), ("dabplus_slots", C.c_uint64), ("dabplus_phase", C.c_int32)]
 
     def set_reconf(self, k, at_cif, subs, fic_lead=0):
         """Reconfiguration k (0 / 1): from logical CIF at_cif on the multiplex is `subs`, a list of (id, start_cu, slform, uep_index, eep_protlev,
@@ -174,6 +174,15 @@ _SIGNATURES = {
     "dabhip_synth_generate": (C.c_int64, [C.POINTER(SynthCfg), C.c_int, u8p, C.c_size_t]),
     "dabhip_synth_payload": (C.c_int, [C.POINTER(SynthCfg), C.c_int, C.c_int, u8p, C.c_int]),
     "dabhip_synth_fibs": (C.c_int, [C.POINTER(SynthCfg), C.c_int, u8p]),
+    "dabhip_synth_dabplus_superframe": (C.c_int, [C.POINTER(SynthCfg), C.c_int, C.c_int, u8p, C.c_int]),
+    "dabhip_dabplus_create": (C.c_void_p, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
+    "dabhip_dabplus_destroy": (None, [C.c_void_p]),
+    "dabhip_dabplus_push": (C.c_int64, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "dabhip_dabplus_superframes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
+    "dabhip_dabplus_data": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, u8p, C.c_int64]),
+    "dabhip_dabplus_au_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, u8p, C.c_int64]),
+    "dabhip_dabplus_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "dabhip_dabplus_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
     "dabhip_engine_set_fused": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_engine_set_sync_speculation": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_stream_set_sync_speculation": (C.c_int, [C.c_void_p, C.c_int]),
@@ -371,6 +380,14 @@ def synth_fibs(cfg, cif_index):
     buf = np.zeros(96, dtype=np.uint8)
     _need(lib().dabhip_synth_fibs(C.byref(cfg), cif_index, _p(buf)) == 96, "synth_fibs")
     return buf
+
+
+def synth_dabplus_superframe(cfg, sf_index, slot):
+    """The unprotected 110 s bytes of DAB+ superframe sf_index of a dabplus_slots slot (before RS parity and interleaving)."""
+    buf = np.zeros(110 * 72, dtype=np.uint8)
+    n = lib().dabhip_synth_dabplus_superframe(C.byref(cfg), sf_index, slot, _p(buf), buf.size)
+    _need(n >= 0, "synth_dabplus_superframe")
+    return buf[:n].copy()
 
 
 def stream_ceiling(device=0, nbytes=4 << 30, reps=3):
@@ -660,6 +677,109 @@ class Dab:
 
 
 # ---- batch engine -------------------------------------------------------------------------------
+# one record of dabhip_dabplus_superframes (dabhip.h: dabhip_dabplus_sf)
+DABPLUS_SF = np.dtype([("stream", "<i4"), ("sub", "<i4"), ("fct", "<i4"), ("s", "<i4"), ("fire_ok", "u1"), ("layout_ok", "u1"), ("rfa", "u1"),
+                       ("dac_rate", "u1"), ("sbr_flag", "u1"), ("aac_channel_mode", "u1"), ("ps_flag", "u1"), ("mpeg_surround_config", "u1"),
+                       ("num_aus", "<i4"), ("au_start", "<u2", (6,)), ("au_len", "<u2", (6,)), ("crc_ok", "<u4"), ("rs_corrected", "<i4"),
+                       ("rs_failed", "<i4")])
+assert DABPLUS_SF.itemsize == 64
+DABPLUS_STATS = ("superframes", "fire_fails", "rs_corrected_bytes", "rs_failed_codewords", "aus", "au_crc_fails", "sync_losses")
+
+
+class DabPlus:
+    """DAB+ audio out of ETI frames on the GPU (dabhip_dabplus_*): superframe sync, RS(120,110) correction, AU CRCs, for nstreams streams and the
+    DAB+ sub-channels subch_ids of each.  State (sync, the last 4 frames of every stream) carries from push to push."""
+
+    def __init__(self, nstreams, subch_ids, device=0):
+        self.nstreams, self.subch_ids = int(nstreams), [int(i) for i in subch_ids]
+        ids = (C.c_int32 * len(self.subch_ids))(*self.subch_ids)
+        self._h = lib().dabhip_dabplus_create(device, self.nstreams, ids, len(self.subch_ids))
+        _need(self._h, "dabplus_create")
+
+    def push(self, frames, counts=None):
+        """frames: a list of per-stream arrays of ETI frames (n x 6144 bytes each), one array of all frames stream after stream with counts, or
+        (device_ptr, counts) for frames in device memory (Engine.eti_device_ptr's layout).  Returns the superframes this push completed."""
+        if isinstance(frames, tuple):
+            ptr, counts = frames
+            src, on_dev = C.c_void_p(ptr), 1
+        else:
+            if isinstance(frames, list):
+                counts = [np.asarray(f).size // ETI_BYTES for f in frames]
+                arr = np.ascontiguousarray(np.concatenate([np.asarray(f, dtype=np.uint8).reshape(-1) for f in frames]) if frames else np.zeros(0, np.uint8))
+            else:
+                arr = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+                if counts is None:
+                    _need(self.nstreams == 1, "dabplus_push: counts needed for several streams")
+                    counts = [arr.size // ETI_BYTES]
+            self._keep = arr
+            src, on_dev = C.c_void_p(arr.ctypes.data), 0
+        cnt = (C.c_int64 * self.nstreams)(*[int(c) for c in counts])
+        n = lib().dabhip_dabplus_push(self._h, src, cnt, on_dev)
+        _need(n >= 0, "dabplus_push")
+        return n
+
+    def superframes(self, stream=0, sub=0):
+        """Records of the last push's superframes of (stream, sub-channel index): a DABPLUS_SF array."""
+        n = lib().dabhip_dabplus_superframes(self._h, stream, sub, None, 0)
+        _need(n >= 0, "dabplus_superframes")
+        out = np.zeros(n, dtype=DABPLUS_SF)
+        _need(lib().dabhip_dabplus_superframes(self._h, stream, sub, out.ctypes.data, n) == n, "dabplus_superframes")
+        return out
+
+    def data(self, stream=0, sub=0):
+        """The corrected 110 s audio bytes of those superframes, one after another."""
+        n = lib().dabhip_dabplus_data(self._h, stream, sub, None, 0)
+        _need(n >= 0, "dabplus_data")
+        out = np.zeros(n, dtype=np.uint8)
+        _need(lib().dabhip_dabplus_data(self._h, stream, sub, _p(out), n) == n, "dabplus_data")
+        return out
+
+    def au_bytes(self, stream=0, sub=0):
+        """The AUs of the last push with a good CRC, CRC bytes stripped, one after another."""
+        n = lib().dabhip_dabplus_au_bytes(self._h, stream, sub, None, 0)
+        _need(n >= 0, "dabplus_au_bytes")
+        out = np.zeros(n, dtype=np.uint8)
+        _need(lib().dabhip_dabplus_au_bytes(self._h, stream, sub, _p(out), n) == n, "dabplus_au_bytes")
+        return out
+
+    def aus(self, stream=0, sub=0):
+        """The same AUs as a list of uint8 arrays, in order."""
+        blob, out, off = self.au_bytes(stream, sub), [], 0
+        for r in self.superframes(stream, sub):
+            if not r["layout_ok"]:
+                continue
+            for k in range(r["num_aus"]):
+                if r["crc_ok"] >> k & 1:
+                    n = int(r["au_len"][k]) - 2
+                    out.append(blob[off:off + n])
+                    off += n
+        return out
+
+    def stats(self, stream=0, sub=0):
+        """Counters since creation, in DABPLUS_STATS order (int64 array of 7)."""
+        c = np.zeros(7, dtype=np.int64)
+        _need(lib().dabhip_dabplus_stats(self._h, stream, sub, c.ctypes.data_as(C.POINTER(C.c_int64))) == 0, "dabplus_stats")
+        return c
+
+    def stage_ms(self):
+        """GPU time of the last push per stage: {"locate", "sync", "rs", "au", "carry"} in ms."""
+        names = (C.c_char_p * 5)()
+        ms = (C.c_float * 5)()
+        n = lib().dabhip_dabplus_stage_ms(self._h, names, ms, 5)
+        return {names[i].decode(): ms[i] for i in range(n)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().dabhip_dabplus_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     def __init__(self, device=0, host_threads=0, _borrowed=None):
         self._owned = _borrowed is None

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <mutex>
 
+#include "dabplus.hpp"
 #include "device_types.hpp"
 
 namespace dabhip {
@@ -177,6 +178,23 @@ hipError_t launch_fib_crc(const uint8_t* fibs, int nfib, const uint16_t* crc_tab
 // K5: ETI header/FIB copy, EOF CRC, trailer
 hipError_t launch_eti_finish(const EtiFrameMeta* meta, int nframes, const uint8_t* headers, int header_stride, const uint8_t* fibs,
                              const uint16_t* crc_tab, const uint16_t* shift_cols, uint8_t* eti, hipStream_t stream);
+
+// k_dabplus.hip: DAB+ superframes out of ETI frames (dabplus.hpp has the types, dabhip.h the sync rule).  locate: the sub-channels of every
+// (stream, frame) into loc [nstreams][maxv][nsub]; sync + scan + jobs: the candidates of every (stream, sub-channel) (at most cap each), the push's
+// superframe list, totals = {superframes, codewords}; rs: the ncw codewords into data (110 s bytes per superframe) and cw_status (symbols
+// corrected, 0xff = failed), syn: 16 bytes of scratch per codeword; au: one record per superframe and the counters (crc_tab: the CRC-16 byte table, then
+// x^(8 n) mod G for n < kRsK kMaxS; data: 16 bytes of slack at its end); carry: the last 4 frames of every stream.
+hipError_t launch_dabplus_locate(const DabPlusFrames& fr, const int32_t* subch, int nsub, int nstreams, int maxv, DabPlusLoc* loc, hipStream_t stream);
+hipError_t launch_dabplus_sync(const DabPlusFrames& fr, int nstreams, int nsub, int maxv, const DabPlusLoc* loc, DabPlusSync* sync, DabPlusCand* cand,
+                               int cap, int* ncand, int* lane_cw, int64_t* counters, DabPlusJob* jobs, int* lane_sf_base, int* lane_cw_base, int* totals,
+                               hipStream_t stream);
+hipError_t launch_dabplus_rs(const DabPlusJob* jobs, const int* totals, int ncw, const DabPlusLoc* loc, int maxv, int nsub, const uint8_t* gf_tables,
+                             uint8_t* data, uint8_t* cw_status, uint32_t* syn, hipStream_t stream);
+hipError_t launch_dabplus_au(const DabPlusJob* jobs, int nsf, const DabPlusLoc* loc, int maxv, int nsub, const uint8_t* data, const uint8_t* cw_status,
+                             const uint16_t* crc_tab, dabhip_dabplus_sf* recs, int64_t* counters, hipStream_t stream);
+hipError_t launch_dabplus_carry(const DabPlusFrames& fr, int nstreams, uint8_t* carry_next, hipStream_t stream);
+size_t dabplus_gf_table_bytes();                 // the rs kernel's GF(256) tables: their size, and filled on the host
+void dabplus_gf_table_fill(uint8_t* out);
 
 // k_probe.hip: streaming rates of this device (fill, copy, K2's read/write mix) in GB/s -- bench.py's yardstick beside the K2 figure
 int stream_ceiling(int device, size_t bytes, int reps, double* gbs);

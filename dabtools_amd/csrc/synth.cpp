@@ -11,6 +11,7 @@
 #include "../../include/dabhip.h"
 #include "dab_bits.hpp"
 #include "dab_tables.hpp"
+#include "dabplus.hpp"
 #include "synth.hpp"
 
 namespace dabhip {
@@ -28,7 +29,7 @@ inline uint64_t mix64(uint64_t z)
 }
 inline uint64_t key(uint64_t seed, uint64_t a, uint64_t b, uint64_t c) { return mix64(mix64(mix64(seed ^ mix64(a)) + b) + c); }
 
-enum : uint64_t { kDomPayload = 1, kDomFiller = 2, kDomNoise = 3 };
+enum : uint64_t { kDomPayload = 1, kDomFiller = 2, kDomNoise = 3, kDomDabPlus = 4 };
 
 SubChannel to_subchannel(const dabhip_subch_cfg& c)
 {
@@ -90,6 +91,13 @@ bool channel_active(const dabhip_channel_cfg& c)
 bool validate(const dabhip_synth_cfg& cfg)
 {
   if (!validate_multiplex(cfg.nsub, cfg.sub)) return false;
+  if (cfg.dabplus_slots) {
+    if (cfg.nsub < 64 && (cfg.dabplus_slots >> cfg.nsub)) { set_error("synth: dabplus_slots names a slot past nsub"); return false; }
+    for (const dabhip_reconf_cfg& r : cfg.reconf)
+      if (r.at_cif != 0) { set_error("synth: dabplus_slots cannot be combined with reconfigurations"); return false; }
+    for (int k = 0; k < cfg.nsub; ++k)
+      if ((cfg.dabplus_slots >> k & 1) && to_subchannel(cfg.sub[k]).bitrate % 8) { set_error("synth: a DAB+ slot needs a multiple of 8 kbit/s"); return false; }
+  }
   int prev = 0;
   for (const dabhip_reconf_cfg& r : cfg.reconf) {
     if (r.at_cif == 0) continue;
@@ -105,8 +113,115 @@ bool validate(const dabhip_synth_cfg& cfg)
   return true;
 }
 
+// ---- DAB+ superframes (ETSI TS 102 563) --------------------------------------------------------------------------------------------------------
+const GfTables& gf()
+{
+  struct Init {
+    GfTables t;
+    Init() { gf_build(t); }
+  };
+  static const Init g;
+  return g.t;
+}
+
+inline uint8_t gf_mul(uint8_t a, uint8_t b)
+{
+  return (a && b) ? gf().exp[gf().log[a] + gf().log[b]] : 0;
+}
+
+// coefficients of prod_{i=0..9} (x + alpha^i), highest degree first (gen[0] = 1)
+const uint8_t* rs_generator()
+{
+  struct Init {
+    uint8_t g[kRsRoots + 1] = {1};
+    Init()
+    {
+      for (int i = 0; i < kRsRoots; ++i) {
+        const uint8_t r = gf().exp[i];
+        for (int k = i + 1; k >= 1; --k) g[k] ^= gf_mul(g[k - 1], r);
+      }
+    }
+  };
+  static const Init g;
+  return g.g;
+}
+
+// the 110 s unprotected bytes of superframe n of a DAB+ slot of 8 s kbit/s
+void dabplus_superframe(const dabhip_synth_cfg& cfg, int n, int slot, int s, uint8_t* out)
+{
+  const int total = kRsK * s;
+  const uint64_t pk = key(cfg.seed, kDomDabPlus, static_cast<uint64_t>(slot), ~0ull);   // the slot's audio parameters
+  static const int pairs[4][2] = {{0, 1}, {0, 0}, {1, 1}, {1, 0}};                      // (dac_rate, sbr_flag): 2, 4, 3, 6 AUs
+  const uint64_t rot = key(cfg.seed, kDomDabPlus, 64, ~0ull) + static_cast<uint64_t>(slot);               // consecutive slots: all four pairs
+  const int dac = pairs[rot & 3][0], sbr = pairs[rot & 3][1];
+  const int ch = static_cast<int>(pk >> 8 & 1), ps = static_cast<int>(pk >> 9 & 1);
+  int nau = 0, start0 = 0;
+  au_layout(dac, sbr, &nau, &start0);
+  const uint64_t sfk = (static_cast<uint64_t>(static_cast<uint32_t>(n)) << 8) | static_cast<uint64_t>(slot);
+  // AU lengths (each >= 3: one byte and the CRC): weights from the key; au_start is 12 bits, so all AUs but the last start below 4096
+  int64_t w[kMaxAus], wsum = 0, len[kMaxAus];
+  for (int i = 0; i < nau; ++i) { w[i] = 1 + static_cast<int64_t>(key(cfg.seed, kDomDabPlus, sfk, 1000 + i) & 255); wsum += w[i]; }
+  const int64_t extra = total - start0 - 3 * nau;
+  int64_t used = 0;
+  for (int i = 0; i < nau - 1; ++i) { len[i] = 3 + extra * w[i] / wsum; used += len[i]; }
+  const int64_t room = 4095 - start0 - 3 * (nau - 1);          // the last AU's start, start0 + used, must stay <= 4095
+  if (used - 3 * (nau - 1) > room) {
+    const int64_t ex = used - 3 * (nau - 1);
+    used = 0;
+    for (int i = 0; i < nau - 1; ++i) { len[i] = 3 + (len[i] - 3) * room / ex; used += len[i]; }
+  }
+  len[nau - 1] = total - start0 - used;
+  std::memset(out, 0, static_cast<size_t>(total));
+  out[2] = static_cast<uint8_t>((dac << 6) | (sbr << 5) | (ch << 4) | (ps << 3));   // rfa 0, mpeg_surround_config 0
+  int pos = start0;
+  uint64_t bits = 0;
+  for (int i = 0; i < nau; ++i) {
+    if (i) bits = (bits << 12) | static_cast<uint64_t>(pos);
+    const int body = static_cast<int>(len[i]) - 2;
+    for (int b = 0; b < body; b += 8) {
+      const uint64_t v = key(cfg.seed, kDomDabPlus, sfk, static_cast<uint64_t>(pos + b));
+      for (int q = 0; q < 8 && b + q < body; ++q) out[pos + b + q] = static_cast<uint8_t>(v >> (8 * q));
+    }
+    const uint16_t crc = static_cast<uint16_t>(~crc16_ccitt(out + pos, static_cast<size_t>(body)));
+    out[pos + body] = static_cast<uint8_t>(crc >> 8);
+    out[pos + body + 1] = static_cast<uint8_t>(crc & 0xff);
+    pos += static_cast<int>(len[i]);
+  }
+  const int nbits = 12 * (nau - 1), nbytes = (nbits + 7) / 8;
+  bits <<= 8 * nbytes - nbits;
+  for (int b = 0; b < nbytes; ++b) out[3 + b] = static_cast<uint8_t>(bits >> (8 * (nbytes - 1 - b)));
+  const uint16_t fc = fire_code(out + 2);
+  out[0] = static_cast<uint8_t>(fc >> 8);
+  out[1] = static_cast<uint8_t>(fc & 0xff);
+}
+
+// bytes [24 s part, 24 s (part + 1)) of the protected superframe n: data, then the parity of the s interleaved codewords (codeword j = bytes j + k s)
+void dabplus_protected_part(const dabhip_synth_cfg& cfg, int n, int part, int slot, int s, uint8_t* out)
+{
+  std::vector<uint8_t> sf(static_cast<size_t>(kRsN) * s);
+  dabplus_superframe(cfg, n, slot, s, sf.data());
+  const uint8_t* g = rs_generator();
+  for (int j = 0; j < s; ++j) {
+    uint8_t rem[kRsRoots] = {0};
+    for (int k = 0; k < kRsK; ++k) {
+      const uint8_t fb = sf[j + k * s] ^ rem[0];
+      for (int q = 0; q < kRsRoots - 1; ++q) rem[q] = rem[q + 1] ^ gf_mul(fb, g[q + 1]);
+      rem[kRsRoots - 1] = gf_mul(fb, g[kRsRoots]);
+    }
+    for (int q = 0; q < kRsRoots; ++q) sf[static_cast<size_t>(kRsK + q) * s + j] = rem[q];
+  }
+  std::memcpy(out, sf.data() + static_cast<size_t>(24) * s * part, static_cast<size_t>(24) * s);
+}
+
+int floor_div(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+
 void payload_bytes(const dabhip_synth_cfg& cfg, int cif, int slot, uint8_t* out, int n)
 {
+  if (cfg.dabplus_slots >> slot & 1) {                     // n = 24 s
+    const int rel = cif - cfg.dabplus_phase, sf = floor_div(rel, kSfFrames);
+    dabplus_protected_part(cfg, sf, rel - kSfFrames * sf, slot, n / 24, out);
+    return;
+  }
   for (int i = 0; i < n; i += 8) {
     uint64_t v = key(cfg.seed, kDomPayload, (static_cast<uint64_t>(static_cast<uint32_t>(cif)) << 8) | static_cast<uint64_t>(slot), static_cast<uint64_t>(i));
     for (int b = 0; b < 8 && i + b < n; ++b) out[i + b] = static_cast<uint8_t>(v >> (8 * b));
@@ -445,10 +560,24 @@ extern "C" int dabhip_synth_payload(const dabhip_synth_cfg* cfg, int cif_index, 
   if (!cfg) { set_error("synth_payload: bad slot"); return -1; }
   const Multiplex mux = multiplex_at(*cfg, cif_index, false);
   if (slot < 0 || slot >= mux.nsub) { set_error("synth_payload: bad slot"); return -1; }
+  if (cfg->dabplus_slots && !validate(*cfg)) return -1;
   const int n = to_subchannel(mux.sub[slot]).bitrate * 3;
   if (cap < n) { set_error("synth_payload: buffer too small"); return -1; }
   payload_bytes(*cfg, cif_index, slot, out, n);
   return n;
+}
+
+extern "C" int dabhip_synth_dabplus_superframe(const dabhip_synth_cfg* cfg, int sf_index, int slot, uint8_t* out, int cap)
+{
+  if (!cfg || !out || slot < 0 || slot >= cfg->nsub || slot >= 64 || !(cfg->dabplus_slots >> slot & 1)) {
+    set_error("synth_dabplus_superframe: not a DAB+ slot");
+    return -1;
+  }
+  if (!validate(*cfg)) return -1;
+  const int s = to_subchannel(cfg->sub[slot]).bitrate / 8;
+  if (cap < kRsK * s) { set_error("synth_dabplus_superframe: buffer too small"); return -1; }
+  dabplus_superframe(*cfg, sf_index, slot, s, out);
+  return kRsK * s;
 }
 
 extern "C" int dabhip_synth_fibs(const dabhip_synth_cfg* cfg, int cif_index, uint8_t* out96)

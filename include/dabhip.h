@@ -485,6 +485,50 @@ int dabhip_host_fifo_call(dabhip_fifo *f, int32_t coarse_timeshift, int32_t fine
  * Refused (-1) while a shift is pending or the first frame has not been dropped yet. */
 int dabhip_host_fifo_skip_unshifted(dabhip_fifo *f, int32_t ncalls, int64_t *fed, int64_t *consumed);
 
+/* ---- DAB+ audio (ETSI TS 102 563) ------------------------------------------------------- */
+/* A stateful consumer of ETI frames that extracts the AUs of DAB+ sub-channels on the GPU: superframe sync on the fire code, RS(120,110)
+ * correction of the s interleaved codewords of every superframe, AU CRCs.  Frames are pushed stream by stream; between pushes it keeps the last
+ * 4 frames of every stream and the sync state of every (stream, sub-channel), so batches, sessions' fetched frames and a pipe all go through it.
+ *
+ * Sync rule, per (stream, sub-channel), walking the frames in order: unsynced, frame f starts a superframe if the raw (uncorrected) fire code
+ * of its first 11 bytes passes and frames f..f+4 carry the sub-channel with the same STL (a multiple of 3 up to 216: 8 STL = 24 s bytes, s <= 72) and consecutive
+ * FCTs (mod 250).  Synced, every 5th frame starts a candidate, whose frames must carry the locked STL with FCTs continuing the last
+ * superframe's.  A gap or an STL change loses sync (the search restarts at that candidate's first frame); so does the 3rd consecutive candidate
+ * whose raw fire code fails (the search restarts at the frame after it).  A candidate that loses sync is not decoded. */
+typedef struct dabhip_dabplus dabhip_dabplus;
+typedef struct dabhip_dabplus_sf {  /* one superframe of the last push */
+  int32_t stream;
+  int32_t sub;                      /* index into the SubChId list */
+  int32_t fct;                      /* FCT of its first ETI frame */
+  int32_t s;                        /* sub-channel rate / 8 kbit/s: 120 s bytes, 110 s of them audio */
+  uint8_t fire_ok;                  /* fire code of the corrected bytes good */
+  uint8_t layout_ok;                /* fire code good, au_start strictly increasing, every AU >= 3 bytes and inside 110 s */
+  uint8_t rfa, dac_rate, sbr_flag, aac_channel_mode, ps_flag, mpeg_surround_config;
+  int32_t num_aus;                  /* from (dac_rate, sbr_flag): 2, 3, 4 or 6 */
+  uint16_t au_start[6];             /* AU offsets in the superframe (layout_ok only) */
+  uint16_t au_len[6];               /* AU lengths including their 2 CRC bytes */
+  uint32_t crc_ok;                  /* bit i: CRC of AU i good */
+  int32_t rs_corrected;             /* bytes corrected by the RS decoder */
+  int32_t rs_failed;                /* codewords beyond correction (left as received) */
+} dabhip_dabplus_sf;
+/* nsub SubChIds, the same for every stream.  NULL when there is no GPU (dabhip_last_error). */
+dabhip_dabplus *dabhip_dabplus_create(int device, int nstreams, const int32_t *subch_ids, int nsub);
+void dabhip_dabplus_destroy(dabhip_dabplus *d);
+/* counts[s] ETI frames of stream s, stream after stream in `frames` (dabhip_engine_eti_device_ptr's layout): DEVICE memory when on_device != 0,
+ * host memory otherwise.  Returns the superframes completed by this call, <0 on error. */
+int64_t dabhip_dabplus_push(dabhip_dabplus *d, const uint8_t *frames, const int64_t *counts, int on_device);
+/* The superframes of the last push of one (stream, sub-channel index), in order: copies min(n, cap) records, returns n. */
+int64_t dabhip_dabplus_superframes(const dabhip_dabplus *d, int stream, int sub, dabhip_dabplus_sf *out, int64_t cap);
+/* Their corrected 110 s audio bytes, superframe after superframe (cap bytes at most); returns the byte count. */
+int64_t dabhip_dabplus_data(const dabhip_dabplus *d, int stream, int sub, uint8_t *dst, int64_t cap);
+/* Their AUs whose CRC is good, without the CRC bytes, one after another (boundaries: the records); returns the byte count. */
+int64_t dabhip_dabplus_au_bytes(const dabhip_dabplus *d, int stream, int sub, uint8_t *dst, int64_t cap);
+/* Counters since creation: superframes, fire-code fails, RS corrected bytes, RS failed codewords, AUs (of superframes with a good layout), AU
+ * CRC fails, sync losses.  Returns 0, <0 on error. */
+int dabhip_dabplus_stats(const dabhip_dabplus *d, int stream, int sub, int64_t *counters7);
+/* GPU time of the last push in ms, stage by stage (names: "locate", "sync", "rs", "au", "carry"; as dabhip_engine_stage_ms); returns the count. */
+int dabhip_dabplus_stage_ms(const dabhip_dabplus *d, const char **names, float *ms, int cap);
+
 /* ---- synthetic Mode-I modulator (host only) --------------------------------------------- */
 typedef struct dabhip_subch_cfg {
   int32_t id;          /* SubChId 0..63 */
@@ -543,6 +587,13 @@ typedef struct dabhip_synth_cfg {
   /* Channel between modulator and receiver (round 5; all zero = the ideal channel of rounds 1-4, byte-identical captures).  Host generator only:
    * dabhip_synth_generate_device refuses a configuration with any of these set. */
   dabhip_channel_cfg channel;
+  /* DAB+ content (ETSI TS 102 563; all zero = off, byte-identical captures): bit k set = slot k carries audio superframes instead of keyed
+   * random bytes.  Superframe n of a slot spans logical CIFs dabplus_phase + 5 n .. + 4 (n may be negative: every CIF belongs to one).  Each slot
+   * draws its audio parameters from its key -- consecutive slots cycle through the four (dac_rate, sbr_flag) pairs, i.e. 2 / 3 / 4 / 6 AUs --
+   * and each superframe its AU lengths and content; the synth computes the AU CRCs, the fire code and the RS parity, and interleaves.  The
+   * slots' bit rates must be multiples of 8 kbit/s; refused together with reconfigurations. */
+  uint64_t dabplus_slots;
+  int32_t dabplus_phase;
 } dabhip_synth_cfg;
 
 /* preset 0: 12 sub-channels, 1136 kbit/s, 862 CU (the benchmark mix); 1: 4 light sub-channels. */
@@ -557,6 +608,9 @@ int64_t dabhip_synth_generate(const dabhip_synth_cfg *cfg, int ntf, uint8_t *iq,
 int dabhip_synth_payload(const dabhip_synth_cfg *cfg, int cif_index, int slot, uint8_t *out, int cap);
 /* The 96 FIB bytes (3 FIBs with CRC) carried by CIF n. */
 int dabhip_synth_fibs(const dabhip_synth_cfg *cfg, int cif_index, uint8_t *out96);
+/* The unprotected 110 s bytes of DAB+ superframe sf_index of slot (a dabplus_slots slot of 8 s kbit/s): fire code, header, au_start, the AUs
+ * with their CRCs -- before the RS parity and the interleaving that dabhip_synth_payload's bytes carry.  Returns 110 s, <0 on error. */
+int dabhip_synth_dabplus_superframe(const dabhip_synth_cfg *cfg, int sf_index, int slot, uint8_t *out, int cap);
 /* Device-side modulator (needs a GPU): the ensembles cfgs[0..nstreams) modulated on `device`
  * straight into DEVICE buffers iq[i] of dabhip_synth_bytes(&cfgs[i], ntf) bytes each.  The bit content comes from the
  * same generator as dabhip_synth_generate; samples may differ from the host generator's by one LSB where fp32 and
