@@ -239,6 +239,11 @@ _SIGNATURES = {
     "dabhip_stream_eti_fetch": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64]),
     "dabhip_stream_eti_fetch_wait": (C.c_int, [C.c_void_p]),
     "dabhip_engine_demapped_tf": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int8), C.POINTER(C.c_int8)]),
+    "dabhip_engine_set_demod_all": (C.c_int, [C.c_void_p, C.c_int]),
+    "dabhip_engine_msc_deferred": (C.c_int, [C.c_void_p]),
+    "dabhip_stream_set_demod_all": (C.c_int, [C.c_void_p, C.c_int]),
+    "dabhip_stream_msc_deferred": (C.c_int, [C.c_void_p]),
+    "dabhip_host_lockin_deferred": (C.c_int, [C.c_int, C.c_int, C.c_int]),
 }
 
 _lib = None
@@ -467,6 +472,11 @@ def host_eti_header(hdr, sub):
     n = lib().dabhip_host_eti_header(hdr.ctypes.data_as(C.POINTER(C.c_int32)), sub.ctypes.data_as(C.POINTER(C.c_int32)), _p(out), out.size)
     _need(n > 0, "host_eti_header")
     return out[:n].copy()
+
+
+def host_lockin_deferred(locked, okcount, ntf):
+    """The lock-in rule (dabhip.h): how many of the next ntf TFs of a stream cannot be locked, given the back end's state in front of them."""
+    return int(lib().dabhip_host_lockin_deferred(1 if locked else 0, int(okcount), int(ntf)))
 
 
 def host_control_replay(fibs, crc_ok):
@@ -813,6 +823,16 @@ class Engine:
     def set_fused(self, enable):
         """True (default): one kernel for OFDM transform + demap (spectra never written); False: K2 + K2b.  Identical output."""
         _need(lib().dabhip_engine_set_fused(self._h, 1 if enable else 0) == 0, "set_fused")
+
+    def set_demod_all(self, on):
+        """Lock-in skip off switch: True = the MSC symbols of every TF are demodulated, also of those that cannot be locked (dabhip.h).  Identical ETI."""
+        _need(lib().dabhip_engine_set_demod_all(self._h, 1 if on else 0) == 0, "set_demod_all")
+
+    def msc_deferred(self):
+        """TFs of the last decode whose MSC symbols were deferred by the lock-in skip (demapped_tf completes them on demand)."""
+        n = lib().dabhip_engine_msc_deferred(self._h)
+        _need(n >= 0, "msc_deferred")
+        return n
 
     def set_sync_speculation(self, mode):
         """K1's chain: 0 = call after call, 1 = with the look-ahead pass, -1 (default) = the pass for small batches.  Identical results."""
@@ -1163,6 +1183,16 @@ class Stream:
     def set_parity_guard(self, level=True):
         """see Engine.set_parity_guard"""
         _need(self._f("set_parity_guard")(self._h, _guard_level(level)) == 0, "stream_set_parity_guard")
+
+    def set_demod_all(self, on):
+        """see Engine.set_demod_all (single-device sessions)"""
+        _need(lib().dabhip_stream_set_demod_all(self._h, 1 if on else 0) == 0, "stream_set_demod_all")
+
+    def msc_deferred(self):
+        """TFs of the segment fed last whose MSC symbols were deferred by the lock-in skip (single-device sessions)."""
+        n = lib().dabhip_stream_msc_deferred(self._h)
+        _need(n >= 0, "stream_msc_deferred")
+        return n
 
     def log(self, stream):
         """The reference's operator messages for one stream since the last call (dabhip_stream_log): 'Locked', 'Lock lost, resetting ringbuffer', ensemble dump."""

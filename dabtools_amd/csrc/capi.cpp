@@ -379,6 +379,20 @@ int dabhip_engine_set_fused(dabhip_engine* e, int enable)
   for (auto& l : e->lanes) l->set_fused(enable != 0);
   return 0;
 }
+int dabhip_engine_set_demod_all(dabhip_engine* e, int on)
+{
+  if (!e) return -1;
+  for (auto& l : e->lanes) l->set_demod_all(on != 0);
+  return 0;
+}
+int dabhip_engine_msc_deferred(const dabhip_engine* e)
+{
+  if (!e) return -1;
+  int n = 0;
+  const int nl = e->lane_of.size() >= 64 ? static_cast<int>(e->lanes.size()) : 1;
+  for (int l = 0; l < nl; ++l) n += e->lanes[l]->msc_deferred();
+  return n;
+}
 int dabhip_engine_set_sync_speculation(dabhip_engine* e, int mode)
 {
   if (!e) return -1;
@@ -654,6 +668,7 @@ int dabhip_host_parse_fibs(const uint8_t* fibs, const uint8_t* crc_ok, int32_t* 
   return 0;
 }
 
+int dabhip_host_lockin_deferred(int locked, int okcount, int ntf) { return lockin_deferred(locked != 0, okcount, ntf); }
 int dabhip_host_eti_header(const int32_t* hdr3, const int32_t* sub, uint8_t* out, int cap)
 {
   if (!hdr3 || !sub || !out || cap < kEtiHeaderMax) { set_error("host_eti_header: bad argument"); return -1; }
@@ -937,6 +952,8 @@ extern "C" int dabhip_stream_set_subchannels(dabhip_stream* s, const int32_t* id
 extern "C" int dabhip_stream_set_afc(dabhip_stream* s, int on) { if (!s) return -1; s->eng.set_afc(on != 0); return 0; }
 extern "C" int dabhip_stream_set_parity_guard(dabhip_stream* s, int on) { if (!s) return -1; s->eng.set_parity_guard(on); return 0; }
 extern "C" int dabhip_stream_set_sync_speculation(dabhip_stream* s, int mode) { if (!s) return -1; s->eng.set_sync_speculation(mode); return 0; }
+extern "C" int dabhip_stream_set_demod_all(dabhip_stream* s, int on) { if (!s) return -1; s->eng.set_demod_all(on != 0); return 0; }
+extern "C" int dabhip_stream_msc_deferred(const dabhip_stream* s) { return s ? s->eng.msc_deferred() : -1; }
 extern "C" int dabhip_stream_set_soft(dabhip_stream* s, int on)
 {
   if (!s) return -1;

@@ -219,6 +219,17 @@ inline uint32_t layout_fault(const std::vector<SubChannel>& active, int header_l
   return f;
 }
 
+// How many of the next n TFs of a stream cannot be locked whatever their FIBs say, given the lock state in front of them (dab.c:46-52: lock needs
+// okcount >= 10, one step per TF with 12 of 12 good FIBs).  dab_process_frame returns before it touches the MSC data of an unlocked TF (dab.c:64),
+// the 16-CIF ring starts with the TF that reaches lock and a loss drops it: the MSC symbols of those TFs are never read, so the OFDM stage need not
+// demodulate them.  Once locked everything is demodulated: a loss in mid-decode is not known before the FIC is decoded.
+inline int lockin_deferred(bool locked, int okcount, int n)
+{
+  if (locked || n <= 0) return 0;
+  const int dead = 9 - okcount;
+  return dead <= 0 ? 0 : (dead < n ? dead : n);
+}
+
 class ControlPlane {
  public:
   ControlPlane()
@@ -295,6 +306,7 @@ class ControlPlane {
   }
 
   bool locked() const { return locked_; }
+  int okcount() const { return okcount_; }           // consecutive TFs with 12 of 12 good FIBs up to here
   uint32_t fault() const { return fault_; }          // StreamFault bits seen so far (sticky)
   const std::vector<std::vector<SubChannel>>& layouts() const { return layouts_; }
   // streaming use: CIF indices are rebased when old TF slots are dropped

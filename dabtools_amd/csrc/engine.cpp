@@ -392,7 +392,8 @@ bool Engine::recycle_tf_slots(int used_slots, int keep_slots)
 // What the OFDM stage of the LAST decode() / feed() left for transmission frame `tf` (0-based among the stream's TF slots of that
 // decode, carried slots of a session first) of `stream`: the content of tf->fic_symbols_demapped / msc_symbols_demapped (dab.h:27-33)
 // as the batch path holds it -- FIC row in natural order, MSC values gathered back out of the planar logical rows the demapper
-// scattered them into.  Hard decisions: 0 / 1; soft decisions: the signed 4-bit values.
+// scattered them into.  Hard decisions: 0 / 1; soft decisions: the signed 4-bit values.  A TF whose MSC part the decode deferred (lock-in skip) is
+// completed first, together with all other deferred TFs of that decode.
 bool Engine::read_demapped_tf(int stream, int tf, int8_t* fic_out, int8_t* msc_out)
 {
   static const int tmap[16] = {0, 8, 4, 12, 2, 10, 6, 14, 1, 9, 5, 13, 3, 11, 7, 15};
@@ -401,6 +402,14 @@ bool Engine::read_demapped_tf(int stream, int tf, int8_t* fic_out, int8_t* msc_o
     return false;
   }
   if (!check(hipSetDevice(device_), "hipSetDevice")) return false;
+  // lock-in skip: the MSC part of this TF was deferred -- complete the last decode's deferred frames first (once; all of them)
+  if (static_cast<size_t>(stream) < msc_missing_.size() && static_cast<size_t>(tf) < msc_missing_[stream].size() && msc_missing_[stream][tf]) {
+    if (!msc_pending_ || tf < last_keep_[stream]) {
+      set_error("demapped_tf: the MSC symbols of this transmission frame were not demodulated (it could not be locked) and its samples belong to an earlier segment");
+      return false;
+    }
+    if (!complete_deferred()) return false;
+  }
   const int bits = soft_bits_ ? 4 : 1, per = 32 / bits;
   const size_t fic_words = static_cast<size_t>(kFicWords) * bits, row_words = static_cast<size_t>(kCifWords) * bits, plane_words = 108u * bits;
   std::vector<uint32_t> f(fic_words), rows(static_cast<size_t>(kRowLead + 4) * row_words);
@@ -1044,6 +1053,82 @@ bool Engine::scan_streams(const uint8_t* const* iq, const size_t* nbytes, int ns
   return true;
 }
 
+// The one-kernel OFDM stage over frames [first, first + n) of the frame list, data symbols [sym_a, sym_b), nparts workgroups per frame
+bool Engine::fused_parts(int first, int n, int sym_a, int sym_b, int nparts)
+{
+  if (soft_bits_ != 0)
+    return check(launch_ofdm_demap_fused_soft(afc_, d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), first, n, d_twf_.get(), d_frame_slot_.get(),
+                                              d_frame_cif_row_.get(), d_qpsk_.get(), d_fic_bits_.get(), d_msc_bits_.get(), stream_, sym_a, sym_b, nparts),
+                 "fused fft/demap launch");
+  const bool guard = guard_active();
+  GuardArgs ga{};
+  if (guard && !guard_begin(n, &ga)) return false;
+  const bool launched =
+      guard ? check(launch_ofdm_demap_fused_guarded(d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), first, n, d_twf_.get(), d_frame_slot_.get(),
+                                                    d_frame_cif_row_.get(), d_qpsk_.get(), d_fic_bits_.get(), d_msc_bits_.get(), ga, stream_, sym_a, sym_b, nparts),
+                    "fused fft/demap launch")
+            : check(launch_ofdm_demap_fused_plain(afc_, d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), first, n, d_twf_.get(), d_frame_slot_.get(),
+                                                  d_frame_cif_row_.get(), d_qpsk_.get(), d_fic_bits_.get(), d_msc_bits_.get(), stream_, sym_a, sym_b, nparts),
+                    "fused fft/demap launch");
+  return launched && (!guard || guard_finish(true, first, n, sym_a, sym_b, false));
+}
+
+// K2 + K2b over the 72 MSC symbols of frames [first, first + n) in chunks (the two-kernel stage's chunks share one spectra buffer; stream order keeps
+// them apart), timed with per-chunk events.  The FIC symbols of those frames ran before (stage A of decode_impl).
+bool Engine::ofdm_msc_part(int first, int n, int chunk, int ev_base)
+{
+  const bool guard = guard_active(), soft = soft_bits_ != 0, energies = guard || soft;
+  GuardArgs soft_args{};                                  // soft decisions, two-kernel stage: K2b reads the energies, lists nothing
+  soft_args.delta = d_delta_.get();
+  soft_args.delta_stride = kSymbolsPerTf;
+  soft_args.c = kSoftNormC;
+  bool gpu_ok = true;
+  for (int c = 0; c * chunk < n && gpu_ok; ++c) {
+    const int f0 = first + c * chunk, nf = std::min(chunk, n - c * chunk);
+    hipEvent_t* const ev = ev_base >= 0 ? &chunk_ev_[static_cast<size_t>(3) * (ev_base + c)] : nullptr;
+    gpu_ok = !ev || record(ev[0], stream_);
+    if (fused_) {
+      // the 72 MSC symbols (the FIC symbols ran before the FIC decode was queued); workgroups per frame: measurement knob
+      static const int msc_wgs = std::getenv("DABHIP_FUSED_MSC_WGS") ? std::max(1, std::min(8, std::atoi(std::getenv("DABHIP_FUSED_MSC_WGS")))) : 1;
+      gpu_ok = gpu_ok && fused_parts(f0, nf, 4, 76, msc_wgs);
+      gpu_ok = gpu_ok && (!ev || record(ev[1], stream_));
+    } else {
+      GuardArgs ga = soft ? soft_args : GuardArgs{};   // (hard decisions: a non-null delta switches the guard's listing on)
+      if (guard && !guard_begin(nf, &ga)) return false;
+      // with the guard on (or soft decisions), K2 also leaves the per-symbol sample energies K2b decides with
+      gpu_ok = gpu_ok && check(launch_ofdm_fft(d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), f0, nf, d_spectra_.get(), d_twf_.get(), stream_,
+                                               energies ? d_delta_.get() : nullptr, soft ? kSoftNormC : guard_c_of(guard_rule_level())),
+                               "fft launch");
+      gpu_ok = gpu_ok && (!ev || record(ev[1], stream_));
+      gpu_ok = gpu_ok && check(launch_demap(true, soft_bits_, d_spectra_.get(), f0, nf, d_frame_slot_.get(), d_frame_cif_row_.get(), d_qpsk_.get(), d_fic_bits_.get(), d_msc_bits_.get(), ga, stream_), "demap launch");
+      if (guard) gpu_ok = gpu_ok && guard_finish(true, f0, nf, 1, kSymbolsPerTf, true);     // timed with the demapper; the FIC symbols belong to the pre-pass
+    }
+    gpu_ok = gpu_ok && (!ev || record(ev[2], stream_));
+  }
+  return gpu_ok;
+}
+
+// read_demapped_tf asked for a TF whose MSC part the last decode deferred: that part now, over all deferred frames of that decode -- its frame list, call
+// descriptors and IQ pointers are still on the device (the engine's own upload buffer outlives the decode; device-resident input must still be where it was).
+bool Engine::complete_deferred()
+{
+  const int first = last_msc_n_, n = last_ntf_ - last_msc_n_;
+  if (!msc_pending_ || n <= 0) return true;
+  if (!fused_ && !d_spectra_.reserve(static_cast<size_t>(last_chunk_) * kSymbolsPerTf * 2048)) return false;
+  const bool guard = guard_active();
+  guard_counters_clear_ = false;
+  guard_launches_ = 0;
+  bool gpu_ok = ofdm_msc_part(first, n, last_chunk_, -1);
+  if (guard && gpu_ok) gpu_ok = guard_download();
+  const bool drained = check(hipStreamSynchronize(stream_), "deferred MSC symbols");      // also on the error path: nothing may stay in flight
+  if (!gpu_ok || !drained) return false;
+  if (guard && !guard_check()) return false;
+  msc_pending_ = false;
+  for (size_t b = 0; b < msc_missing_.size(); ++b)
+    std::fill(msc_missing_[b].begin() + std::min<size_t>(static_cast<size_t>(last_keep_[b]), msc_missing_[b].size()), msc_missing_[b].end(), uint8_t(0));
+  return true;
+}
+
 int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int nstreams, bool on_device, bool cont, bool full_scan)
 {
   if (!ok_) { set_error("engine not initialised (no GPU?)"); return -1; }
@@ -1060,17 +1145,19 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
   guard_flagged_ = guard_decisions_ = 0;
   guard_launches_ = 0;
   guard_overflows_ = 0;
+  msc_pending_ = false;                      // the scan overwrites the descriptors the deferred frames of the last decode would be completed from
+  msc_deferred_ = 0;
   if (!begin_decode(nstreams, cont)) return -1;
   struct SideStreamGuard {                   // whatever was queued on the side stream is awaited before returning
     hipStream_t s;
     ~SideStreamGuard() { (void)hipStreamSynchronize(s); }
   } side_guard{copy_stream_};
   mark("begin_decode done");
-  // frame list: demodulated TFs, stream-major.  Slots and logical CIF rows of a stream: first the ones carried over from
+  // frame list: demodulated TFs, stream-major within each of its two parts (see the layout).  Slots and logical CIF rows of a stream: first the ones carried over from
   // the previous segment of a session (the last <= 4 TFs), then this segment's.  Built (and uploaded) by the scan as soon as the
   // calls' {status, ordinal} are known, i.e. while K1's verification kernel still runs.
-  std::vector<int> tf_base(nstreams + 1, 0), row_base(nstreams), fib_base(nstreams), nnew(nstreams, 0);
-  int next_row = 0, ntf_new = 0;
+  std::vector<int> tf_base(nstreams + 1, 0), row_base(nstreams), fib_base(nstreams), nnew(nstreams, 0), ndefer_of(nstreams, 0);
+  int next_row = 0, ntf_new = 0, nmsc = 0;
   float frames_ms = 0;
   auto layout = [&]() -> bool {
     const auto tfr = std::chrono::steady_clock::now();
@@ -1079,25 +1166,41 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
     next_row = 0;
     ntf_new = 0;
     tf_base[0] = 0;
+    // Lock-in skip: the leading TFs of a stream that cannot be locked (lockin_deferred; a fresh decode's planes are reset later, inside the control-plane
+    // pass: their content here is stale) go to the END of the list, [nmsc, ntf_new): the FIC launches run over the whole list, the MSC launches over
+    // [0, nmsc).  Slots and rows are what they would be without the skip; no reader of the list relies on its order (every kernel goes from the list
+    // entry to stream, call, slot and row; the guard's entries carry list indices of the launch that wrote them).
+    int ndefer = 0;
     for (int b = 0; b < nstreams; ++b) {
-      const int keep = carry_keep_[b], j0 = ntf_new;
+      const int ncalls = static_cast<int>(nbytes[b] / kChunkBytes) - calls_done_[b];
+      int n = 0;
+      for (int k = 0; k < ncalls; ++k) n += h_info_[static_cast<size_t>(b) * max_calls_ + k].x == 2 ? 1 : 0;
+      nnew[b] = n;
+      ndefer_of[b] = demod_all_ ? 0 : (planes_fresh_ ? lockin_deferred(false, 0, n) : lockin_deferred(planes_[b].locked(), planes_[b].okcount(), n));
+      ntf_new += n;
+      ndefer += ndefer_of[b];
+    }
+    nmsc = ntf_new - ndefer;
+    int at_msc = 0, at_defer = nmsc;
+    for (int b = 0; b < nstreams; ++b) {
+      const int keep = carry_keep_[b];
       const int ncalls = static_cast<int>(nbytes[b] / kChunkBytes) - calls_done_[b];
       row_base[b] = next_row + kRowLead;      // each stream gets 15 lead-in rows for the scatter of its first CIFs
       for (int k = 0; k < ncalls; ++k) {
         const int2 d = h_info_[static_cast<size_t>(b) * max_calls_ + k];     // {status, ordinal}
         if (d.x == 2) {
           const int local = keep + (d.y - ord_done_[b]);
-          h_frames_[ntf_new] = make_int2(b, k);
-          h_frame_slot_[ntf_new] = tf_base[b] + local;
-          h_frame_cif_row_[ntf_new] = row_base[b] + 4 * local;
-          ++ntf_new;
+          const int at = local - keep < ndefer_of[b] ? at_defer++ : at_msc++;
+          h_frames_[at] = make_int2(b, k);
+          h_frame_slot_[at] = tf_base[b] + local;
+          h_frame_cif_row_[at] = row_base[b] + 4 * local;
         }
       }
-      nnew[b] = ntf_new - j0;
       tf_base[b + 1] = tf_base[b] + keep + nnew[b];
       fib_base[b] = 4 * tf_base[b];
       next_row += kRowLead + 4 * (keep + nnew[b]);
     }
+    if (at_msc != nmsc || at_defer != ntf_new) { set_error("decode: the calls' ordinals do not number this segment's transmission frames"); return false; }
     // the three lists go up in ONE launch that reads the page-locked arrays itself (three copy-engine copies cost 45 us of idle GPU before the first
     // OFDM launch); with the guard on it also clears the guard's counters, which guard_begin() then leaves alone
     bool up = true;
@@ -1140,22 +1243,6 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
   uint8_t* fibs = nullptr;
   uint8_t* ok = nullptr;
   GuardArgs soft_args{};                                  // soft decisions, two-kernel stage: K2b reads the energies, lists nothing
-  auto fused_parts = [&](int first, int n, int sym_a, int sym_b, int nparts) -> bool {
-    if (soft)
-      return check(launch_ofdm_demap_fused_soft(afc_, d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), first, n, d_twf_.get(), d_frame_slot_.get(),
-                                                d_frame_cif_row_.get(), d_qpsk_.get(), d_fic_bits_.get(), d_msc_bits_.get(), stream_, sym_a, sym_b, nparts),
-                   "fused fft/demap launch");
-    GuardArgs ga{};
-    if (guard && !guard_begin(n, &ga)) return false;
-    const bool launched =
-        guard ? check(launch_ofdm_demap_fused_guarded(d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), first, n, d_twf_.get(), d_frame_slot_.get(),
-                                                      d_frame_cif_row_.get(), d_qpsk_.get(), d_fic_bits_.get(), d_msc_bits_.get(), ga, stream_, sym_a, sym_b, nparts),
-                      "fused fft/demap launch")
-              : check(launch_ofdm_demap_fused_plain(afc_, d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), first, n, d_twf_.get(), d_frame_slot_.get(),
-                                                    d_frame_cif_row_.get(), d_qpsk_.get(), d_fic_bits_.get(), d_msc_bits_.get(), stream_, sym_a, sym_b, nparts),
-                      "fused fft/demap launch");
-    return launched && (!guard || guard_finish(true, first, n, sym_a, sym_b, false));
-  };
   auto stage_a = [&]() -> bool {
     ntf = ntf_new;
     nslots = tf_base[nstreams];
@@ -1208,35 +1295,15 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
   // away and shares the GPU with them, waiting neither for the download nor for the host
   if (!fic_decode_slots_async(0, nslots, fibs, ok, copy_stream_)) return -1;      // carried slots are decoded again: their FIBs are read by K5
 
-  // K2 + K2b in chunks (they share one spectra buffer; stream order keeps them apart), timed with per-chunk events
+  // K2 + K2b over the MSC symbols of the frames that can be locked: [0, nmsc) of the list (ofdm_msc_part); the deferred ones stay as they are
   bool gpu_ok = true;
-  const int nchunks = (ntf + chunk - 1) / chunk;
+  const int nchunks = (nmsc + chunk - 1) / chunk;
   while (static_cast<int>(chunk_ev_.size()) < 3 * nchunks) {
     hipEvent_t e = nullptr;
     if (!check(hipEventCreate(&e), "hipEventCreate")) { gpu_ok = false; break; }
     chunk_ev_.push_back(e);
   }
-  for (int c = 0; c < nchunks && gpu_ok; ++c) {
-    const int first = c * chunk, n = std::min(chunk, ntf - first);
-    gpu_ok = record(chunk_ev_[3 * c], stream_);
-    if (one_kernel) {
-      // the 72 MSC symbols (the FIC symbols ran before the FIC decode was queued); workgroups per frame: measurement knob
-      static const int msc_wgs = std::getenv("DABHIP_FUSED_MSC_WGS") ? std::max(1, std::min(8, std::atoi(std::getenv("DABHIP_FUSED_MSC_WGS")))) : 1;
-      gpu_ok = gpu_ok && fused_parts(first, n, 4, 76, msc_wgs);
-      gpu_ok = gpu_ok && record(chunk_ev_[3 * c + 1], stream_);
-    } else {
-      GuardArgs ga = soft ? soft_args : GuardArgs{};   // (hard decisions: a non-null delta switches the guard's listing on)
-      if (guard && !guard_begin(n, &ga)) { gpu_ok = false; break; }
-      // with the guard on (or soft decisions), K2 also leaves the per-symbol sample energies K2b decides with
-      gpu_ok = gpu_ok && check(launch_ofdm_fft(d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), first, n, d_spectra_.get(), d_twf_.get(), stream_,
-                                               energies ? d_delta_.get() : nullptr, soft ? kSoftNormC : guard_c_of(guard_rule_level())),
-                               "fft launch");
-      gpu_ok = gpu_ok && record(chunk_ev_[3 * c + 1], stream_);
-      gpu_ok = gpu_ok && check(launch_demap(true, soft_bits_, d_spectra_.get(), first, n, d_frame_slot_.get(), d_frame_cif_row_.get(), d_qpsk_.get(), d_fic_bits_.get(), d_msc_bits_.get(), ga, stream_), "demap launch");
-      if (guard) gpu_ok = gpu_ok && guard_finish(true, first, n, 1, kSymbolsPerTf, true);     // timed with the demapper; the FIC symbols belong to the pre-pass
-    }
-    gpu_ok = gpu_ok && record(chunk_ev_[3 * c + 2], stream_);
-  }
+  gpu_ok = gpu_ok && ofdm_msc_part(0, nmsc, chunk, 0);
   mark("ofdm queued");
   if (!check(hipEventSynchronize(ev_fibs_), "fic decode")) return -1;
   mark("fibs on host");
@@ -1319,17 +1386,31 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
     times_.demap += d;
     fft_ms_ += a;
     fft_launches_ += 1;
-    fft_tfs_ += std::min(chunk, ntf - c * chunk);
+    fft_tfs_ += std::min(chunk, nmsc - c * chunk);
   }
   msc_collect();
   if (!on_device && times_.h2d_bytes > 0 && !elapsed(&times_.h2d, ev_h2d_[0], ev_h2d_[1])) return -1;
   if (guard && !guard_check()) return -1;
   // what the next segment of a session starts from
+  msc_missing_.resize(nstreams);
+  last_keep_.assign(nstreams, 0);
   for (int b = 0; b < nstreams; ++b) {
+    // carried slots keep their flag (a deferred TF of an earlier segment cannot be completed any more), this segment's deferred ones get theirs
+    std::vector<uint8_t>& miss = msc_missing_[b];
+    const int keep = carry_keep_[b];
+    miss.resize(static_cast<size_t>(prev_used_[b]), 0);
+    miss.erase(miss.begin(), miss.end() - keep);
+    miss.resize(static_cast<size_t>(keep + nnew[b]), 0);
+    std::fill(miss.begin() + keep, miss.begin() + keep + ndefer_of[b], uint8_t(1));
+    last_keep_[b] = keep;
     prev_used_[b] = carry_keep_[b] + nnew[b];
     carry_keep_[b] = std::min(4, prev_used_[b]);
     ord_done_[b] += nnew[b];
   }
+  last_msc_n_ = nmsc;
+  last_chunk_ = chunk;
+  msc_deferred_ = ntf - nmsc;
+  msc_pending_ = msc_deferred_ > 0;
   prev_tf_base_ = tf_base;
   prev_row_base_ = row_base;
   times_.wall = since(wall0);
@@ -1465,6 +1546,7 @@ int Engine::stage_ofdm_fft(const uint8_t* frames, int nframes, float* spectra, b
   }
   std::vector<const uint8_t*> ptrs = {d_in};
   const size_t nspec = static_cast<size_t>(nframes) * kSymbolsPerTf * 2048;
+  msc_pending_ = false;             // the last decode's frame list and descriptors are gone: its deferred TFs can no longer be completed
   if (!d_iq_ptrs_.upload(ptrs, stream_) || !d_descs_.upload(descs, stream_) || !d_frames_.upload(list, stream_) || !d_spectra_.reserve(nspec)) return -1;
   reps = std::max(reps, 1);
   // one untimed launch first when timing
@@ -1557,6 +1639,7 @@ int Engine::stage_decision_audit(const uint8_t* frames, int nframes, bool on_dev
     }
     std::vector<const uint8_t*> ptrs = {d_in};
     max_calls_ = n;
+    msc_pending_ = false;             // the last decode's frame list and descriptors are gone: its deferred TFs can no longer be completed
     if (!reserve_tf_slots(n) || !d_iq_ptrs_.upload(ptrs, stream_) || !d_descs_.upload(descs, stream_) || !d_frames_.upload(list, stream_) ||
         !d_frame_slot_.upload(slots, stream_) || !d_frame_cif_row_.upload(rows, stream_) || !d_spectra_.reserve(static_cast<size_t>(n) * kSymbolsPerTf * 2048))
       return -1;
@@ -1619,6 +1702,7 @@ int Engine::stage_decision_audit_fused(const uint8_t* frames, int nframes, bool 
     }
     std::vector<const uint8_t*> ptrs = {d_in};
     max_calls_ = n;
+    msc_pending_ = false;             // the last decode's frame list and descriptors are gone: its deferred TFs can no longer be completed
     if (!reserve_tf_slots(n) || !d_iq_ptrs_.upload(ptrs, stream_) || !d_descs_.upload(descs, stream_) || !d_frames_.upload(list, stream_) ||
         !d_frame_slot_.upload(slots, stream_) || !d_frame_cif_row_.upload(rows, stream_) || !d_delta_.reserve(static_cast<size_t>(n) * kSymbolsPerTf))
       return -1;
@@ -1748,6 +1832,7 @@ bool Engine::demod_one_frame(const uint8_t* iq_virtual_base, const CallDesc& des
   std::vector<int2> list = {make_int2(0, 0)};
   std::vector<int> slots = {0};
   std::vector<CallDesc> d = {desc};
+  msc_pending_ = false;             // the last decode's frame list and descriptors are gone: its deferred TFs can no longer be completed
   if (!reserve_tf_slots(1) || !d_iq_ptrs_.upload(ptrs, stream_) || !d_descs_.upload(d, stream_) || !d_frames_.upload(list, stream_) ||
       !d_frame_slot_.upload(slots, stream_) || !d_frame_cif_row_.upload(slots, stream_) ||
       !d_spectra_.reserve(static_cast<size_t>(kSymbolsPerTf) * 2048))

@@ -186,6 +186,11 @@ class Engine {
   // kernels K2 (the HBM-roofline stage of SURVEY.md 8(d), always measurable on its own: fft_roofline) and K2b.  The output
   // bits are identical either way.
   void set_fused(bool on) { fused_ = on; }
+  // Lock-in skip (default on): the 72 MSC symbols of the TFs that cannot be locked whatever their FIBs say (control_plane.hpp: lockin_deferred --
+  // the first 9 - okcount TFs of a stream that is not locked when the decode starts) are not demodulated: no ETI frame ever reads them.
+  // read_demapped_tf completes them on demand.  on = true (DABHIP_DEMOD_ALL=1): every TF is demodulated in full, as before.
+  void set_demod_all(bool on) { demod_all_ = on; }
+  int msc_deferred() const { return msc_deferred_; }     // TFs of the last decode / segment whose MSC part was deferred (completed on demand or not)
   // K1's chain: 0 = call after call, 1 = with the look-ahead pass, -1 = the pass for small batches (include/dabhip.h: dabhip_engine_set_sync_speculation)
   void set_sync_speculation(int mode) { spec_mode_ = mode < 0 ? -1 : (mode > 0 ? 1 : 0); }
   // sub-channel filter (TODO.md:28-31): bit i = SubChId i is decoded and carried in the ETI frames; takes effect with the next
@@ -325,9 +330,16 @@ class Engine {
   bool guard_download();
   bool guard_reserve_counters(int ntf);
   bool guard_check();
+  // the OFDM stage's launches over frames [first, first + n) of the frame list: fused_parts = the one-kernel stage's data symbols [sym_a, sym_b);
+  // ofdm_msc_part = the 72 MSC symbols through the configured stage (fused / two-kernel, hard / soft, guard as set) in chunks of `chunk` frames,
+  // with three timing events per chunk from chunk_ev_[3 * ev_base] on when ev_base >= 0
+  bool fused_parts(int first, int n, int sym_a, int sym_b, int nparts);
+  bool ofdm_msc_part(int first, int n, int chunk, int ev_base);
+  bool complete_deferred();            // read_demapped_tf: the MSC part of the last decode's deferred frames, awaited
 
   bool ok_ = false;
   bool afc_ = false, fused_ = true;
+  bool demod_all_ = std::getenv("DABHIP_DEMOD_ALL") != nullptr && std::atoi(std::getenv("DABHIP_DEMOD_ALL")) != 0;
   int guard_level_ = kDefaultGuardLevel;
   uint64_t subch_keep_ = ~0ull;
   int soft_bits_ = 0;
@@ -442,6 +454,13 @@ class Engine {
   PinnedBuffer<int2> h_info_;
   PinnedBuffer<uint8_t> h_fibs_, h_fib_ok_;
   int max_calls_ = 0, nstreams_ = 0, last_ntf_ = 0;
+  // lock-in skip: the last decode's frame list holds the frames whose MSC part ran at [0, last_msc_n_) and the deferred ones behind them, up to last_ntf_
+  // (pending: their samples, descriptors and the list are still those of that decode, so read_demapped_tf can complete them); msc_missing_[b][slot] = the
+  // MSC rows of that TF slot of stream b (layout of the last decode, carried slots first: last_keep_[b] of them) were never written
+  int last_msc_n_ = 0, last_chunk_ = 1, msc_deferred_ = 0;
+  bool msc_pending_ = false;
+  std::vector<std::vector<uint8_t>> msc_missing_;
+  std::vector<int> last_keep_;
   float scan_setup_ms_ = 0;
   std::vector<int64_t> eti_base_, eti_count_;
   std::vector<uint32_t> stream_status_;

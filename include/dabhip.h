@@ -231,6 +231,16 @@ int dabhip_engine_set_subchannels(dabhip_engine *e, const int32_t *ids, int n);
  * dabhip_engine_fft_stats describes whichever kernel ran; dabhip_engine_fft_roofline measures K2 by itself. */
 int dabhip_engine_set_fused(dabhip_engine *e, int enable);
 
+/* Lock-in skip.  The reference's back end takes MSC data only from transmission frames it is locked on (dab_process_frame, dab.c:46-98: lock needs
+ * ten consecutive TFs with 12 of 12 good FIBs, the 16-CIF ring starts with the TF that reaches lock, a loss drops it).  So of a stream that is not
+ * locked when a decode (or a session's segment) starts, the first 9 - okcount TFs cannot be locked whatever their FIBs say
+ * (dabhip_host_lockin_deferred), and the OFDM stage demodulates only their FIC symbols: no ETI frame reads their MSC symbols.  A stream that is
+ * locked at the start of a segment is demodulated in full.  ETI bytes are identical either way.
+ * on != 0 (or the environment variable DABHIP_DEMOD_ALL=1): every TF is demodulated in full.  Default: off.
+ * dabhip_engine_msc_deferred: TFs of the last decode whose MSC symbols were deferred (dabhip_engine_demapped_tf completes them on demand). */
+int dabhip_engine_set_demod_all(dabhip_engine *e, int on);
+int dabhip_engine_msc_deferred(const dabhip_engine *e);
+
 /* Schedule of K1's per-stream chain (sdr_demod's FIFO + time synchronisation, input_sdr.c:36-84, where call n + 1 is positioned by what call n
  * found).  mode 0: the chain, call after call.  mode 1: with a look-ahead pass -- what a call computes from its frame (null-symbol energy,
  * fine time search) depends only on where in the stream its read began, and a locked receiver's reads begin within a few samples of a predictable
@@ -321,6 +331,8 @@ int dabhip_stream_set_subchannels(dabhip_stream *s, const int32_t *ids, int n); 
 int dabhip_stream_set_soft(dabhip_stream *s, int enable);   /* before the first segment only */
 int dabhip_stream_set_parity_guard(dabhip_stream *s, int level);   /* see dabhip_engine_set_parity_guard */
 int dabhip_stream_set_sync_speculation(dabhip_stream *s, int mode);   /* default -1, see dabhip_engine_set_sync_speculation */
+int dabhip_stream_set_demod_all(dabhip_stream *s, int on);            /* see dabhip_engine_set_demod_all */
+int dabhip_stream_msc_deferred(const dabhip_stream *s);               /* TFs of the segment fed last whose MSC symbols were deferred */
 /* ---- sessions over several devices of one node -----------------------------------------------------------------------
  * dab2eti.c:60-130,237 is a session on ONE device: calls arrive for ever from one demod thread.  B independent unbounded streams shard like a batch
  * does: the streams are dealt ONCE, at creation, to the listed devices in contiguous slices (the rule of dabhip_multi_plan: slice i of n takes
@@ -380,7 +392,11 @@ int dabhip_device_copy(void *dst, const void *src, size_t nbytes, int to_device)
 /* What the OFDM stage of the LAST dabhip_engine_decode left for transmission frame `tf` (0-based among the frames `stream`
  * demodulated in that decode) -- the content of tf->fic_symbols_demapped[3][3072] and tf->msc_symbols_demapped[72][3072]
  * (dab.h:27-33, filled at input_sdr.c:146-162) as the batch path holds it: 9216 + 221184 values, 0 / 1 for hard decisions, the
- * signed 4-bit values (-7 .. 7) with soft decisions on.  Host arrays.  0, <0 on error. */
+ * signed 4-bit values (-7 .. 7) with soft decisions on.  Host arrays.  0, <0 on error.
+ * A TF whose MSC symbols the decode deferred (lock-in skip, dabhip_engine_set_demod_all) is completed on demand: the first such request runs the MSC
+ * symbols of ALL deferred TFs of that decode through the configured OFDM stage, from that decode's samples -- host input lives on in the engine's
+ * own upload buffer; with dabhip_engine_decode_device the caller's buffers must still be in place and unchanged.  (The engine behind a session
+ * cannot complete a deferred TF it carried over from an earlier segment, whose samples may be gone: that request is an error.) */
 int dabhip_engine_demapped_tf(dabhip_engine *e, int stream, int tf, int8_t *fic, int8_t *msc);
 
 /* Per sdr_demod call trace of one stream, for parity with the reference's state after each
@@ -438,6 +454,9 @@ int dabhip_stage_fic_decode(dabhip_engine *e, const uint8_t *fic, int nframes, u
  * hdr3 = {EId, CIFCount_hi, CIFCount_lo}; sub = 64 rows of
  * {id, slForm, uep_index, start_cu, size, bitrate, protlev, ASCTy}. */
 int dabhip_host_parse_fibs(const uint8_t *fibs, const uint8_t *crc_ok, int32_t *hdr3, int32_t *sub);
+/* The lock-in rule (dab.c:46-52): how many of the next ntf TFs of a stream cannot be locked, given the back end's state in front of them
+ * (locked; okcount = consecutive TFs with 12 of 12 good FIBs so far): locked ? 0 : min(ntf, max(0, 9 - okcount)). */
+int dabhip_host_lockin_deferred(int locked, int okcount, int ntf);
 /* ETI(NI) header (init_eti, misc.c:153-213) from the same table layout; returns its length. */
 int dabhip_host_eti_header(const int32_t *hdr3, const int32_t *sub, uint8_t *out, int cap);
 /* Lock FSM + 16-CIF ring + header sequence (dab_process_frame, dab.c:35-98) over ntf TFs
