@@ -26,7 +26,7 @@ constexpr int64_t kMaxDecisionRows = int64_t(48) << 20;   // x 512 B = 24 GiB of
 constexpr int kFicWords = kFicBits / 32;                  // 288
 constexpr int kMscWords = kMscBits / 32;                  // 6912
 constexpr int kCifWords = kCifBits / 32;                  // 1728 words per (logical) CIF row
-constexpr int kRowLead = 15;                              // logical rows before a stream's CIF 0 (interleaver depth - 1)
+static_assert(sizeof(IntPair) == sizeof(int2) && alignof(IntPair) <= alignof(int2), "layout_segment reads h_info_ and writes h_frames_ as {int, int} records");
 
 StreamState initial_state()
 {
@@ -39,6 +39,36 @@ StreamState initial_state()
 void unpack_bits(const uint32_t* words, int nbits, uint8_t* bytes)
 {
   for (int i = 0; i < nbits; ++i) bytes[i] = static_cast<uint8_t>((words[i >> 5] >> (i & 31)) & 1u);
+}
+// stage entries: n transmission frames that lie back to back in one stream, from its frame `first` on, as calls 0 .. n - 1 of a frame list
+// (TF slot j, CIF rows from row0 + 4 j)
+void contiguous_frames(int first, int n, int row0, std::vector<CallDesc>& descs, std::vector<int2>& list, std::vector<int>& slots, std::vector<int>& rows)
+{
+  descs.resize(n);
+  list.resize(n);
+  slots.resize(n);
+  rows.resize(n);
+  for (int j = 0; j < n; ++j) {
+    std::memset(&descs[j], 0, sizeof(CallDesc));
+    descs[j].status = 2;
+    descs[j].ordinal = j;
+    descs[j].view = initial_state().view;
+    descs[j].view.seg_src[0] = static_cast<int64_t>(first + j) * kTfBytes;
+    list[j] = make_int2(0, j);
+    slots[j] = j;
+    rows[j] = row0 + 4 * j;
+  }
+}
+// decision_audit_kernel's result (k_parity.hip) -> out8 of the stage entries; listed: entries the demappers listed
+struct AuditOut { unsigned long long decisions, disagree, outside, flagged; unsigned bin_bits, dec_bits, prod_bits, pad; };
+bool read_audit(const uint8_t* d_out, uint64_t listed, double* out8)
+{
+  AuditOut h;
+  if (blocking_copy(&h, d_out, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) return false;
+  auto f = [](unsigned bits) { float v; std::memcpy(&v, &bits, 4); return static_cast<double>(v); };
+  out8[0] = static_cast<double>(h.decisions); out8[1] = static_cast<double>(h.disagree); out8[2] = static_cast<double>(h.outside);
+  out8[3] = static_cast<double>(h.flagged); out8[4] = f(h.bin_bits); out8[5] = f(h.dec_bits); out8[6] = f(h.prod_bits); out8[7] = static_cast<double>(listed);
+  return true;
 }
 void pack_bits(const uint8_t* bytes, int nbits, uint32_t* words)
 {
@@ -81,21 +111,13 @@ Engine::Engine(int device, int host_threads, std::vector<int> cpus) : device_(de
   if (!check(hipStreamCreate(&stream_), "hipStreamCreate") ||
       !check(side_prio ? hipStreamCreateWithPriority(&copy_stream_, hipStreamDefault, prio_high) : hipStreamCreate(&copy_stream_), "hipStreamCreate"))
     return;
-  for (auto& e : ev_)
-    if (!check(hipEventCreate(&e), "hipEventCreate")) return;
-  if (!check(hipEventCreate(&ev_upload_), "hipEventCreate") || !check(hipEventCreate(&ev_fic_), "hipEventCreate") || !check(hipEventCreate(&ev_fic_done_), "hipEventCreate") ||
-      !check(hipEventCreate(&ev_chain_), "hipEventCreate") || !check(hipEventCreate(&ev_info_), "hipEventCreate") ||
-      !check(hipEventCreate(&ev_fibs_), "hipEventCreate") || !check(hipEventCreate(&ev_part0_), "hipEventCreate"))
-    return;
-  for (auto& e : ev_msc_)
-    if (!check(hipEventCreate(&e), "hipEventCreate")) return;
-  for (auto& e : ev_h2d_)
-    if (!check(hipEventCreate(&e), "hipEventCreate")) return;
-  for (auto& e : stage_ev_)
-    if (!check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate")) return;
-  if (!check(hipStreamCreateWithFlags(&d2h_stream_, hipStreamNonBlocking), "hipStreamCreate") ||
-      !check(hipEventCreateWithFlags(&ev_eti_fetch_[0], hipEventDisableTiming), "hipEventCreate") ||
-      !check(hipEventCreateWithFlags(&ev_eti_fetch_[1], hipEventDisableTiming), "hipEventCreate"))
+  for (Event* e : {&ev_[0], &ev_[1], &ev_[2], &ev_[3], &ev_upload_, &ev_fic_, &ev_fic_done_, &ev_chain_, &ev_info_, &ev_fibs_, &ev_part0_, &ev_msc_[0], &ev_msc_[1],
+                   &ev_msc_[2], &ev_msc_[3], &ev_h2d_[0], &ev_h2d_[1]})
+    if (!check(e->create(), "hipEventCreate")) return;
+  for (Event& e : stage_ev_)
+    if (!check(e.create(false), "hipEventCreate")) return;
+  if (!check(hipStreamCreateWithFlags(&d2h_stream_, hipStreamNonBlocking), "hipStreamCreate") || !check(ev_eti_fetch_[0].create(false), "hipEventCreate") ||
+      !check(ev_eti_fetch_[1].create(false), "hipEventCreate"))
     return;
 
   std::vector<double2> tw2048(2048), tw1536(1536);
@@ -111,8 +133,7 @@ Engine::Engine(int device, int host_threads, std::vector<int> cpus) : device_(de
   }
   for (int k = 0; k < 1536; ++k) tw1536[k] = make_double2(std::cos(2 * M_PI * k / 1536), std::sin(2 * M_PI * k / 1536));
   std::vector<uint8_t> prs(prs_quarter_turns().begin(), prs_quarter_turns().end());
-  std::vector<uint16_t> qpsk(carrier_to_qpsk().begin(), carrier_to_qpsk().end()), qpsk_inv(kCarriers);
-  for (int c = 0; c < kCarriers; ++c) qpsk_inv[qpsk[c]] = static_cast<uint16_t>(c);
+  std::vector<uint16_t> qpsk(carrier_to_qpsk().begin(), carrier_to_qpsk().end());
   std::vector<uint16_t> crc(256);
   for (int v = 0; v < 256; ++v) {
     const uint8_t b = static_cast<uint8_t>(v);
@@ -142,7 +163,7 @@ Engine::Engine(int device, int host_threads, std::vector<int> cpus) : device_(de
     }
   }
   if (!d_tw2048_.upload(tw2048, stream_) || !d_tw1536_.upload(tw1536, stream_) || !d_twf_.upload(twf, stream_) ||
-      !d_prs_.upload(prs, stream_) || !d_qpsk_.upload(qpsk, stream_) || !d_qpsk_inv_.upload(qpsk_inv, stream_) || !d_crc_tab_.upload(crc, stream_) || !d_crc_shift_.upload(crc_shift, stream_) ||
+      !d_prs_.upload(prs, stream_) || !d_qpsk_.upload(qpsk, stream_) || !d_crc_tab_.upload(crc, stream_) || !d_crc_shift_.upload(crc_shift, stream_) ||
       !d_prbs_.upload(prbs, stream_) || !d_zero_words_.upload(zeros, stream_))
     return;
   if (!check(hipStreamSynchronize(stream_), "table upload")) return;
@@ -165,12 +186,7 @@ Engine::Engine(int device, int host_threads, std::vector<int> cpus) : device_(de
       if (populated > 1 && numa_node_ < static_cast<int>(nodes.size())) host_cpus_ = nodes[static_cast<size_t>(numa_node_)];
     }
   }
-  if (const char* env = std::getenv("DABHIP_VIT_WAVE_MAX")) wave_max_codewords_ = wave_max_fic_blocks_ = std::max(0, std::atoi(env));
-  if (const char* env = std::getenv("DABHIP_VIT_TWO_LANES")) two_lanes_max_groups_ = std::max(0, std::atoi(env));
-  if (const char* env = std::getenv("DABHIP_VIT_FOUR_LANES")) four_lanes_max_groups_ = std::max(0, std::atoi(env));
-  if (const char* env = std::getenv("DABHIP_FIC_FOUR_LANES")) fic_four_lanes_max_tiles_ = std::max(0, std::atoi(env));
-  if (const char* env = std::getenv("DABHIP_VIT_LANES_PLAIN")) two_lanes_plain_ = std::atoi(env) != 0;
-  if (const char* env = std::getenv("DABHIP_FIC_WAVE_MAX")) wave_max_fic_blocks_ = std::max(0, std::atoi(env));
+  knobs_.from_env();
   pool_.reset(new ThreadPool(std::max(0, nthreads - 1), host_cpus_));
   host_lane_.reset(new AsyncLane(host_cpus_));
   ok_ = true;
@@ -178,9 +194,7 @@ Engine::Engine(int device, int host_threads, std::vector<int> cpus) : device_(de
 
 bool Engine::set_decoder_forms(int msc_form, int fic_form)
 {
-  const bool msc_ok = msc_form >= DABHIP_FORM_AUTO && msc_form <= DABHIP_FORM_FOUR;
-  const bool fic_ok = fic_form == DABHIP_FORM_AUTO || fic_form == DABHIP_FORM_WAVE || fic_form == DABHIP_FORM_LANE || fic_form == DABHIP_FORM_FOUR;
-  if (!msc_ok || !fic_ok) {
+  if (!msc_form_valid(msc_form) || !fic_form_valid(fic_form)) {
     set_error("set_decoder_forms: no such form (MSC " + std::to_string(msc_form) + ", FIC " + std::to_string(fic_form) +
               "; the FIC decoder has AUTO, WAVE, LANE and FOUR)");
     return false;
@@ -192,25 +206,7 @@ bool Engine::set_decoder_forms(int msc_form, int fic_form)
 
 Engine::~Engine()
 {
-  for (auto& e : ev_)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : chunk_ev_) (void)hipEventDestroy(e);
-  if (ev_upload_) (void)hipEventDestroy(ev_upload_);
-  if (ev_fic_) (void)hipEventDestroy(ev_fic_);
-  if (ev_fic_done_) (void)hipEventDestroy(ev_fic_done_);
-  if (ev_chain_) (void)hipEventDestroy(ev_chain_);
-  if (ev_info_) (void)hipEventDestroy(ev_info_);
-  if (ev_fibs_) (void)hipEventDestroy(ev_fibs_);
-  if (ev_part0_) (void)hipEventDestroy(ev_part0_);
-  for (auto& e : ev_msc_)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : ev_h2d_)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : stage_ev_)
-    if (e) (void)hipEventDestroy(e);
   if (d2h_stream_) { (void)hipStreamSynchronize(d2h_stream_); (void)hipStreamDestroy(d2h_stream_); }
-  for (hipEvent_t ev : ev_eti_fetch_)
-    if (ev) (void)hipEventDestroy(ev);
   if (copy_stream_) (void)hipStreamDestroy(copy_stream_);
   if (stream_) (void)hipStreamDestroy(stream_);
 }
@@ -234,7 +230,7 @@ bool Engine::upload_small(const SmallUpload* items, int n, hipStream_t s, SmallS
   // the stage's previous launch reads these words when it runs: still in flight -> wait for it (see engine.hpp; not reached by today's callers)
   if (stage.armed && hipEventQuery(stage.done) == hipErrorNotReady && !check(hipEventSynchronize(stage.done), "work list staging")) return false;
   (void)hipGetLastError();
-  if (!stage.done && !check(hipEventCreateWithFlags(&stage.done, hipEventDisableTiming), "hipEventCreate")) return false;
+  if (!stage.done && !check(stage.done.create(false), "hipEventCreate")) return false;
   size_t at = 0;
   HostWordsArgs hw{};
   int k = 0;
@@ -246,9 +242,7 @@ bool Engine::upload_small(const SmallUpload* items, int n, hipStream_t s, SmallS
       src = staging.data() + at;
       at += items[i].bytes / 4;
     }
-    hw.src[k] = src;
-    hw.dst[k] = static_cast<uint32_t*>(items[i].dst);
-    hw.nwords[k] = static_cast<uint32_t>(items[i].bytes / 4);
+    hw.set(k, src, items[i].dst, items[i].bytes / 4);
     if (++k == 4) {
       if (!check(launch_host_words(hw, s), "work list upload")) return false;
       hw = HostWordsArgs{};
@@ -260,25 +254,12 @@ bool Engine::upload_small(const SmallUpload* items, int n, hipStream_t s, SmallS
   return stage.armed;
 }
 
-// work lists of a batch to the device (any stream: only the launches below consume them)
-bool Engine::upload_decode_batch(const DecodeBatch& b, const HostList<DecodeJob>& jobs, hipStream_t s)
-{
-  if (b.groups.empty()) return true;
-  const int row_words = kCifWords * (soft_bits_ ? 4 : 1);
-  const size_t ntiles = b.job_ids.size() / 64;
-  return d_plans_.upload(plan_table_.plans(), s) && d_groups_.upload(b.groups, s) && d_job_ids_.upload(b.job_ids, s) && d_jobs_.upload(jobs, s) &&
-         d_decisions_.reserve(static_cast<size_t>(b.max_dec_rows) * 64) && d_grouped_.reserve(ntiles * row_words * 64);
-}
-
 // regroup + Viterbi over an uploaded batch: queued only; ev_msc_[0..2] bracket the two stages
 bool Engine::launch_decode_batch(const DecodeBatch& b, const uint32_t* bits, const int* d_stream_cif_base, const uint32_t* prbs, uint8_t* out,
                                  int record_stride)
 {
   if (b.groups.empty()) {                                 // nothing to decode: the three stamps still exist for msc_collect
-    if (!record(ev_msc_[0], stream_)) return false;
-    if (!record(ev_msc_[1], stream_)) return false;
-    if (!record(ev_msc_[2], stream_)) return false;
-    return true;
+    return record(ev_msc_[0], stream_) && record(ev_msc_[1], stream_) && record(ev_msc_[2], stream_);
   }
   const int* ids = d_job_ids_.get();
   const int row_words = kCifWords * (soft_bits_ ? 4 : 1);
@@ -286,44 +267,14 @@ bool Engine::launch_decode_batch(const DecodeBatch& b, const uint32_t* bits, con
   if (!record(ev_msc_[0], stream_)) return false;
   if (!check(launch_regroup(soft_bits_, ids, ntiles, d_jobs_.get(), d_stream_cif_base, bits, d_grouped_.get(), stream_), "regroup launch")) return false;
   if (!record(ev_msc_[1], stream_)) return false;
-  if (b.wave_form) {
-    msc_ran_ |= 1u << DABHIP_FORM_WAVE;
-    // small batch: one wave per code word (k_vitwave.hip), all lengths in one launch (longest first); its decisions use the survivor-record buffer
-    if (!check(launch_viterbi_wave(soft_bits_, d_groups_.get(), static_cast<int>(b.groups.size()), ids, d_plans_.get(), d_grouped_.get(), row_words,
-                                   d_decisions_.get(), prbs, out, record_stride, stream_),
-               "viterbi (wave per code word) launch"))
-      return false;
-    if (!record(ev_msc_[2], stream_)) return false;
-    return true;
-  }
-  // mid-size batches (hard decisions): two lanes per code word (engine.hpp: two_lanes_max_groups_; 1 = always)
-  // (a form set by set_decoder_forms replaces the rule; multi-lane forms are hard-only: a soft engine runs the lane form)
-  const bool forced = msc_form_ != DABHIP_FORM_AUTO;
-  const bool two_lanes = !soft_bits_ && (forced ? msc_form_ == DABHIP_FORM_TWO || msc_form_ == DABHIP_FORM_TWO_PLAIN
-                                                : two_lanes_max_groups_ > 0 && (two_lanes_max_groups_ == 1 || static_cast<int>(b.groups.size()) <= two_lanes_max_groups_));
-  const bool four_lanes = !soft_bits_ && (forced ? msc_form_ == DABHIP_FORM_FOUR
-                                                 : four_lanes_max_groups_ > 0 && (four_lanes_max_groups_ == 1 || static_cast<int>(b.groups.size()) <= four_lanes_max_groups_));
-  const bool plain = forced ? msc_form_ == DABHIP_FORM_TWO_PLAIN : two_lanes_plain_;
-  msc_ran_ |= 1u << (four_lanes ? DABHIP_FORM_FOUR : two_lanes ? (plain ? DABHIP_FORM_TWO_PLAIN : DABHIP_FORM_TWO) : DABHIP_FORM_LANE);
+  // the form the knobs' rule or set_decoder_forms picks (decoder_form.hpp), slice by slice (a small batch -- one wave per code word, all lengths longest
+  // first, its decisions in the survivor-record buffer -- is one slice: worklist.hpp)
+  const int form = msc_form(knobs_, msc_form_, soft_bits_ != 0, b.wave_form, static_cast<int>(b.groups.size()));
+  msc_ran_ |= 1u << form;
   for (size_t sl = 0; sl + 1 < b.slice_start.size(); ++sl) {
-    const int g0 = b.slice_start[sl], n = b.slice_start[sl + 1] - g0;
-    if (four_lanes || (two_lanes && plain)) {
-      if (!check(launch_viterbi_fused_lanes(four_lanes ? 4 : 2, d_groups_.get() + g0, n, ids, d_plans_.get(), d_grouped_.get(), row_words, d_decisions_.get(), prbs, out,
-                                            record_stride, stream_),
-                 "viterbi (lanes per code word) launch"))
-        return false;
-      continue;
-    }
-    if (two_lanes) {
-      if (!check(launch_viterbi_fused_two(d_groups_.get() + g0, n, ids, d_plans_.get(), d_grouped_.get(), row_words, d_decisions_.get(), prbs, out, record_stride, stream_),
-                 "viterbi (two lanes per code word) launch"))
-        return false;
-      continue;
-    }
-    if (!check(launch_viterbi_fused(soft_bits_, d_groups_.get() + g0, n, ids, d_plans_.get(), d_grouped_.get(), row_words, d_decisions_.get(), prbs,
-                                    out, record_stride, stream_),
-               "viterbi launch"))
-      return false;
+    const int g0 = b.slice_start[sl];
+    const ViterbiLaunch v{d_groups_.get() + g0, b.slice_start[sl + 1] - g0, ids, d_plans_.get(), d_grouped_.get(), row_words, d_decisions_.get(), prbs, out, record_stride};
+    if (!check(launch_viterbi_form(form, soft_bits_, v, stream_), "viterbi launch")) return false;
   }
   if (!record(ev_msc_[2], stream_)) return false;
   return true;
@@ -353,7 +304,6 @@ bool Engine::reserve_tf_slots(int nslots, int msc_rows)
 // values (-7 .. 7 as int8; > 0: bit 0) and the rows hold a nibble per value: word u / 8 of a plane, nibble u % 8.
 bool Engine::store_tf_bytes(int slot, const uint8_t* fic_bytes, const uint8_t* msc_bytes)
 {
-  static const int tmap[16] = {0, 8, 4, 12, 2, 10, 6, 14, 1, 9, 5, 13, 3, 11, 7, 15};
   const int bits = soft_bits_ ? 4 : 1, per = 32 / bits;
   const uint32_t vmask = soft_bits_ ? 15u : 1u;
   const size_t fic_words = static_cast<size_t>(kFicWords) * bits, row_words = static_cast<size_t>(kCifWords) * bits, plane_words = 108u * bits;
@@ -365,7 +315,7 @@ bool Engine::store_tf_bytes(int slot, const uint8_t* fic_bytes, const uint8_t* m
     for (int r = 0; r < 16; ++r) {
       std::fill(plane.begin(), plane.end(), 0u);
       for (int u = 0; u < kCifBits / 16; ++u) plane[u / per] |= (static_cast<uint32_t>(cif[16 * u + r]) & vmask) << (bits * (u % per));
-      const size_t row = static_cast<size_t>(kRowLead + 4 * slot + q - tmap[r]);
+      const size_t row = static_cast<size_t>(kRowLead + 4 * slot + q - kPlaneRowsBack[r]);
       // plane r occupies words [108 r, 108 r + 108) (x 4 with soft values) of the logical row (layout of demap_kernel<true>)
       if (!check(blocking_copy(d_msc_bits_.get() + row * row_words + r * plane_words, plane.data(), plane_words * 4, hipMemcpyHostToDevice), "msc upload")) return false;
     }
@@ -396,15 +346,15 @@ bool Engine::recycle_tf_slots(int used_slots, int keep_slots)
 // completed first, together with all other deferred TFs of that decode.
 bool Engine::read_demapped_tf(int stream, int tf, int8_t* fic_out, int8_t* msc_out)
 {
-  static const int tmap[16] = {0, 8, 4, 12, 2, 10, 6, 14, 1, 9, 5, 13, 3, 11, 7, 15};
-  if (stream < 0 || stream >= nstreams_ || static_cast<int>(prev_tf_base_.size()) <= stream || tf < 0 || tf >= prev_used_[stream]) {
+  if (stream < 0 || stream >= nstreams_ || static_cast<int>(carry_.size()) <= stream || tf < 0 || tf >= carry_[stream].prev_used) {
     set_error("demapped_tf: no such stream / transmission frame in the last decode");
     return false;
   }
   if (!check(hipSetDevice(device_), "hipSetDevice")) return false;
   // lock-in skip: the MSC part of this TF was deferred -- complete the last decode's deferred frames first (once; all of them)
-  if (static_cast<size_t>(stream) < msc_missing_.size() && static_cast<size_t>(tf) < msc_missing_[stream].size() && msc_missing_[stream][tf]) {
-    if (!msc_pending_ || tf < last_keep_[stream]) {
+  const StreamCarry& sc = carry_[stream];
+  if (static_cast<size_t>(tf) < sc.msc_missing.size() && sc.msc_missing[tf]) {
+    if (!last_.pending || tf < sc.last_keep) {
       set_error("demapped_tf: the MSC symbols of this transmission frame were not demodulated (it could not be locked) and its samples belong to an earlier segment");
       return false;
     }
@@ -413,7 +363,7 @@ bool Engine::read_demapped_tf(int stream, int tf, int8_t* fic_out, int8_t* msc_o
   const int bits = soft_bits_ ? 4 : 1, per = 32 / bits;
   const size_t fic_words = static_cast<size_t>(kFicWords) * bits, row_words = static_cast<size_t>(kCifWords) * bits, plane_words = 108u * bits;
   std::vector<uint32_t> f(fic_words), rows(static_cast<size_t>(kRowLead + 4) * row_words);
-  const size_t slot = static_cast<size_t>(prev_tf_base_[stream]) + tf, row0 = static_cast<size_t>(prev_row_base_[stream]) + 4 * tf - kRowLead;
+  const size_t slot = static_cast<size_t>(sc.prev_tf_base) + tf, row0 = static_cast<size_t>(sc.prev_row_base) + 4 * tf - kRowLead;
   if (!check(blocking_copy(f.data(), d_fic_bits_.get() + slot * fic_words, f.size() * 4, hipMemcpyDeviceToHost), "fic download") ||
       !check(blocking_copy(rows.data(), d_msc_bits_.get() + row0 * row_words, rows.size() * 4, hipMemcpyDeviceToHost), "msc download"))
     return false;
@@ -425,7 +375,7 @@ bool Engine::read_demapped_tf(int stream, int tf, int8_t* fic_out, int8_t* msc_o
   for (int q = 0; q < 4; ++q)
     for (int i = 0; i < kCifBits; ++i) {
       const int r = i & 15, u = i >> 4;
-      const size_t row = static_cast<size_t>(kRowLead + q - tmap[r]);                 // transmitted CIF q of this TF: plane r lives tmap[r] rows earlier
+      const size_t row = static_cast<size_t>(kRowLead + q - kPlaneRowsBack[r]);       // transmitted CIF q of this TF
       msc_out[static_cast<size_t>(q) * kCifBits + i] = value(rows[row * row_words + r * plane_words + u / per], u % per);
     }
   return true;
@@ -460,14 +410,9 @@ bool Engine::fic_decode_slots_async(int first, int n, uint8_t* fibs_host, uint8_
   std::vector<int> ids(static_cast<size_t>(ntiles) * 64, -1);
   for (int i = 0; i < nblocks; ++i) ids[i] = 4 * first + i;
   std::vector<WaveGroup> groups;
-  // (fic_form_ from set_decoder_forms replaces the rule; four lanes are hard-only: a soft engine runs the lane form)
-  const bool forced = fic_form_ != DABHIP_FORM_AUTO;
-  const bool wave_form = forced ? fic_form_ == DABHIP_FORM_WAVE : nblocks <= wave_max_fic_blocks_;   // few blocks: one wave per block (k_vitwave.hip), rows per block and chunk of steps
-  // more, but not enough to fill the device with one lane per block (774 dependent steps in front of the control plane): four lanes per block
-  // (vit_four_lanes.hpp; same records, same arguments), up to 128 tiles = 32 streams x 64 TF (measured: nothing to gain above).
-  const bool fic_four_lanes = !wave_form && !soft_bits_ &&
-                              (forced ? fic_form_ == DABHIP_FORM_FOUR : fic_four_lanes_max_tiles_ > 0 && (fic_four_lanes_max_tiles_ == 1 || ntiles <= fic_four_lanes_max_tiles_));
-  fic_ran_ |= 1u << (wave_form ? DABHIP_FORM_WAVE : fic_four_lanes ? DABHIP_FORM_FOUR : DABHIP_FORM_LANE);
+  const int form = fic_form(knobs_, fic_form_, soft_bits_ != 0, nblocks, ntiles);      // decoder_form.hpp; WAVE: rows per block and chunk of steps
+  const bool wave_form = form == DABHIP_FORM_WAVE;
+  fic_ran_ |= 1u << form;
   const int64_t dr = wave_form ? int64_t(64) * ((plan_table_[pid].nsteps + kWaveChunk - 1) / kWaveChunk) : (plan_table_[pid].nsteps + 7) / 8 * 8;
   for (int g = 0; g < ntiles; ++g) groups.push_back(WaveGroup{pid, 64 * g, std::min(64, nblocks - 64 * g), plan_table_[pid].nsteps, 0, g * dr});
   // The FIC kernels run on the side stream as well, behind what the main stream has queued so far (the FIC bits): 1008 waves of 774
@@ -487,14 +432,8 @@ bool Engine::fic_decode_slots_async(int first, int n, uint8_t* fibs_host, uint8_
     if (!upload_small(items, 3, ks, h_small_fic_)) return false;
   }
   if (!check(launch_fic_group(d_fic_bits_.get(), 4 * first, nblocks, block_words, d_grouped_.get(), ks), "fic group launch") ||
-      !check(wave_form
-                 ? launch_viterbi_wave(soft_bits_, d_groups_.get(), ntiles, d_job_ids_.get(), d_plans_.get(), d_grouped_.get(), block_words,
-                                       d_decisions_.get(), d_prbs_.get(), d_fibs_.get(), 96, ks)
-             : fic_four_lanes
-                 ? launch_viterbi_fused_lanes(4, d_groups_.get(), ntiles, d_job_ids_.get(), d_plans_.get(), d_grouped_.get(), block_words, d_decisions_.get(),
-                                              d_prbs_.get(), d_fibs_.get(), 96, ks)
-                 : launch_viterbi_fused(soft_bits_, d_groups_.get(), ntiles, d_job_ids_.get(), d_plans_.get(), d_grouped_.get(), block_words,
-                                        d_decisions_.get(), d_prbs_.get(), d_fibs_.get(), 96, ks),
+      !check(launch_viterbi_form(form, soft_bits_, ViterbiLaunch{d_groups_.get(), ntiles, d_job_ids_.get(), d_plans_.get(), d_grouped_.get(), block_words,
+                                                                 d_decisions_.get(), d_prbs_.get(), d_fibs_.get(), 96}, ks),
              "fic viterbi launch"))
     return false;
   if (!check(launch_fib_crc(d_fibs_.get() + static_cast<size_t>(first) * 384, n * 12, d_crc_tab_.get(), d_fib_ok_.get() + static_cast<size_t>(first) * 12, ks), "fib crc launch")) return false;
@@ -502,12 +441,8 @@ bool Engine::fic_decode_slots_async(int first, int n, uint8_t* fibs_host, uint8_
   // (few frames, page-locked destinations -- the engine's own: both downloads as one kernel that writes the host arrays itself, see scan_streams' fetch)
   if (n <= 512 && fibs_host == h_fibs_.data() && ok_host == h_fib_ok_.data()) {
     HostWordsArgs hw{};
-    hw.src[0] = reinterpret_cast<const uint32_t*>(d_fibs_.get() + static_cast<size_t>(first) * 384);
-    hw.dst[0] = reinterpret_cast<uint32_t*>(fibs_host);
-    hw.nwords[0] = static_cast<uint32_t>(n) * 96;
-    hw.src[1] = reinterpret_cast<const uint32_t*>(d_fib_ok_.get() + static_cast<size_t>(first) * 12);
-    hw.dst[1] = reinterpret_cast<uint32_t*>(ok_host);
-    hw.nwords[1] = static_cast<uint32_t>(n) * 3;
+    hw.set(0, d_fibs_.get() + static_cast<size_t>(first) * 384, fibs_host, static_cast<size_t>(n) * 96);
+    hw.set(1, d_fib_ok_.get() + static_cast<size_t>(first) * 12, ok_host, static_cast<size_t>(n) * 3);
     return check(launch_host_words(hw, copy), "fib download") && check(hipEventRecord(ev_fibs_, copy), "fib download event");
   }
   return check(hipMemcpyAsync(fibs_host, d_fibs_.get() + static_cast<size_t>(first) * 384, static_cast<size_t>(n) * 384, hipMemcpyDeviceToHost, copy), "fib download") &&
@@ -524,9 +459,8 @@ bool Engine::msc_prepare(const std::vector<const JobList*>& stream_jobs, const s
     if (trace_host) std::fprintf(stderr, "[host]   msc_prepare %-14s %8.3f ms\n", what, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_in).count());
   };
   std::string error;
-  // a forced form: every batch, or none, in the wave form (set_decoder_forms)
-  const int64_t wave_max = msc_form_ == DABHIP_FORM_AUTO ? wave_max_codewords_ : msc_form_ == DABHIP_FORM_WAVE ? INT64_MAX : 0;
-  if (prepare_msc_work(plan_table_, *pool_, stream_jobs, planes, stream_row_base, stream_fib_base, kMaxDecisionRows, out, &error, mark, wave_max)) return true;
+  if (prepare_msc_work(plan_table_, *pool_, stream_jobs, planes, stream_row_base, stream_fib_base, kMaxDecisionRows, out, &error, mark, msc_wave_max(knobs_, msc_form_)))
+    return true;
   set_error(error);
   return false;
 }
@@ -607,30 +541,32 @@ bool Engine::read_eti(int64_t first, int64_t n, uint8_t* dst)
 }
 
 // ---------------------------------------------------------------------------------------------
-// Session carry-over: the FIC blocks, FIBs and CRC flags of each stream's last carry_keep_ TF slots and its logical CIF rows
+// Session carry-over: the FIC blocks, FIBs and CRC flags of each stream's last StreamCarry::keep TF slots and its logical CIF rows
 // from 15 before the oldest kept CIF move from the previous segment's layout to the front of the stream's part of the new
 // one (through a dense temporary: the buffers may be re-allocated in between).
-bool Engine::carry_and_reserve(const std::vector<int>& tf_base, const std::vector<int>& row_base, int nslots, int nrows)
+bool Engine::carry_and_reserve(const SegmentLayout& seg)
 {
+  const int nslots = seg.tf_base.back(), nrows = seg.next_row + 1;
   const size_t bits = soft_bits_ ? 4 : 1;
   const size_t unit[4] = {kFicWords * 4 * bits, 384, 12, kCifWords * 4 * bits};
   HostList<CopyDesc>&out = carry_out_descs_, &in = carry_in_descs_;   // (the previous segment's lists were consumed before its feed returned)
   out.clear();
   in.clear();
   size_t tmp_bytes = 0;
-  const int n = static_cast<int>(carry_keep_.size());
+  const int n = static_cast<int>(carry_.size());
   uint8_t* base[4] = {reinterpret_cast<uint8_t*>(d_fic_bits_.get()), d_fibs_.get(), d_fib_ok_.get(), reinterpret_cast<uint8_t*>(d_msc_bits_.get())};
   struct Piece { int which; size_t src, dst, bytes, tmp; };
   std::vector<Piece> pieces;
   for (int b = 0; b < n; ++b) {
-    const int keep = carry_keep_[b];
+    const StreamCarry& c = carry_[b];
+    const int keep = c.keep;
     if (keep == 0) continue;
-    const size_t src_slot = static_cast<size_t>(prev_tf_base_[b]) + prev_used_[b] - keep, dst_slot = tf_base[b];
+    const size_t src_slot = static_cast<size_t>(c.prev_tf_base) + c.prev_used - keep, dst_slot = seg.tf_base[b];
     for (int w = 0; w < 3; ++w) {
       pieces.push_back(Piece{w, src_slot * unit[w], dst_slot * unit[w], keep * unit[w], tmp_bytes});
       tmp_bytes += (keep * unit[w] + 15) & ~size_t(15);
     }
-    const size_t src_row = static_cast<size_t>(prev_row_base_[b]) - kRowLead + 4 * (prev_used_[b] - keep), dst_row = static_cast<size_t>(row_base[b]) - kRowLead;
+    const size_t src_row = static_cast<size_t>(c.prev_row_base) - kRowLead + 4 * (c.prev_used - keep), dst_row = static_cast<size_t>(seg.row_base[b]) - kRowLead;
     const size_t rows = 4 * static_cast<size_t>(keep) + kRowLead;
     pieces.push_back(Piece{3, src_row * unit[3], dst_row * unit[3], rows * unit[3], tmp_bytes});
     tmp_bytes += rows * unit[3];
@@ -640,7 +576,7 @@ bool Engine::carry_and_reserve(const std::vector<int>& tf_base, const std::vecto
     for (const Piece& p : pieces) out.push_back(CopyDesc{base[p.which] + p.src, d_carry_.get() + p.tmp, static_cast<uint32_t>(p.bytes)});
     // (the copy out must be over before a growing buffer is given back; when nothing grows -- every segment of a session but the first few --
     // stream order alone keeps the two copies apart, and the host does not wait)
-    const bool grows = nslots > tf_slots_ || (nrows < 0 ? 4 * nslots + kRowLead + 1 : nrows) > msc_rows_;
+    const bool grows = nslots > tf_slots_ || nrows > msc_rows_;
     if (!d_copy_descs_.upload(out, stream_) || !check(launch_batched_copy(d_copy_descs_.get(), static_cast<int>(out.size()), stream_), "carry out") ||
         (grows && !check(hipStreamSynchronize(stream_), "carry out")))
       return false;
@@ -698,12 +634,9 @@ bool Engine::guard_finish(bool planar, int first, int n, int sym_a, int sym_b, b
 {
   uint32_t* const counter = d_guard_counter_.get() + static_cast<size_t>(guard_launches_) * kGuardSlotWords;    // guard_begin's
   ++guard_launches_;
-  return check(launch_exact_decide(d_guard_list_.get(), counter, guard_cap_, d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(),
-                                   d_tw2048_.get(), d_qpsk_.get(), d_qpsk_inv_.get(), d_frame_slot_.get(), d_frame_cif_row_.get(), planar, d_fic_bits_.get(), d_msc_bits_.get(), stream_),
-               "exact decide launch") &&
-         check(launch_exact_decide_all(counter, guard_cap_, d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), first, n, sym_a, sym_b,
-                                       d_tw2048_.get(), d_qpsk_.get(), d_frame_slot_.get(), d_frame_cif_row_.get(), planar, skip_fic, d_fic_bits_.get(), d_msc_bits_.get(), stream_),
-               "exact decide (overflow) launch");
+  const FrameListArgs fl = frame_list();
+  return check(launch_exact_decide(d_guard_list_.get(), counter, guard_cap_, fl, d_tw2048_.get(), planar, stream_), "exact decide launch") &&
+         check(launch_exact_decide_all(counter, guard_cap_, fl, first, n, sym_a, sym_b, d_tw2048_.get(), planar, skip_fic, stream_), "exact decide (overflow) launch");
 }
 // behind the last guarded launch of a decode, before the stream is awaited
 bool Engine::guard_download()
@@ -761,12 +694,8 @@ bool Engine::begin_decode(int nstreams, bool cont)
   if (!cont) {
     planes_.resize(nstreams);                  // re-initialised by the control-plane pass itself (planes_fresh_): 0.2 ms that would otherwise delay K1
     planes_fresh_ = true;
-    carry_keep_.assign(nstreams, 0);
-    prev_used_.assign(nstreams, 0);
-    calls_done_.assign(nstreams, 0);
-    ord_done_.assign(nstreams, 0);
-    prev_tf_base_.assign(nstreams + 1, 0);
-    prev_row_base_.assign(nstreams, 0);
+    carry_.resize(nstreams);
+    for (StreamCarry& c : carry_) c.reset();
   }
   return true;
 }
@@ -851,7 +780,7 @@ bool Engine::scan_streams(const uint8_t* const* iq, const size_t* nbytes, int ns
   size_t total = 0;
   for (int b = 0; b < nstreams; ++b) {
     nb[b] = static_cast<int64_t>(nbytes[b]);
-    max_calls_ = std::max<int>(max_calls_, static_cast<int>(nbytes[b] / kChunkBytes) - calls_done_[b]);
+    max_calls_ = std::max<int>(max_calls_, static_cast<int>(nbytes[b] / kChunkBytes) - carry_[b].calls_done);
     total += (nbytes[b] + 15) & ~size_t(15);
   }
   if (on_device) {
@@ -892,7 +821,7 @@ bool Engine::scan_streams(const uint8_t* const* iq, const size_t* nbytes, int ns
     if (!h_viol_.resize(nstreams + 1) || !d_viol_.reserve(nstreams + 1) || !d_states_prev_.reserve(nstreams) || !d_calls_before_.reserve(nstreams) ||
         !h_calls_before_.resize(nstreams))
       return false;
-    std::copy(calls_done_.begin(), calls_done_.begin() + nstreams, h_calls_before_.data());
+    for (int b = 0; b < nstreams; ++b) h_calls_before_[b] = carry_[b].calls_done;
   }
   {
     // one launch instead of nine copies and fills (launch_scan_setup): the kernel reads the page-locked host arrays itself
@@ -999,11 +928,7 @@ bool Engine::scan_streams(const uint8_t* const* iq, const size_t* nbytes, int ns
     if (words <= (size_t(1) << 18)) {
       HostWordsArgs hw{};
       int k = 0;
-      auto add = [&](const void* src, void* dst, size_t n) {
-        hw.src[k] = static_cast<const uint32_t*>(src);
-        hw.dst[k] = static_cast<uint32_t*>(dst);
-        hw.nwords[k++] = static_cast<uint32_t>(n);
-      };
+      auto add = [&](const void* src, void* dst, size_t n) { hw.set(k++, src, dst, n); };
       if (split_scan) add(d_viol_.get(), h_viol_.data(), nstreams + 1);
       if (split_scan && use_spec) add(d_spec_ctl_.get() + nstreams, h_spec_hits_.data(), 1);
       add(d_info_.get(), h_info_.data(), ndesc * 2);
@@ -1053,23 +978,25 @@ bool Engine::scan_streams(const uint8_t* const* iq, const size_t* nbytes, int ns
   return true;
 }
 
+// the argument block of every launch over the frame list: THE one place that names these buffers (taken afresh before a launch: a reserve may move them)
+FrameListArgs Engine::frame_list() const
+{
+  return FrameListArgs{d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), d_twf_.get(), d_frame_slot_.get(), d_frame_cif_row_.get(), d_qpsk_.get(),
+                       d_fic_bits_.get(), d_msc_bits_.get()};
+}
+GuardArgs Engine::soft_guard_args() const { return GuardArgs{d_delta_.get(), kSymbolsPerTf, kSoftNormC, 0.0f, 0, 0u, nullptr, nullptr}; }
+
 // The one-kernel OFDM stage over frames [first, first + n) of the frame list, data symbols [sym_a, sym_b), nparts workgroups per frame
 bool Engine::fused_parts(int first, int n, int sym_a, int sym_b, int nparts)
 {
-  if (soft_bits_ != 0)
-    return check(launch_ofdm_demap_fused_soft(afc_, d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), first, n, d_twf_.get(), d_frame_slot_.get(),
-                                              d_frame_cif_row_.get(), d_qpsk_.get(), d_fic_bits_.get(), d_msc_bits_.get(), stream_, sym_a, sym_b, nparts),
-                 "fused fft/demap launch");
+  const FrameListArgs fl = frame_list();
+  if (soft_bits_ != 0) return check(launch_ofdm_demap_fused_soft(afc_, fl, first, n, stream_, sym_a, sym_b, nparts), "fused fft/demap launch");
   const bool guard = guard_active();
   GuardArgs ga{};
   if (guard && !guard_begin(n, &ga)) return false;
-  const bool launched =
-      guard ? check(launch_ofdm_demap_fused_guarded(d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), first, n, d_twf_.get(), d_frame_slot_.get(),
-                                                    d_frame_cif_row_.get(), d_qpsk_.get(), d_fic_bits_.get(), d_msc_bits_.get(), ga, stream_, sym_a, sym_b, nparts),
-                    "fused fft/demap launch")
-            : check(launch_ofdm_demap_fused_plain(afc_, d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), first, n, d_twf_.get(), d_frame_slot_.get(),
-                                                  d_frame_cif_row_.get(), d_qpsk_.get(), d_fic_bits_.get(), d_msc_bits_.get(), stream_, sym_a, sym_b, nparts),
-                    "fused fft/demap launch");
+  const bool launched = check(guard ? launch_ofdm_demap_fused_guarded(fl, first, n, ga, stream_, sym_a, sym_b, nparts)
+                                    : launch_ofdm_demap_fused_plain(afc_, fl, first, n, stream_, sym_a, sym_b, nparts),
+                              "fused fft/demap launch");
   return launched && (!guard || guard_finish(true, first, n, sym_a, sym_b, false));
 }
 
@@ -1078,14 +1005,10 @@ bool Engine::fused_parts(int first, int n, int sym_a, int sym_b, int nparts)
 bool Engine::ofdm_msc_part(int first, int n, int chunk, int ev_base)
 {
   const bool guard = guard_active(), soft = soft_bits_ != 0, energies = guard || soft;
-  GuardArgs soft_args{};                                  // soft decisions, two-kernel stage: K2b reads the energies, lists nothing
-  soft_args.delta = d_delta_.get();
-  soft_args.delta_stride = kSymbolsPerTf;
-  soft_args.c = kSoftNormC;
   bool gpu_ok = true;
   for (int c = 0; c * chunk < n && gpu_ok; ++c) {
     const int f0 = first + c * chunk, nf = std::min(chunk, n - c * chunk);
-    hipEvent_t* const ev = ev_base >= 0 ? &chunk_ev_[static_cast<size_t>(3) * (ev_base + c)] : nullptr;
+    Event* const ev = ev_base >= 0 ? &chunk_ev_[static_cast<size_t>(3) * (ev_base + c)] : nullptr;
     gpu_ok = !ev || record(ev[0], stream_);
     if (fused_) {
       // the 72 MSC symbols (the FIC symbols ran before the FIC decode was queued); workgroups per frame: measurement knob
@@ -1093,11 +1016,11 @@ bool Engine::ofdm_msc_part(int first, int n, int chunk, int ev_base)
       gpu_ok = gpu_ok && fused_parts(f0, nf, 4, 76, msc_wgs);
       gpu_ok = gpu_ok && (!ev || record(ev[1], stream_));
     } else {
-      GuardArgs ga = soft ? soft_args : GuardArgs{};   // (hard decisions: a non-null delta switches the guard's listing on)
+      GuardArgs ga = soft ? soft_guard_args() : GuardArgs{};   // (hard decisions: a non-null delta switches the guard's listing on)
       if (guard && !guard_begin(nf, &ga)) return false;
       // with the guard on (or soft decisions), K2 also leaves the per-symbol sample energies K2b decides with
-      gpu_ok = gpu_ok && check(launch_ofdm_fft(d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), f0, nf, d_spectra_.get(), d_twf_.get(), stream_,
-                                               energies ? d_delta_.get() : nullptr, soft ? kSoftNormC : guard_c_of(guard_rule_level())),
+      gpu_ok = gpu_ok && check(launch_ofdm_fft(frame_list(), f0, nf, d_spectra_.get(), stream_, energies ? d_delta_.get() : nullptr,
+                                               soft ? kSoftNormC : guard_c_of(guard_rule_level())),
                                "fft launch");
       gpu_ok = gpu_ok && (!ev || record(ev[1], stream_));
       gpu_ok = gpu_ok && check(launch_demap(true, soft_bits_, d_spectra_.get(), f0, nf, d_frame_slot_.get(), d_frame_cif_row_.get(), d_qpsk_.get(), d_fic_bits_.get(), d_msc_bits_.get(), ga, stream_), "demap launch");
@@ -1112,21 +1035,63 @@ bool Engine::ofdm_msc_part(int first, int n, int chunk, int ev_base)
 // descriptors and IQ pointers are still on the device (the engine's own upload buffer outlives the decode; device-resident input must still be where it was).
 bool Engine::complete_deferred()
 {
-  const int first = last_msc_n_, n = last_ntf_ - last_msc_n_;
-  if (!msc_pending_ || n <= 0) return true;
-  if (!fused_ && !d_spectra_.reserve(static_cast<size_t>(last_chunk_) * kSymbolsPerTf * 2048)) return false;
+  const int first = seg_.nmsc, n = seg_.ntf - seg_.nmsc;
+  if (!last_.pending || n <= 0) return true;
+  if (!fused_ && !d_spectra_.reserve(static_cast<size_t>(last_.chunk) * kSymbolsPerTf * 2048)) return false;
   const bool guard = guard_active();
   guard_counters_clear_ = false;
   guard_launches_ = 0;
-  bool gpu_ok = ofdm_msc_part(first, n, last_chunk_, -1);
+  bool gpu_ok = ofdm_msc_part(first, n, last_.chunk, -1);
   if (guard && gpu_ok) gpu_ok = guard_download();
   const bool drained = check(hipStreamSynchronize(stream_), "deferred MSC symbols");      // also on the error path: nothing may stay in flight
   if (!gpu_ok || !drained) return false;
   if (guard && !guard_check()) return false;
-  msc_pending_ = false;
-  for (size_t b = 0; b < msc_missing_.size(); ++b)
-    std::fill(msc_missing_[b].begin() + std::min<size_t>(static_cast<size_t>(last_keep_[b]), msc_missing_[b].size()), msc_missing_[b].end(), uint8_t(0));
+  last_.pending = false;
+  for (StreamCarry& c : carry_)
+    std::fill(c.msc_missing.begin() + std::min<size_t>(static_cast<size_t>(c.last_keep), c.msc_missing.size()), c.msc_missing.end(), uint8_t(0));
   return true;
+}
+
+// The frame list of this decode / segment (segment_layout.hpp) into seg_ and, in one launch, onto the device: called by the scan as soon as the calls'
+// {status, ordinal} are on the host (h_info_), i.e. while K1's verification kernel still runs, and again after a re-scan.
+bool Engine::layout_frames(const size_t* nbytes, int nstreams)
+{
+  const auto tfr = std::chrono::steady_clock::now();
+  SegmentLayout& seg = seg_;
+  const size_t nd = static_cast<size_t>(nstreams) * max_calls_;
+  if (!h_frames_.resize(nd) || !h_frame_slot_.resize(nd) || !h_frame_cif_row_.resize(nd)) return false;   // page-locked: uploaded asynchronously
+  // Lock-in skip: the leading TFs of a stream that cannot be locked (a fresh decode's planes are reset later, inside the control-plane pass: their
+  // content here is stale) go to the END of the list: the FIC launches run over the whole list, the MSC launches over [0, nmsc)
+  seg_ncalls_.resize(nstreams);
+  seg_defer_max_.resize(nstreams);
+  for (int b = 0; b < nstreams; ++b) {
+    seg_ncalls_[b] = static_cast<int>(nbytes[b] / kChunkBytes) - carry_[b].calls_done;
+    seg_defer_max_[b] = demod_all_ ? 0 : (planes_fresh_ ? lockin_deferred(false, 0, max_calls_) : lockin_deferred(planes_[b].locked(), planes_[b].okcount(), max_calls_));
+  }
+  std::string error;
+  if (!layout_segment(reinterpret_cast<const IntPair*>(h_info_.data()), max_calls_, seg_ncalls_.data(), carry_, seg_defer_max_.data(), seg,
+                      reinterpret_cast<IntPair*>(h_frames_.data()), h_frame_slot_.data(), h_frame_cif_row_.data(), &error)) {
+    set_error(error);
+    return false;
+  }
+  // the three lists go up in ONE launch that reads the page-locked arrays itself (three copy-engine copies cost 45 us of idle GPU before the first
+  // OFDM launch); with the guard on it also clears the guard's counters, which guard_begin() then leaves alone
+  bool up = true;
+  if (seg.ntf > 0) {
+    up = d_frames_.reserve(seg.ntf) && d_frame_slot_.reserve(seg.ntf) && d_frame_cif_row_.reserve(seg.ntf);
+    HostWordsArgs hw{};
+    hw.set(0, h_frames_.data(), d_frames_.get(), 2 * static_cast<size_t>(seg.ntf));
+    hw.set(1, h_frame_slot_.data(), d_frame_slot_.get(), static_cast<size_t>(seg.ntf));
+    hw.set(2, h_frame_cif_row_.data(), d_frame_cif_row_.get(), static_cast<size_t>(seg.ntf));
+    if (up && guard_active() && guard_launches_ == 0 && guard_reserve_counters(seg.ntf)) {
+      hw.zero = d_guard_counter_.get();
+      hw.nzero = static_cast<uint32_t>(h_guard_counts_.size());
+      guard_counters_clear_ = true;
+    }
+    up = up && check(launch_host_words(hw, stream_), "frame list upload");
+  }
+  layout_ms_ += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tfr).count();
+  return up;
 }
 
 int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int nstreams, bool on_device, bool cont, bool full_scan)
@@ -1145,87 +1110,16 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
   guard_flagged_ = guard_decisions_ = 0;
   guard_launches_ = 0;
   guard_overflows_ = 0;
-  msc_pending_ = false;                      // the scan overwrites the descriptors the deferred frames of the last decode would be completed from
-  msc_deferred_ = 0;
+  last_.pending = false;                     // the scan overwrites the descriptors the deferred frames of the last decode would be completed from
+  last_.deferred = 0;
+  layout_ms_ = 0;
   if (!begin_decode(nstreams, cont)) return -1;
+  const SegmentLayout& seg = seg_;          // filled by layout_frames, from inside the scan
   struct SideStreamGuard {                   // whatever was queued on the side stream is awaited before returning
     hipStream_t s;
     ~SideStreamGuard() { (void)hipStreamSynchronize(s); }
   } side_guard{copy_stream_};
   mark("begin_decode done");
-  // frame list: demodulated TFs, stream-major within each of its two parts (see the layout).  Slots and logical CIF rows of a stream: first the ones carried over from
-  // the previous segment of a session (the last <= 4 TFs), then this segment's.  Built (and uploaded) by the scan as soon as the
-  // calls' {status, ordinal} are known, i.e. while K1's verification kernel still runs.
-  std::vector<int> tf_base(nstreams + 1, 0), row_base(nstreams), fib_base(nstreams), nnew(nstreams, 0), ndefer_of(nstreams, 0);
-  int next_row = 0, ntf_new = 0, nmsc = 0;
-  float frames_ms = 0;
-  auto layout = [&]() -> bool {
-    const auto tfr = std::chrono::steady_clock::now();
-    const size_t nd = static_cast<size_t>(nstreams) * max_calls_;
-    if (!h_frames_.resize(nd) || !h_frame_slot_.resize(nd) || !h_frame_cif_row_.resize(nd)) return false;   // page-locked: uploaded asynchronously
-    next_row = 0;
-    ntf_new = 0;
-    tf_base[0] = 0;
-    // Lock-in skip: the leading TFs of a stream that cannot be locked (lockin_deferred; a fresh decode's planes are reset later, inside the control-plane
-    // pass: their content here is stale) go to the END of the list, [nmsc, ntf_new): the FIC launches run over the whole list, the MSC launches over
-    // [0, nmsc).  Slots and rows are what they would be without the skip; no reader of the list relies on its order (every kernel goes from the list
-    // entry to stream, call, slot and row; the guard's entries carry list indices of the launch that wrote them).
-    int ndefer = 0;
-    for (int b = 0; b < nstreams; ++b) {
-      const int ncalls = static_cast<int>(nbytes[b] / kChunkBytes) - calls_done_[b];
-      int n = 0;
-      for (int k = 0; k < ncalls; ++k) n += h_info_[static_cast<size_t>(b) * max_calls_ + k].x == 2 ? 1 : 0;
-      nnew[b] = n;
-      ndefer_of[b] = demod_all_ ? 0 : (planes_fresh_ ? lockin_deferred(false, 0, n) : lockin_deferred(planes_[b].locked(), planes_[b].okcount(), n));
-      ntf_new += n;
-      ndefer += ndefer_of[b];
-    }
-    nmsc = ntf_new - ndefer;
-    int at_msc = 0, at_defer = nmsc;
-    for (int b = 0; b < nstreams; ++b) {
-      const int keep = carry_keep_[b];
-      const int ncalls = static_cast<int>(nbytes[b] / kChunkBytes) - calls_done_[b];
-      row_base[b] = next_row + kRowLead;      // each stream gets 15 lead-in rows for the scatter of its first CIFs
-      for (int k = 0; k < ncalls; ++k) {
-        const int2 d = h_info_[static_cast<size_t>(b) * max_calls_ + k];     // {status, ordinal}
-        if (d.x == 2) {
-          const int local = keep + (d.y - ord_done_[b]);
-          const int at = local - keep < ndefer_of[b] ? at_defer++ : at_msc++;
-          h_frames_[at] = make_int2(b, k);
-          h_frame_slot_[at] = tf_base[b] + local;
-          h_frame_cif_row_[at] = row_base[b] + 4 * local;
-        }
-      }
-      tf_base[b + 1] = tf_base[b] + keep + nnew[b];
-      fib_base[b] = 4 * tf_base[b];
-      next_row += kRowLead + 4 * (keep + nnew[b]);
-    }
-    if (at_msc != nmsc || at_defer != ntf_new) { set_error("decode: the calls' ordinals do not number this segment's transmission frames"); return false; }
-    // the three lists go up in ONE launch that reads the page-locked arrays itself (three copy-engine copies cost 45 us of idle GPU before the first
-    // OFDM launch); with the guard on it also clears the guard's counters, which guard_begin() then leaves alone
-    bool up = true;
-    if (ntf_new > 0) {
-      up = d_frames_.reserve(ntf_new) && d_frame_slot_.reserve(ntf_new) && d_frame_cif_row_.reserve(ntf_new);
-      HostWordsArgs hw{};
-      hw.src[0] = reinterpret_cast<const uint32_t*>(h_frames_.data());
-      hw.dst[0] = reinterpret_cast<uint32_t*>(d_frames_.get());
-      hw.nwords[0] = 2u * static_cast<uint32_t>(ntf_new);
-      hw.src[1] = reinterpret_cast<const uint32_t*>(h_frame_slot_.data());
-      hw.dst[1] = reinterpret_cast<uint32_t*>(d_frame_slot_.get());
-      hw.nwords[1] = static_cast<uint32_t>(ntf_new);
-      hw.src[2] = reinterpret_cast<const uint32_t*>(h_frame_cif_row_.data());
-      hw.dst[2] = reinterpret_cast<uint32_t*>(d_frame_cif_row_.get());
-      hw.nwords[2] = static_cast<uint32_t>(ntf_new);
-      if (up && guard_active() && guard_launches_ == 0 && guard_reserve_counters(ntf_new)) {
-        hw.zero = d_guard_counter_.get();
-        hw.nzero = static_cast<uint32_t>(h_guard_counts_.size());
-        guard_counters_clear_ = true;
-      }
-      up = up && check(launch_host_words(hw, stream_), "frame list upload");
-    }
-    frames_ms += since(tfr);
-    return up;
-  };
   // Stage A: everything between the layout and the FIC decode -- buffers for the layout, then the FIC symbols (0..3) of every TF
   // through the OFDM stage.  K3 comes first so that the FIC is decoded, and the host control plane can run, while the bulk of the
   // OFDM stage still occupies the GPU: a launch of 4 / 76 of the work, so that the FIBs reach the host 2 ms before the MSC
@@ -1239,41 +1133,29 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
   const bool guard = guard_active();
   const bool soft = soft_bits_ != 0;
   const bool energies = guard || soft;                    // the per-symbol sample energies: the guard's error bounds, the soft scale
-  int ntf = 0, nslots = 0, chunk = 1;
-  uint8_t* fibs = nullptr;
-  uint8_t* ok = nullptr;
-  GuardArgs soft_args{};                                  // soft decisions, two-kernel stage: K2b reads the energies, lists nothing
+  int chunk = 1;
   auto stage_a = [&]() -> bool {
-    ntf = ntf_new;
-    nslots = tf_base[nstreams];
+    const int ntf = seg.ntf, nslots = seg.tf_base[nstreams];
     if (ntf == 0) return true;
-    if (!carry_and_reserve(tf_base, row_base, nslots, next_row + 1)) return false;
+    if (!carry_and_reserve(seg)) return false;
     if (heavy_mu_ && !heavy.owns_lock()) heavy = std::unique_lock<std::mutex>(*heavy_mu_);
     chunk = one_kernel ? std::max(ntf, 1) : std::min(ntf, kFftChunkTfs);   // only the spectra buffer of the two-kernel stage calls for chunks
     if (!one_kernel && !d_spectra_.reserve(static_cast<size_t>(chunk) * kSymbolsPerTf * 2048)) return false;
     if (!h_fibs_.resize(static_cast<size_t>(nslots) * 384) || !h_fib_ok_.resize(static_cast<size_t>(nslots) * 12)) return false;
-    fibs = h_fibs_.data();
-    ok = h_fib_ok_.data();
     if (!record(ev_[3], stream_)) return false;
     if (energies && !d_delta_.reserve(static_cast<size_t>(ntf) * kSymbolsPerTf)) return false;
     if (guard && guard_launches_ == 0 && !guard_counters_clear_ && !guard_reserve_counters(ntf)) return false;
-    soft_args.delta = d_delta_.get();
-    soft_args.delta_stride = kSymbolsPerTf;
-    soft_args.c = kSoftNormC;
     if (one_kernel) {
       for (int first = 0; first < ntf; first += chunk)
         if (!fused_parts(first, std::min(chunk, ntf - first), 1, 4, 1)) return false;      // the three FIC symbols (and symbol 0, their reference)
     } else {
       for (int first = 0; first < ntf; first += chunk * 19) {       // 4 of 76 symbols: 19 x as many TFs fit the spectra buffer
         const int n = std::min(chunk * 19, ntf - first);
-        GuardArgs ga = soft ? soft_args : GuardArgs{};   // (hard decisions: a non-null delta switches the guard's listing on)
+        GuardArgs ga = soft ? soft_guard_args() : GuardArgs{};   // (hard decisions: a non-null delta switches the guard's listing on)
         if (guard && !guard_begin(n, &ga)) return false;
-        if (energies && !check(launch_symbol_delta(d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), first, n, 4, d_delta_.get(), kSymbolsPerTf, soft ? kSoftNormC : guard_c_of(guard_rule_level()), stream_), "symbol delta launch"))
+        if (energies && !check(launch_symbol_delta(frame_list(), first, n, 4, d_delta_.get(), kSymbolsPerTf, soft ? kSoftNormC : guard_c_of(guard_rule_level()), stream_), "symbol delta launch"))
           return false;
-        if (!check(launch_fic_prepass(soft_bits_, d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), first, n, d_spectra_.get(), d_twf_.get(),
-                                      d_frame_slot_.get(), d_qpsk_.get(), d_fic_bits_.get(), ga, stream_),
-                   "fic pre-pass launch"))
-          return false;
+        if (!check(launch_fic_prepass(soft_bits_, frame_list(), first, n, d_spectra_.get(), ga, stream_), "fic pre-pass launch")) return false;
         if (guard && !guard_finish(true, first, n, 1, 4, false)) return false;
       }
     }
@@ -1281,15 +1163,17 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
     return true;
   };
   const bool early_a = !cont;
-  auto layout_and_a = [&]() -> bool { return layout() && (!early_a || stage_a()); };
+  auto layout_and_a = [&]() -> bool { return layout_frames(nbytes, nstreams) && (!early_a || stage_a()); };
   if (!scan_streams(iq, nbytes, nstreams, on_device, cont, full_scan, layout_and_a)) return -1;
   mark("scan done");
   times_.setup = scan_setup_ms_;
-  for (int b = 0; b < nstreams; ++b) calls_done_[b] = std::max(calls_done_[b], static_cast<int>(nbytes[b] / kChunkBytes));
+  for (int b = 0; b < nstreams; ++b) carry_[b].calls_done = std::max(carry_[b].calls_done, static_cast<int>(nbytes[b] / kChunkBytes));
   if (!early_a && !stage_a()) return -1;
-  last_ntf_ = ntf;
-  if (ntf == 0) return 0;                   // nothing demodulated: layout and carried data stay as they are
-  times_.frames = frames_ms;
+  const int ntf = seg.ntf, nslots = seg.tf_base[nstreams];
+  uint8_t* const fibs = h_fibs_.data();
+  uint8_t* const ok = h_fib_ok_.data();
+  if (ntf == 0) return 0;                   // nothing demodulated: the carried data stay as they are
+  times_.frames = layout_ms_;
   if (guard) guard_decisions_ += static_cast<int64_t>(ntf) * (kFicBits + kMscBits);
   // FIC decode kernels and the FIB download on the side stream: the rest of the OFDM stage is queued on the main stream right
   // away and shares the GPU with them, waiting neither for the download nor for the host
@@ -1297,11 +1181,10 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
 
   // K2 + K2b over the MSC symbols of the frames that can be locked: [0, nmsc) of the list (ofdm_msc_part); the deferred ones stay as they are
   bool gpu_ok = true;
-  const int nchunks = (nmsc + chunk - 1) / chunk;
-  while (static_cast<int>(chunk_ev_.size()) < 3 * nchunks) {
-    hipEvent_t e = nullptr;
-    if (!check(hipEventCreate(&e), "hipEventCreate")) { gpu_ok = false; break; }
-    chunk_ev_.push_back(e);
+  const int nmsc = seg.nmsc, nchunks = (nmsc + chunk - 1) / chunk;
+  while (gpu_ok && static_cast<int>(chunk_ev_.size()) < 3 * nchunks) {
+    chunk_ev_.emplace_back();
+    gpu_ok = check(chunk_ev_.back().create(), "hipEventCreate");
   }
   gpu_ok = gpu_ok && ofdm_msc_part(0, nmsc, chunk, 0);
   mark("ofdm queued");
@@ -1316,12 +1199,10 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
   }
 
   // control plane + work lists on a host thread, hidden behind the MSC symbols' part of the OFDM stage
-  std::vector<ControlPlane>& planes = planes_;
   // host work lists live in the engine: ~35 MB per step at the benchmark size, reused instead of re-allocated
   std::vector<JobList>& stream_jobs = stream_jobs_;
   stream_jobs.resize(nstreams);
   for (auto& v : stream_jobs) v.clear();
-  MscWork& work = work_;
   bool host_ok = true;
   std::string host_error;
   // (on the engine's persistent lane since round 3; a std::thread created and joined per decode measured the same on an idle host:
@@ -1332,23 +1213,23 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
     const bool fresh = planes_fresh_;
     pool_->parallel_for(nstreams, [&](int b) {
       if (fresh) {
-        planes[b] = ControlPlane();
-        planes[b].set_filter(subch_keep_);
+        planes_[b] = ControlPlane();
+        planes_[b].set_filter(subch_keep_);
       }
-      stream_jobs[b].reserve(static_cast<size_t>(4) * nnew[b]);
-      planes[b].rebase(4 * (prev_used_[b] - carry_keep_[b]));   // CIF numbering of this segment's layout
-      for (int s = tf_base[b] + carry_keep_[b]; s < tf_base[b + 1]; ++s)
-        planes[b].on_tf(s - tf_base[b], fibs + static_cast<size_t>(s) * 384, ok + static_cast<size_t>(s) * 12, stream_jobs[b]);
+      stream_jobs[b].reserve(static_cast<size_t>(4) * seg.nnew[b]);
+      planes_[b].rebase(4 * (carry_[b].prev_used - carry_[b].keep));   // CIF numbering of this segment's layout
+      for (int s = seg.tf_base[b] + carry_[b].keep; s < seg.tf_base[b + 1]; ++s)
+        planes_[b].on_tf(s - seg.tf_base[b], fibs + static_cast<size_t>(s) * 384, ok + static_cast<size_t>(s) * 12, stream_jobs[b]);
     });
     std::vector<const ControlPlane*> plane_ptrs(nstreams);
     std::vector<const JobList*> job_ptrs(nstreams);
     total_eti_ = 0;
     for (int b = 0; b < nstreams; ++b) {
-      plane_ptrs[b] = &planes[b];
+      plane_ptrs[b] = &planes_[b];
       job_ptrs[b] = &stream_jobs[b];
       eti_base_[b] = total_eti_;
       eti_count_[b] = static_cast<int64_t>(stream_jobs[b].size());
-      stream_status_[b] = planes[b].fault();
+      stream_status_[b] = planes_[b].fault();
       total_eti_ += eti_count_[b];
     }
     planes_fresh_ = false;
@@ -1356,9 +1237,9 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
     mark("control plane done");
     const auto t1 = std::chrono::steady_clock::now();
     // the work lists go up on the side stream while the OFDM stage still runs on the main one
-    host_ok = msc_prepare(job_ptrs, plane_ptrs, row_base, fib_base, work);
+    host_ok = msc_prepare(job_ptrs, plane_ptrs, seg.row_base, seg.fib_base, work_);
     mark("work lists built");
-    host_ok = host_ok && msc_upload(work, copy_stream_) && check(hipEventRecord(ev_upload_, copy_stream_), "work list upload");
+    host_ok = host_ok && msc_upload(work_, copy_stream_) && check(hipEventRecord(ev_upload_, copy_stream_), "work list upload");
     mark("work lists queued");
     if (!host_ok) host_error = dabhip_last_error();
     times_.worklist = since(t1);
@@ -1370,7 +1251,7 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
   if (gpu_ok && host_ok)
     // (the upload is normally through long before this point: then no wait is queued at all -- a wait on an event that has already fired still costs the
     // main stream a barrier packet, 10 .. 15 us of idle GPU before K4)
-    gpu_ok = (hipEventQuery(ev_upload_) == hipSuccess || check(hipStreamWaitEvent(stream_, ev_upload_, 0), "work list wait")) && msc_launch_async(work);
+    gpu_ok = (hipEventQuery(ev_upload_) == hipSuccess || check(hipStreamWaitEvent(stream_, ev_upload_, 0), "work list wait")) && msc_launch_async(work_);
   if (guard && gpu_ok) gpu_ok = guard_download();        // the entry counts of all guarded launches, behind everything else
   mark("all queued");
   const bool drained = check(hipStreamSynchronize(stream_), "decode");      // also on the error paths: nothing may stay in flight
@@ -1392,27 +1273,10 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
   if (!on_device && times_.h2d_bytes > 0 && !elapsed(&times_.h2d, ev_h2d_[0], ev_h2d_[1])) return -1;
   if (guard && !guard_check()) return -1;
   // what the next segment of a session starts from
-  msc_missing_.resize(nstreams);
-  last_keep_.assign(nstreams, 0);
-  for (int b = 0; b < nstreams; ++b) {
-    // carried slots keep their flag (a deferred TF of an earlier segment cannot be completed any more), this segment's deferred ones get theirs
-    std::vector<uint8_t>& miss = msc_missing_[b];
-    const int keep = carry_keep_[b];
-    miss.resize(static_cast<size_t>(prev_used_[b]), 0);
-    miss.erase(miss.begin(), miss.end() - keep);
-    miss.resize(static_cast<size_t>(keep + nnew[b]), 0);
-    std::fill(miss.begin() + keep, miss.begin() + keep + ndefer_of[b], uint8_t(1));
-    last_keep_[b] = keep;
-    prev_used_[b] = carry_keep_[b] + nnew[b];
-    carry_keep_[b] = std::min(4, prev_used_[b]);
-    ord_done_[b] += nnew[b];
-  }
-  last_msc_n_ = nmsc;
-  last_chunk_ = chunk;
-  msc_deferred_ = ntf - nmsc;
-  msc_pending_ = msc_deferred_ > 0;
-  prev_tf_base_ = tf_base;
-  prev_row_base_ = row_base;
+  for (int b = 0; b < nstreams; ++b) carry_[b].advance(seg, b);
+  last_.chunk = chunk;
+  last_.deferred = ntf - nmsc;
+  last_.pending = last_.deferred > 0;
   times_.wall = since(wall0);
   mark("return");
   return total_eti_;
@@ -1491,9 +1355,9 @@ int Engine::trace_nco(int stream, int32_t* nco_hz, int cap_calls) const
 int Engine::fft_roofline(int reps, int64_t* launches, int64_t* tfs, double* ms)
 {
   if (!ok_) { set_error("engine not initialised (no GPU?)"); return -1; }
-  if (last_ntf_ <= 0) { set_error("fft_roofline: no decode to measure on"); return -1; }
+  if (seg_.ntf <= 0) { set_error("fft_roofline: no decode to measure on"); return -1; }
   if (!check(hipSetDevice(device_), "hipSetDevice")) return -1;
-  const int ntf = last_ntf_, chunk = std::min(ntf, kFftChunkTfs);
+  const int ntf = seg_.ntf, chunk = std::min(ntf, kFftChunkTfs);
   if (!d_spectra_.reserve(static_cast<size_t>(chunk) * kSymbolsPerTf * 2048)) return -1;
   reps = std::max(reps, 1);
   int64_t nl = 0, nt = 0;
@@ -1502,7 +1366,7 @@ int Engine::fft_roofline(int reps, int64_t* launches, int64_t* tfs, double* ms)
     for (int first = 0; first < ntf; first += chunk) {
       const int n = std::min(chunk, ntf - first);
       if (!record(ev_[0], stream_)) return -1;
-      if (!check(launch_ofdm_fft(d_iq_ptrs_.get(), d_descs_.get(), max_calls_, d_frames_.get(), first, n, d_spectra_.get(), d_twf_.get(), stream_), "fft launch")) return -1;
+      if (!check(launch_ofdm_fft(frame_list(), first, n, d_spectra_.get(), stream_), "fft launch")) return -1;
       if (!record(ev_[1], stream_)) return -1;
       if (!check(hipEventSynchronize(ev_[1]), "fft")) return -1;
       float t = 0;
@@ -1534,26 +1398,22 @@ int Engine::stage_ofdm_fft(const uint8_t* frames, int nframes, float* spectra, b
     if (!d_iq_own_.reserve(bytes) || !check(blocking_copy(d_iq_own_.get(), frames, bytes, hipMemcpyHostToDevice), "frame upload")) return -1;
     d_in = d_iq_own_.get();
   }
-  std::vector<CallDesc> descs(nframes);
-  std::vector<int2> list(nframes);
-  for (int j = 0; j < nframes; ++j) {
-    std::memset(&descs[j], 0, sizeof(CallDesc));
-    descs[j].status = 2;
-    descs[j].ordinal = j;
-    descs[j].view = initial_state().view;
-    descs[j].view.seg_src[0] = static_cast<int64_t>(j) * kTfBytes;
-    list[j] = make_int2(0, j);
-  }
+  std::vector<CallDesc> descs;
+  std::vector<int2> list;
+  std::vector<int> slots, rows;
+  contiguous_frames(0, nframes, 0, descs, list, slots, rows);
   std::vector<const uint8_t*> ptrs = {d_in};
   const size_t nspec = static_cast<size_t>(nframes) * kSymbolsPerTf * 2048;
-  msc_pending_ = false;             // the last decode's frame list and descriptors are gone: its deferred TFs can no longer be completed
+  last_.pending = false;             // the last decode's frame list and descriptors are gone: its deferred TFs can no longer be completed
   if (!d_iq_ptrs_.upload(ptrs, stream_) || !d_descs_.upload(descs, stream_) || !d_frames_.upload(list, stream_) || !d_spectra_.reserve(nspec)) return -1;
   reps = std::max(reps, 1);
+  FrameListArgs fl = frame_list();
+  fl.max_calls = nframes;                                 // (one stream: its descriptors are descs[call] whatever max_calls says)
   // one untimed launch first when timing
-  if (reps > 1 && !check(launch_ofdm_fft(d_iq_ptrs_.get(), d_descs_.get(), nframes, d_frames_.get(), 0, nframes, d_spectra_.get(), d_twf_.get(), stream_), "fft launch")) return -1;
+  if (reps > 1 && !check(launch_ofdm_fft(fl, 0, nframes, d_spectra_.get(), stream_), "fft launch")) return -1;
   if (!record(ev_[0], stream_)) return -1;
   for (int r = 0; r < reps; ++r)
-    if (!check(launch_ofdm_fft(d_iq_ptrs_.get(), d_descs_.get(), nframes, d_frames_.get(), 0, nframes, d_spectra_.get(), d_twf_.get(), stream_), "fft launch")) return -1;
+    if (!check(launch_ofdm_fft(fl, 0, nframes, d_spectra_.get(), stream_), "fft launch")) return -1;
   if (!record(ev_[1], stream_)) return -1;
   if (!check(hipEventSynchronize(ev_[1]), "fft")) return -1;
   float ms = 0;
@@ -1610,7 +1470,6 @@ int Engine::stage_decision_audit(const uint8_t* frames, int nframes, bool on_dev
   if (!hard_only("stage_decision_audit")) return -1;
   if (nframes <= 0 || !out8) return 0;
   if (fused) return stage_decision_audit_fused(frames, nframes, on_device, guard_on, out8, out_extra);
-  struct AuditOut { unsigned long long decisions, disagree, outside, flagged; unsigned bin_bits, dec_bits, prod_bits, pad; };
   DeviceBuffer<uint8_t> d_out;
   if (!d_out.reserve(sizeof(AuditOut)) || !check(hipMemsetAsync(d_out.get(), 0, sizeof(AuditOut), stream_), "audit memset")) return -1;
   const int chunk = 256;
@@ -1624,22 +1483,13 @@ int Engine::stage_decision_audit(const uint8_t* frames, int nframes, bool on_dev
   }
   for (int first = 0; first < nframes; first += chunk) {
     const int n = std::min(chunk, nframes - first);
-    std::vector<CallDesc> descs(n);
-    std::vector<int2> list(n);
-    std::vector<int> slots(n), rows(n);
-    for (int j = 0; j < n; ++j) {
-      std::memset(&descs[j], 0, sizeof(CallDesc));
-      descs[j].status = 2;
-      descs[j].ordinal = j;
-      descs[j].view = initial_state().view;
-      descs[j].view.seg_src[0] = static_cast<int64_t>(first + j) * kTfBytes;
-      list[j] = make_int2(0, j);
-      slots[j] = j;
-      rows[j] = 4 * j;
-    }
+    std::vector<CallDesc> descs;
+    std::vector<int2> list;
+    std::vector<int> slots, rows;
+    contiguous_frames(first, n, 0, descs, list, slots, rows);
     std::vector<const uint8_t*> ptrs = {d_in};
     max_calls_ = n;
-    msc_pending_ = false;             // the last decode's frame list and descriptors are gone: its deferred TFs can no longer be completed
+    last_.pending = false;             // the last decode's frame list and descriptors are gone: its deferred TFs can no longer be completed
     if (!reserve_tf_slots(n) || !d_iq_ptrs_.upload(ptrs, stream_) || !d_descs_.upload(descs, stream_) || !d_frames_.upload(list, stream_) ||
         !d_frame_slot_.upload(slots, stream_) || !d_frame_cif_row_.upload(rows, stream_) || !d_spectra_.reserve(static_cast<size_t>(n) * kSymbolsPerTf * 2048))
       return -1;
@@ -1648,9 +1498,9 @@ int Engine::stage_decision_audit(const uint8_t* frames, int nframes, bool on_dev
     guard_counters_clear_ = false;
     guard_flagged_ = 0;
     if (guard_on && (!d_delta_.reserve(static_cast<size_t>(n) * kSymbolsPerTf) || !guard_begin(n, &ga) ||
-                     !check(launch_symbol_delta(d_iq_ptrs_.get(), d_descs_.get(), n, d_frames_.get(), 0, n, kSymbolsPerTf, d_delta_.get(), kSymbolsPerTf, guard_c_of(guard_rule_level()), stream_), "symbol delta launch")))
+                     !check(launch_symbol_delta(frame_list(), 0, n, kSymbolsPerTf, d_delta_.get(), kSymbolsPerTf, guard_c_of(guard_rule_level()), stream_), "symbol delta launch")))
       return -1;
-    if (!check(launch_ofdm_fft(d_iq_ptrs_.get(), d_descs_.get(), n, d_frames_.get(), 0, n, d_spectra_.get(), d_twf_.get(), stream_), "fft launch") ||
+    if (!check(launch_ofdm_fft(frame_list(), 0, n, d_spectra_.get(), stream_), "fft launch") ||
         !check(launch_demap(false, 0, d_spectra_.get(), 0, n, d_frame_slot_.get(), d_frame_cif_row_.get(), d_qpsk_.get(), d_fic_bits_.get(), d_msc_bits_.get(), ga, stream_), "demap launch") ||
         (guard_on && !guard_finish(false, 0, n, 1, kSymbolsPerTf, false)) ||
         !check(launch_decision_audit(d_in + static_cast<size_t>(first) * kTfBytes, n, d_spectra_.get(), d_fic_bits_.get(), d_msc_bits_.get(), d_tw2048_.get(), d_qpsk_.get(), d_out.get(), stream_, nullptr, 0, guard_rule_level()), "audit launch") ||
@@ -1658,17 +1508,12 @@ int Engine::stage_decision_audit(const uint8_t* frames, int nframes, bool on_dev
       return -1;
     listed += static_cast<uint64_t>(guard_flagged_);
   }
-  AuditOut h;
-  if (!check(blocking_copy(&h, d_out.get(), sizeof h, hipMemcpyDeviceToHost), "audit download")) return -1;
-  auto f = [](unsigned bits) { float v; std::memcpy(&v, &bits, 4); return static_cast<double>(v); };
-  out8[0] = static_cast<double>(h.decisions); out8[1] = static_cast<double>(h.disagree); out8[2] = static_cast<double>(h.outside);
-  out8[3] = static_cast<double>(h.flagged); out8[4] = f(h.bin_bits); out8[5] = f(h.dec_bits); out8[6] = f(h.prod_bits); out8[7] = static_cast<double>(listed);
+  if (!read_audit(d_out.get(), listed, out8)) { set_error("audit download failed"); return -1; }
   return nframes;
 }
 
 int Engine::stage_decision_audit_fused(const uint8_t* frames, int nframes, bool on_device, bool guard_on, double* out8, double* out_extra)
 {
-  struct AuditOut { unsigned long long decisions, disagree, outside, flagged; unsigned bin_bits, dec_bits, prod_bits, pad; };
   DeviceBuffer<uint8_t> d_out;
   DeviceBuffer<float2> d_bins, d_prod;
   if (!d_out.reserve(sizeof(AuditOut)) || !check(hipMemsetAsync(d_out.get(), 0, sizeof(AuditOut), stream_), "audit memset")) return -1;
@@ -1687,22 +1532,13 @@ int Engine::stage_decision_audit_fused(const uint8_t* frames, int nframes, bool 
   std::vector<uint32_t> bits_a, bits_b;
   for (int first = 0; first < nframes; first += chunk) {
     const int n = std::min(chunk, nframes - first);
-    std::vector<CallDesc> descs(n);
-    std::vector<int2> list(n);
-    std::vector<int> slots(n), rows(n);
-    for (int j = 0; j < n; ++j) {
-      std::memset(&descs[j], 0, sizeof(CallDesc));
-      descs[j].status = 2;
-      descs[j].ordinal = j;
-      descs[j].view = initial_state().view;
-      descs[j].view.seg_src[0] = static_cast<int64_t>(first + j) * kTfBytes;
-      list[j] = make_int2(0, j);
-      slots[j] = j;
-      rows[j] = kRowLead + 4 * j;                         // where a decode puts the frame's first CIF: the scatter reaches kRowLead rows back
-    }
+    std::vector<CallDesc> descs;
+    std::vector<int2> list;
+    std::vector<int> slots, rows;
+    contiguous_frames(first, n, kRowLead, descs, list, slots, rows);      // (where a decode puts the frame's first CIF: the scatter reaches kRowLead rows back)
     std::vector<const uint8_t*> ptrs = {d_in};
     max_calls_ = n;
-    msc_pending_ = false;             // the last decode's frame list and descriptors are gone: its deferred TFs can no longer be completed
+    last_.pending = false;             // the last decode's frame list and descriptors are gone: its deferred TFs can no longer be completed
     if (!reserve_tf_slots(n) || !d_iq_ptrs_.upload(ptrs, stream_) || !d_descs_.upload(descs, stream_) || !d_frames_.upload(list, stream_) ||
         !d_frame_slot_.upload(slots, stream_) || !d_frame_cif_row_.upload(rows, stream_) || !d_delta_.reserve(static_cast<size_t>(n) * kSymbolsPerTf))
       return -1;
@@ -1719,10 +1555,8 @@ int Engine::stage_decision_audit_fused(const uint8_t* frames, int nframes, bool 
         const int sym_a = part ? 4 : 1, sym_b = part ? kSymbolsPerTf : 4;
         if (!guard_begin(n, &ga)) return -1;
         const hipError_t e = pass == 0
-            ? launch_ofdm_demap_fused_guarded(d_iq_ptrs_.get(), d_descs_.get(), n, d_frames_.get(), 0, n, d_twf_.get(), d_frame_slot_.get(), d_frame_cif_row_.get(),
-                                              d_qpsk_.get(), d_fic_bits_.get(), d_msc_bits_.get(), ga, stream_, sym_a, sym_b, 1)
-            : launch_ofdm_demap_fused_audit(d_iq_ptrs_.get(), d_descs_.get(), n, d_frames_.get(), 0, n, d_twf_.get(), d_frame_slot_.get(), d_frame_cif_row_.get(),
-                                            d_qpsk_.get(), d_fic_bits_.get(), d_msc_bits_.get(), ga, stream_, sym_a, sym_b, 1, d_bins.get(), d_prod.get());
+            ? launch_ofdm_demap_fused_guarded(frame_list(), 0, n, ga, stream_, sym_a, sym_b, 1)
+            : launch_ofdm_demap_fused_audit(frame_list(), 0, n, ga, stream_, sym_a, sym_b, 1, d_bins.get(), d_prod.get());
         if (!check(e, "fused audit launch")) return -1;
         if (pass == 1 && guard_on) {
           if (!guard_finish(true, 0, n, sym_a, sym_b, false)) return -1;
@@ -1748,11 +1582,7 @@ int Engine::stage_decision_audit_fused(const uint8_t* frames, int nframes, bool 
     list_equal = list_equal && counts[0] == counts[1];
     if (!guard_on) bits_equal = bits_equal && bits_a == bits_b;
   }
-  AuditOut h;
-  if (!check(blocking_copy(&h, d_out.get(), sizeof h, hipMemcpyDeviceToHost), "audit download")) return -1;
-  auto f = [](unsigned bits) { float v; std::memcpy(&v, &bits, 4); return static_cast<double>(v); };
-  out8[0] = static_cast<double>(h.decisions); out8[1] = static_cast<double>(h.disagree); out8[2] = static_cast<double>(h.outside);
-  out8[3] = static_cast<double>(h.flagged); out8[4] = f(h.bin_bits); out8[5] = f(h.dec_bits); out8[6] = f(h.prod_bits); out8[7] = static_cast<double>(listed);
+  if (!read_audit(d_out.get(), listed, out8)) { set_error("audit download failed"); return -1; }
   if (out_extra) {
     out_extra[0] = guard_on ? -1.0 : (bits_equal ? 1.0 : 0.0);      // (compared on the raw bits only: with the guard on the audit pass's bits are the re-decided ones)
     out_extra[1] = list_equal ? 1.0 : 0.0;
@@ -1832,7 +1662,7 @@ bool Engine::demod_one_frame(const uint8_t* iq_virtual_base, const CallDesc& des
   std::vector<int2> list = {make_int2(0, 0)};
   std::vector<int> slots = {0};
   std::vector<CallDesc> d = {desc};
-  msc_pending_ = false;             // the last decode's frame list and descriptors are gone: its deferred TFs can no longer be completed
+  last_.pending = false;             // the last decode's frame list and descriptors are gone: its deferred TFs can no longer be completed
   if (!reserve_tf_slots(1) || !d_iq_ptrs_.upload(ptrs, stream_) || !d_descs_.upload(d, stream_) || !d_frames_.upload(list, stream_) ||
       !d_frame_slot_.upload(slots, stream_) || !d_frame_cif_row_.upload(slots, stream_) ||
       !d_spectra_.reserve(static_cast<size_t>(kSymbolsPerTf) * 2048))
@@ -1843,9 +1673,9 @@ bool Engine::demod_one_frame(const uint8_t* iq_virtual_base, const CallDesc& des
   guard_launches_ = 0;
   guard_counters_clear_ = false;
   if (guard && (!d_delta_.reserve(kSymbolsPerTf) || !guard_begin(1, &ga) ||
-                !check(launch_symbol_delta(d_iq_ptrs_.get(), d_descs_.get(), 1, d_frames_.get(), 0, 1, kSymbolsPerTf, d_delta_.get(), kSymbolsPerTf, guard_c_of(guard_rule_level()), stream_), "symbol delta launch")))
+                !check(launch_symbol_delta(frame_list(), 0, 1, kSymbolsPerTf, d_delta_.get(), kSymbolsPerTf, guard_c_of(guard_rule_level()), stream_), "symbol delta launch")))
     return false;
-  if (!check(launch_ofdm_fft(d_iq_ptrs_.get(), d_descs_.get(), 1, d_frames_.get(), 0, 1, d_spectra_.get(), d_twf_.get(), stream_), "fft launch") ||
+  if (!check(launch_ofdm_fft(frame_list(), 0, 1, d_spectra_.get(), stream_), "fft launch") ||
       !check(launch_demap(false, 0, d_spectra_.get(), 0, 1, d_frame_slot_.get(), d_frame_cif_row_.get(), d_qpsk_.get(), d_fic_bits_.get(), d_msc_bits_.get(), ga, stream_), "demap launch") ||
       (guard && !guard_finish(false, 0, 1, 1, kSymbolsPerTf, false)) || (guard && !guard_download()) ||
       !check(hipStreamSynchronize(stream_), "demod") || (guard && !guard_check()))

@@ -21,15 +21,19 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "control_plane.hpp"
+#include "decoder_form.hpp"
 #include "device_types.hpp"
+#include "segment_layout.hpp"
 #include "thread_pool.hpp"
 #include "worklist.hpp"
 
 namespace dabhip {
 
+struct FrameListArgs;     // kernels.hpp
 void set_error(const std::string& msg);
 
 // The HIP runtime keeps its records of a stream's finished commands until somebody synchronises THAT STREAM: an event or a blocking copy that waits
@@ -91,6 +95,19 @@ class DeviceBuffer {
  private:
   T* p_ = nullptr;
   size_t cap_ = 0;
+};
+
+// a HIP event, created on demand (with or without timing) and destroyed with its owner
+class Event {
+ public:
+  Event() = default;
+  Event(Event&& o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+  ~Event() { if (e_) (void)hipEventDestroy(e_); }
+  hipError_t create(bool timing = true) { return timing ? hipEventCreate(&e_) : hipEventCreateWithFlags(&e_, hipEventDisableTiming); }
+  operator hipEvent_t() const { return e_; }
+
+ private:
+  hipEvent_t e_ = nullptr;
 };
 
 // std::allocator over page-locked host memory: vectors that are uploaded every decode (the work lists) go to the device
@@ -190,7 +207,7 @@ class Engine {
   // the first 9 - okcount TFs of a stream that is not locked when the decode starts) are not demodulated: no ETI frame ever reads them.
   // read_demapped_tf completes them on demand.  on = true (DABHIP_DEMOD_ALL=1): every TF is demodulated in full, as before.
   void set_demod_all(bool on) { demod_all_ = on; }
-  int msc_deferred() const { return msc_deferred_; }     // TFs of the last decode / segment whose MSC part was deferred (completed on demand or not)
+  int msc_deferred() const { return last_.deferred; }    // TFs of the last decode / segment whose MSC part was deferred (completed on demand or not)
   // K1's chain: 0 = call after call, 1 = with the look-ahead pass, -1 = the pass for small batches (include/dabhip.h: dabhip_engine_set_sync_speculation)
   void set_sync_speculation(int mode) { spec_mode_ = mode < 0 ? -1 : (mode > 0 ? 1 : 0); }
   // sub-channel filter (TODO.md:28-31): bit i = SubChId i is decoded and carried in the ETI frames; takes effect with the next
@@ -287,14 +304,13 @@ class Engine {
   bool hard_only(const char* what);
   int64_t decode_impl(const uint8_t* const* iq, const size_t* nbytes, int nstreams, bool on_device, bool cont, bool full_scan = false);
   bool begin_decode(int nstreams, bool cont);
+  bool layout_frames(const size_t* nbytes, int nstreams);
   // layout: called when the calls' {status, ordinal} are on the host (h_info_) -- early in the split scan, again after a re-scan
   bool scan_streams(const uint8_t* const* iq, const size_t* nbytes, int nstreams, bool on_device, bool cont, bool full_scan,
                     const std::function<bool()>& layout);
   // host-fed decode: the streams' bytes into d_iq_own_ (ptrs[b] = where stream b landed), queued on the main stream
   bool upload_iq(const uint8_t* const* iq, const size_t* nbytes, int nstreams, const uint8_t** ptrs);
-  bool carry_and_reserve(const std::vector<int>& tf_base, const std::vector<int>& row_base, int nslots, int nrows);
-  // MSC decode batch: work lists to the device, regroup + fused Viterbi launches
-  bool upload_decode_batch(const DecodeBatch& b, const HostList<DecodeJob>& jobs, hipStream_t s);
+  bool carry_and_reserve(const SegmentLayout& seg);
   // Several small host arrays to the device in one launch per four of them (launch_host_words: the kernel reads page-locked host memory itself) instead
   // of one copy-engine command each -- a small decode is made of those commands and the 5 .. 10 us of idle GPU between two of them.  Arrays that are
   // not page-locked are staged in `staging` first.  The staging words and the page-locked sources are read when the launch RUNS, not when it is queued:
@@ -310,11 +326,11 @@ class Engine {
   static constexpr size_t kSmallUploadBytes = 256 * 1024;
   struct SmallStage {
     PinnedBuffer<uint32_t> words;
-    hipEvent_t done = nullptr;               // recorded behind the stage's last launch
+    Event done;                              // recorded behind the stage's last launch
     bool armed = false;
-    ~SmallStage() { if (done) (void)hipEventDestroy(done); }
   };
   bool upload_small(const SmallUpload* items, int n, hipStream_t s, SmallStage& staging);
+  // MSC decode batch (its work lists uploaded: msc_upload): regroup + Viterbi launches
   bool launch_decode_batch(const DecodeBatch& b, const uint32_t* bits, const int* d_stream_cif_base, const uint32_t* prbs, uint8_t* out,
                            int record_stride);
   bool msc_launch_async(const MscWork& w);   // K4 + K5 queued, nothing awaited
@@ -333,6 +349,8 @@ class Engine {
   // the OFDM stage's launches over frames [first, first + n) of the frame list: fused_parts = the one-kernel stage's data symbols [sym_a, sym_b);
   // ofdm_msc_part = the 72 MSC symbols through the configured stage (fused / two-kernel, hard / soft, guard as set) in chunks of `chunk` frames,
   // with three timing events per chunk from chunk_ev_[3 * ev_base] on when ev_base >= 0
+  FrameListArgs frame_list() const;    // the block those launches share, from the buffers as they stand now (kernels.hpp)
+  GuardArgs soft_guard_args() const;   // soft decisions, two-kernel stage: K2b reads the energies K2 left, lists nothing
   bool fused_parts(int first, int n, int sym_a, int sym_b, int nparts);
   bool ofdm_msc_part(int first, int n, int chunk, int ev_base);
   bool complete_deferred();            // read_demapped_tf: the MSC part of the last decode's deferred frames, awaited
@@ -343,21 +361,7 @@ class Engine {
   int guard_level_ = kDefaultGuardLevel;
   uint64_t subch_keep_ = ~0ull;
   int soft_bits_ = 0;
-  // Decodes of at most this many code words (MSC: ETI frames x sub-channels; FIC: 4 per TF) run one WAVE per code word (k_vitwave.hip: latency
-  // of a code word 0.1 instead of 1.4 ms) instead of one lane per code word (viterbi_fused_kernel: a sixth of the lane-ops).  DABHIP_VIT_WAVE_MAX.
-  int wave_max_codewords_ = 12288, wave_max_fic_blocks_ = 3072;     // measured crossovers (tools/gpu/wavesweep.sh): MSC 5..6 streams x 64 TF, FIC 12..16
-  // Above that, hard-decision decodes of at most this many groups of 64 code words run TWO LANES per code word (vit_two_lanes.hpp): while the lane form
-  // would leave the SIMDs at one or two waves (8 .. 40 streams x 64 TF: decoder stage 1.45 -> 0.96 ms at 16 streams).  Measured crossover between 32 and
-  // 64 streams (1,176 and 2,352 groups; profiles/r06_two_lanes_curve.txt).  DABHIP_VIT_TWO_LANES = 0 / 1 / N: never / always / at most N groups.
-  int two_lanes_max_groups_ = 1536;
-  // ... and of at most this many groups FOUR lanes per code word (vit_four_lanes.hpp): decoder stage 0.96 -> 0.82 ms at 8 and 16 streams, the same as
-  // two lanes at 32 (1,176 groups; profiles/r06_lanes_curve.txt).  DABHIP_VIT_FOUR_LANES = 0 / 1 / N likewise;
-  // DABHIP_VIT_LANES_PLAIN=1 (measurement) runs the two-lane decodes through that file's table-free two-lane form instead of vit_two_lanes.hpp's.
-  int four_lanes_max_groups_ = 800;
-  bool two_lanes_plain_ = false;
-  // FIC decodes of at most this many tiles of 64 blocks (above the wave form's range: 12 .. 32 streams x 64 TF) run four lanes per block: FIC stage 0.32 -> 0.24 ms
-  // at 16 streams, 0.58 -> 0.50 at 32, nothing from 64 streams (256 tiles) on.  DABHIP_FIC_FOUR_LANES = 0 / 1 / N
-  int fic_four_lanes_max_tiles_ = 128;
+  FormKnobs knobs_;                            // decoder_form.hpp: the thresholds of the forms' rule, environment overrides applied
   int msc_form_ = -1, fic_form_ = -1;          // set_decoder_forms: -1 = the rules above
   std::atomic<uint32_t> msc_ran_{0}, fic_ran_{0};
   std::mutex* heavy_mu_ = nullptr;
@@ -366,26 +370,23 @@ class Engine {
   int device_ = 0, numa_node_ = -1;
   std::vector<int> host_cpus_;
   hipStream_t stream_ = nullptr, copy_stream_ = nullptr;   // copy_stream_: work-list uploads from the control-plane thread
-  hipEvent_t ev_[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_upload_ = nullptr, ev_fic_ = nullptr, ev_fic_done_ = nullptr, ev_fibs_ = nullptr, ev_part0_ = nullptr, ev_chain_ = nullptr, ev_info_ = nullptr;
-  hipEvent_t ev_msc_[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_h2d_[2] = {nullptr, nullptr};
+  Event ev_[4], ev_upload_, ev_fic_, ev_fic_done_, ev_fibs_, ev_part0_, ev_chain_, ev_info_, ev_msc_[4], ev_h2d_[2];
   hipStream_t d2h_stream_ = nullptr;           // eti_fetch_async
-  hipEvent_t ev_eti_fetch_[2] = {nullptr, nullptr};              // one per outstanding fetch (at most two)
+  Event ev_eti_fetch_[2];                      // one per outstanding fetch (at most two; no timing)
   std::atomic<uint64_t> eti_fetch_issued_{0}, eti_fetch_waited_{0};   // (issued: the decoding thread; waited: whichever thread waits -- the CLI's writer)
   // page-locked staging ring for uploads from pageable memory: the host pool copies piece n + 1 into one buffer while the DMA of
   // piece n drains another
   static constexpr int kStageBufs = 4;
   PinnedBuffer<uint8_t> stage_buf_[kStageBufs];
-  hipEvent_t stage_ev_[kStageBufs] = {nullptr, nullptr, nullptr, nullptr};
+  Event stage_ev_[kStageBufs];                 // (no timing)
   bool msc_queued_ = false;
-  std::vector<hipEvent_t> chunk_ev_;
+  std::vector<Event> chunk_ev_;
 
   // constant tables
   DeviceBuffer<double2> d_tw2048_, d_tw1536_;
   DeviceBuffer<uint8_t> d_prs_;
   DeviceBuffer<float2> d_twf_;
-  DeviceBuffer<uint16_t> d_qpsk_, d_qpsk_inv_, d_crc_tab_, d_crc_shift_;
+  DeviceBuffer<uint16_t> d_qpsk_, d_crc_tab_, d_crc_shift_;
   DeviceBuffer<uint32_t> d_prbs_, d_zero_words_;
 
   // batch state
@@ -433,7 +434,13 @@ class Engine {
   PinnedBuffer<const uint8_t*> h_ptrs_;
   PinnedBuffer<int64_t> h_nb_;
   PinnedBuffer<int> h_frame_slot_, h_frame_cif_row_;
-  std::vector<int> carry_keep_, prev_used_, calls_done_, ord_done_, prev_tf_base_, prev_row_base_;
+  std::vector<StreamCarry> carry_;             // segment_layout.hpp: what a segment hands to the next
+  // The last decode's layout: its frame list holds the frames whose MSC part ran at [0, seg_.nmsc) and the deferred ones (lock-in skip) behind them, up to
+  // seg_.ntf.  pending: their samples, descriptors and the list are still those of that decode, so read_demapped_tf can complete them (in chunks of
+  // `chunk` frames, like the decode); deferred = how many there were
+  SegmentLayout seg_;
+  struct { int chunk = 1, deferred = 0; bool pending = false; } last_;
+  std::vector<int> seg_ncalls_, seg_defer_max_;   // layout_segment's per-stream inputs
   DeviceBuffer<float> d_delta_;
   DeviceBuffer<uint4> d_guard_list_;
   DeviceBuffer<uint32_t> d_guard_counter_;
@@ -453,15 +460,8 @@ class Engine {
   PinnedBuffer<CallDesc> h_descs_;
   PinnedBuffer<int2> h_info_;
   PinnedBuffer<uint8_t> h_fibs_, h_fib_ok_;
-  int max_calls_ = 0, nstreams_ = 0, last_ntf_ = 0;
-  // lock-in skip: the last decode's frame list holds the frames whose MSC part ran at [0, last_msc_n_) and the deferred ones behind them, up to last_ntf_
-  // (pending: their samples, descriptors and the list are still those of that decode, so read_demapped_tf can complete them); msc_missing_[b][slot] = the
-  // MSC rows of that TF slot of stream b (layout of the last decode, carried slots first: last_keep_[b] of them) were never written
-  int last_msc_n_ = 0, last_chunk_ = 1, msc_deferred_ = 0;
-  bool msc_pending_ = false;
-  std::vector<std::vector<uint8_t>> msc_missing_;
-  std::vector<int> last_keep_;
-  float scan_setup_ms_ = 0;
+  int max_calls_ = 0, nstreams_ = 0;
+  float scan_setup_ms_ = 0, layout_ms_ = 0;
   std::vector<int64_t> eti_base_, eti_count_;
   std::vector<uint32_t> stream_status_;
   int64_t total_eti_ = 0;

@@ -37,6 +37,7 @@
 #include "dab_tables.hpp"
 #include "device_types.hpp"
 #include "kernels.hpp"
+#include "../../include/dabhip.h"
 
 namespace dabhip {
 namespace {
@@ -1083,41 +1084,34 @@ hipError_t launch_fic_group(const uint32_t* fic_rows, int first_block, int nbloc
   return hipGetLastError();
 }
 
-hipError_t launch_viterbi_fused(int soft_bits, const WaveGroup* groups, int ngroups, const int* job_ids, const CodewordPlan* plans,
-                                const uint32_t* grouped, int row_words, uint2* decisions, const uint32_t* prbs_words, uint8_t* out,
-                                int record_stride, hipStream_t stream)
-{
-  if (ngroups <= 0) return hipSuccess;
-  if (soft_bits)
-    hipLaunchKernelGGL(viterbi_fused_kernel<4>, dim3((ngroups + 3) / 4), dim3(256), 0, stream, groups, ngroups, job_ids, plans, grouped, row_words,
-                       decisions, prbs_words, out, record_stride);
-  else
-    hipLaunchKernelGGL(viterbi_fused_kernel<1>, dim3((ngroups + 3) / 4), dim3(256), 0, stream, groups, ngroups, job_ids, plans, grouped, row_words,
-                       decisions, prbs_words, out, record_stride);
-  return hipGetLastError();
-}
+hipError_t launch_viterbi_wave(int soft_bits, const ViterbiLaunch& v, hipStream_t stream);      // k_vitwave.hip
 
-// hard decisions, two lanes per code word (vit_two_lanes.hpp): two waves per group
-hipError_t launch_viterbi_fused_two(const WaveGroup* groups, int ngroups, const int* job_ids, const CodewordPlan* plans, const uint32_t* grouped, int row_words,
-                                    uint2* decisions, const uint32_t* prbs_words, uint8_t* out, int record_stride, hipStream_t stream)
+// lane: one lane per code word; two: two lanes (vit_two_lanes.hpp), two waves per group; two plain / four: 2^NL lanes without per-lane tables
+// (vit_four_lanes.hpp), 2 or 4 waves' worth of lanes per group.  The multi-lane forms take hard decisions only.
+hipError_t launch_viterbi_form(int form, int soft_bits, const ViterbiLaunch& v, hipStream_t stream)
 {
-  if (ngroups <= 0) return hipSuccess;
-  hipLaunchKernelGGL(viterbi_fused_two_kernel, dim3((2 * ngroups + 3) / 4), dim3(256), 0, stream, groups, ngroups, job_ids, plans, grouped, row_words, decisions,
-                     prbs_words, out, record_stride);
-  return hipGetLastError();
-}
-
-// hard decisions, 2^NL lanes per code word without per-lane tables (vit_four_lanes.hpp): lanes = 2 or 4 waves' worth of lanes per group
-hipError_t launch_viterbi_fused_lanes(int lanes, const WaveGroup* groups, int ngroups, const int* job_ids, const CodewordPlan* plans, const uint32_t* grouped,
-                                      int row_words, uint2* decisions, const uint32_t* prbs_words, uint8_t* out, int record_stride, hipStream_t stream)
-{
-  if (ngroups <= 0) return hipSuccess;
-  if (lanes == 4)
-    hipLaunchKernelGGL(viterbi_fused_lanes_kernel<2>, dim3(ngroups), dim3(256), 0, stream, groups, ngroups, job_ids, plans, grouped, row_words, decisions, prbs_words,
-                       out, record_stride);
+  if (v.ngroups <= 0) return hipSuccess;
+  if (form == DABHIP_FORM_WAVE) return launch_viterbi_wave(soft_bits, v, stream);
+  const int ngroups = v.ngroups;
+  if (form == DABHIP_FORM_LANE && soft_bits)
+    hipLaunchKernelGGL(viterbi_fused_kernel<4>, dim3((ngroups + 3) / 4), dim3(256), 0, stream, v.groups, ngroups, v.job_ids, v.plans, v.grouped, v.row_words,
+                       v.decisions, v.prbs_words, v.out, v.record_stride);
+  else if (form == DABHIP_FORM_LANE)
+    hipLaunchKernelGGL(viterbi_fused_kernel<1>, dim3((ngroups + 3) / 4), dim3(256), 0, stream, v.groups, ngroups, v.job_ids, v.plans, v.grouped, v.row_words,
+                       v.decisions, v.prbs_words, v.out, v.record_stride);
+  else if (soft_bits)
+    return hipErrorInvalidValue;
+  else if (form == DABHIP_FORM_TWO)
+    hipLaunchKernelGGL(viterbi_fused_two_kernel, dim3((2 * ngroups + 3) / 4), dim3(256), 0, stream, v.groups, ngroups, v.job_ids, v.plans, v.grouped, v.row_words,
+                       v.decisions, v.prbs_words, v.out, v.record_stride);
+  else if (form == DABHIP_FORM_FOUR)
+    hipLaunchKernelGGL(viterbi_fused_lanes_kernel<2>, dim3(ngroups), dim3(256), 0, stream, v.groups, ngroups, v.job_ids, v.plans, v.grouped, v.row_words, v.decisions,
+                       v.prbs_words, v.out, v.record_stride);
+  else if (form == DABHIP_FORM_TWO_PLAIN)
+    hipLaunchKernelGGL(viterbi_fused_lanes_kernel<1>, dim3((2 * ngroups + 3) / 4), dim3(256), 0, stream, v.groups, ngroups, v.job_ids, v.plans, v.grouped, v.row_words,
+                       v.decisions, v.prbs_words, v.out, v.record_stride);
   else
-    hipLaunchKernelGGL(viterbi_fused_lanes_kernel<1>, dim3((2 * ngroups + 3) / 4), dim3(256), 0, stream, groups, ngroups, job_ids, plans, grouped, row_words, decisions,
-                       prbs_words, out, record_stride);
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

@@ -345,14 +345,13 @@ __global__ __launch_bounds__(kThreads) void demap_kernel(const float2* __restric
 
 }  // namespace
 
-hipError_t launch_ofdm_fft(const uint8_t* const* iq, const CallDesc* descs, int max_calls, const int2* frames, int first,
-                           int nframes, float2* spectra, const float2* tw, hipStream_t stream, float* delta, float delta_c)
+hipError_t launch_ofdm_fft(const FrameListArgs& f, int first, int nframes, float2* spectra, hipStream_t stream, float* delta, float delta_c)
 {
   if (nframes <= 0) return hipSuccess;
   if (delta)
-    hipLaunchKernelGGL(ofdm_fft_kernel<true>, dim3(4 * nframes), dim3(kThreads), 0, stream, iq, descs, max_calls, frames, first, spectra, tw, delta, delta_c);
+    hipLaunchKernelGGL(ofdm_fft_kernel<true>, dim3(4 * nframes), dim3(kThreads), 0, stream, f.iq, f.descs, f.max_calls, f.frames, first, spectra, f.tw, delta, delta_c);
   else
-    hipLaunchKernelGGL(ofdm_fft_kernel<false>, dim3(4 * nframes), dim3(kThreads), 0, stream, iq, descs, max_calls, frames, first, spectra, tw, delta, delta_c);
+    hipLaunchKernelGGL(ofdm_fft_kernel<false>, dim3(4 * nframes), dim3(kThreads), 0, stream, f.iq, f.descs, f.max_calls, f.frames, first, spectra, f.tw, delta, delta_c);
   return hipGetLastError();
 }
 
@@ -375,18 +374,16 @@ hipError_t launch_demap(bool planar, int soft_bits, const float2* spectra, int f
 }
 
 // FIC pre-pass: 4-symbol spectra -> FIC rows only
-hipError_t launch_fic_prepass(int soft_bits, const uint8_t* const* iq, const CallDesc* descs, int max_calls, const int2* frames, int first,
-                              int nframes, float2* spectra4, const float2* tw, const int* frame_slot, const uint16_t* qpsk_of_carrier,
-                              uint32_t* fic_bits, const GuardArgs& guard, hipStream_t stream)
+hipError_t launch_fic_prepass(int soft_bits, const FrameListArgs& f, int first, int nframes, float2* spectra4, const GuardArgs& guard, hipStream_t stream)
 {
   if (nframes <= 0) return hipSuccess;
-  hipLaunchKernelGGL(fic_fft_kernel, dim3(nframes), dim3(kThreads), 0, stream, iq, descs, max_calls, frames, first, spectra4, tw);
+  hipLaunchKernelGGL(fic_fft_kernel, dim3(nframes), dim3(kThreads), 0, stream, f.iq, f.descs, f.max_calls, f.frames, first, spectra4, f.tw);
   if (soft_bits)
-    hipLaunchKernelGGL((demap_kernel<false, 4>), dim3(nframes), dim3(kThreads), 0, stream, spectra4, 4, 3, 1, first, frame_slot, frame_slot,
-                       qpsk_of_carrier, fic_bits, static_cast<uint32_t*>(nullptr), guard);
+    hipLaunchKernelGGL((demap_kernel<false, 4>), dim3(nframes), dim3(kThreads), 0, stream, spectra4, 4, 3, 1, first, f.frame_slot, f.frame_slot,
+                       f.qpsk_of_carrier, f.fic_bits, static_cast<uint32_t*>(nullptr), guard);
   else
-    hipLaunchKernelGGL((demap_kernel<false, 1>), dim3(nframes), dim3(kThreads), 0, stream, spectra4, 4, 3, 1, first, frame_slot, frame_slot,
-                       qpsk_of_carrier, fic_bits, static_cast<uint32_t*>(nullptr), guard);
+    hipLaunchKernelGGL((demap_kernel<false, 1>), dim3(nframes), dim3(kThreads), 0, stream, spectra4, 4, 3, 1, first, f.frame_slot, f.frame_slot,
+                       f.qpsk_of_carrier, f.fic_bits, static_cast<uint32_t*>(nullptr), guard);
   return hipGetLastError();
 }
 

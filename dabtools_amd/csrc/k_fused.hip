@@ -584,57 +584,49 @@ __global__ __launch_bounds__(kThreads, DABHIP_FUSED_WG_PER_CU) void ofdm_demap_k
 }  // namespace
 
 #if DABHIP_FUSED_SOFT
-hipError_t launch_ofdm_demap_fused_soft(bool afc, const uint8_t* const* iq, const CallDesc* descs, int max_calls, const int2* frames, int first, int nframes,
-                                        const float2* tw, const int* frame_slot, const int* frame_cif_row, const uint16_t* qpsk_of_carrier,
-                                        uint32_t* fic_bits, uint32_t* msc_bits, hipStream_t stream, int sym_a, int sym_b, int nparts)
+hipError_t launch_ofdm_demap_fused_soft(bool afc, const FrameListArgs& f, int first, int nframes, hipStream_t stream, int sym_a, int sym_b, int nparts)
 {
   if (nframes <= 0 || nparts <= 0) return hipSuccess;
   const GuardArgs guard{};
   if (afc)
-    hipLaunchKernelGGL(ofdm_demap_kernel<true>, dim3(nparts * nframes), dim3(kThreads), 0, stream, iq, descs, max_calls, frames, first, tw, frame_slot,
-                       frame_cif_row, qpsk_of_carrier, fic_bits, msc_bits, guard, sym_a, sym_b, nparts);
+    hipLaunchKernelGGL(ofdm_demap_kernel<true>, dim3(nparts * nframes), dim3(kThreads), 0, stream, f.iq, f.descs, f.max_calls, f.frames, first, f.tw, f.frame_slot,
+                       f.frame_cif_row, f.qpsk_of_carrier, f.fic_bits, f.msc_bits, guard, sym_a, sym_b, nparts);
   else
-    hipLaunchKernelGGL(ofdm_demap_kernel<false>, dim3(nparts * nframes), dim3(kThreads), 0, stream, iq, descs, max_calls, frames, first, tw, frame_slot,
-                       frame_cif_row, qpsk_of_carrier, fic_bits, msc_bits, guard, sym_a, sym_b, nparts);
+    hipLaunchKernelGGL(ofdm_demap_kernel<false>, dim3(nparts * nframes), dim3(kThreads), 0, stream, f.iq, f.descs, f.max_calls, f.frames, first, f.tw, f.frame_slot,
+                       f.frame_cif_row, f.qpsk_of_carrier, f.fic_bits, f.msc_bits, guard, sym_a, sym_b, nparts);
   return hipGetLastError();
 }
 #elif DABHIP_FUSED_AUDIT
-hipError_t launch_ofdm_demap_fused_audit(const uint8_t* const* iq, const CallDesc* descs, int max_calls, const int2* frames, int first, int nframes,
-                                         const float2* tw, const int* frame_slot, const int* frame_cif_row, const uint16_t* qpsk_of_carrier,
-                                         uint32_t* fic_bits, uint32_t* msc_bits, const GuardArgs& guard, hipStream_t stream, int sym_a, int sym_b, int nparts,
+hipError_t launch_ofdm_demap_fused_audit(const FrameListArgs& f, int first, int nframes, const GuardArgs& guard, hipStream_t stream, int sym_a, int sym_b, int nparts,
                                          float2* dump_bins, float2* dump_prod)
 {
   if (nframes <= 0 || nparts <= 0) return hipSuccess;
   hipError_t e = hipMemcpyToSymbolAsync(HIP_SYMBOL(g_audit_bins), &dump_bins, sizeof dump_bins, 0, hipMemcpyHostToDevice, stream);
   if (e == hipSuccess) e = hipMemcpyToSymbolAsync(HIP_SYMBOL(g_audit_prod), &dump_prod, sizeof dump_prod, 0, hipMemcpyHostToDevice, stream);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(ofdm_demap_kernel<false>, dim3(nparts * nframes), dim3(kThreads), 0, stream, iq, descs, max_calls, frames, first, tw, frame_slot,
-                     frame_cif_row, qpsk_of_carrier, fic_bits, msc_bits, guard, sym_a, sym_b, nparts);
+  hipLaunchKernelGGL(ofdm_demap_kernel<false>, dim3(nparts * nframes), dim3(kThreads), 0, stream, f.iq, f.descs, f.max_calls, f.frames, first, f.tw, f.frame_slot,
+                       f.frame_cif_row, f.qpsk_of_carrier, f.fic_bits, f.msc_bits, guard, sym_a, sym_b, nparts);
   return hipGetLastError();
 }
 #elif DABHIP_FUSED_GUARD
-hipError_t launch_ofdm_demap_fused_guarded(const uint8_t* const* iq, const CallDesc* descs, int max_calls, const int2* frames, int first, int nframes,
-                                           const float2* tw, const int* frame_slot, const int* frame_cif_row, const uint16_t* qpsk_of_carrier,
-                                           uint32_t* fic_bits, uint32_t* msc_bits, const GuardArgs& guard, hipStream_t stream, int sym_a, int sym_b, int nparts)
+hipError_t launch_ofdm_demap_fused_guarded(const FrameListArgs& f, int first, int nframes, const GuardArgs& guard, hipStream_t stream, int sym_a, int sym_b, int nparts)
 {
   if (nframes <= 0 || nparts <= 0) return hipSuccess;
-  hipLaunchKernelGGL(ofdm_demap_kernel<false>, dim3(nparts * nframes), dim3(kThreads), 0, stream, iq, descs, max_calls, frames, first, tw, frame_slot,
-                     frame_cif_row, qpsk_of_carrier, fic_bits, msc_bits, guard, sym_a, sym_b, nparts);
+  hipLaunchKernelGGL(ofdm_demap_kernel<false>, dim3(nparts * nframes), dim3(kThreads), 0, stream, f.iq, f.descs, f.max_calls, f.frames, first, f.tw, f.frame_slot,
+                       f.frame_cif_row, f.qpsk_of_carrier, f.fic_bits, f.msc_bits, guard, sym_a, sym_b, nparts);
   return hipGetLastError();
 }
 #else
-hipError_t launch_ofdm_demap_fused_plain(bool afc, const uint8_t* const* iq, const CallDesc* descs, int max_calls, const int2* frames, int first, int nframes,
-                                         const float2* tw, const int* frame_slot, const int* frame_cif_row, const uint16_t* qpsk_of_carrier,
-                                         uint32_t* fic_bits, uint32_t* msc_bits, hipStream_t stream, int sym_a, int sym_b, int nparts)
+hipError_t launch_ofdm_demap_fused_plain(bool afc, const FrameListArgs& f, int first, int nframes, hipStream_t stream, int sym_a, int sym_b, int nparts)
 {
   if (nframes <= 0 || nparts <= 0) return hipSuccess;
   const GuardArgs guard{};
   if (afc)
-    hipLaunchKernelGGL(ofdm_demap_kernel<true>, dim3(nparts * nframes), dim3(kThreads), 0, stream, iq, descs, max_calls, frames, first, tw, frame_slot,
-                       frame_cif_row, qpsk_of_carrier, fic_bits, msc_bits, guard, sym_a, sym_b, nparts);
+    hipLaunchKernelGGL(ofdm_demap_kernel<true>, dim3(nparts * nframes), dim3(kThreads), 0, stream, f.iq, f.descs, f.max_calls, f.frames, first, f.tw, f.frame_slot,
+                       f.frame_cif_row, f.qpsk_of_carrier, f.fic_bits, f.msc_bits, guard, sym_a, sym_b, nparts);
   else
-    hipLaunchKernelGGL(ofdm_demap_kernel<false>, dim3(nparts * nframes), dim3(kThreads), 0, stream, iq, descs, max_calls, frames, first, tw, frame_slot,
-                       frame_cif_row, qpsk_of_carrier, fic_bits, msc_bits, guard, sym_a, sym_b, nparts);
+    hipLaunchKernelGGL(ofdm_demap_kernel<false>, dim3(nparts * nframes), dim3(kThreads), 0, stream, f.iq, f.descs, f.max_calls, f.frames, first, f.tw, f.frame_slot,
+                       f.frame_cif_row, f.qpsk_of_carrier, f.fic_bits, f.msc_bits, guard, sym_a, sym_b, nparts);
   return hipGetLastError();
 }
 #endif

@@ -477,29 +477,24 @@ __global__ __launch_bounds__(kFft64Threads) void decision_audit_kernel(const uin
 
 }  // namespace
 
-hipError_t launch_symbol_delta(const uint8_t* const* iq, const CallDesc* descs, int max_calls, const int2* frames, int first, int nframes,
-                               int nsym, float* delta, int delta_stride, float delta_c, hipStream_t stream)
+hipError_t launch_symbol_delta(const FrameListArgs& f, int first, int nframes, int nsym, float* delta, int delta_stride, float delta_c, hipStream_t stream)
 {
   if (nframes <= 0) return hipSuccess;
-  hipLaunchKernelGGL(symbol_delta_kernel, dim3((nframes * nsym + 3) / 4), dim3(256), 0, stream, iq, descs, max_calls, frames, first, nframes,
+  hipLaunchKernelGGL(symbol_delta_kernel, dim3((nframes * nsym + 3) / 4), dim3(256), 0, stream, f.iq, f.descs, f.max_calls, f.frames, first, nframes,
                      nsym, delta, delta_stride, delta_c);
   return hipGetLastError();
 }
 
-hipError_t launch_exact_decide(const uint4* list, const unsigned* counter, unsigned cap, const uint8_t* const* iq, const CallDesc* descs,
-                               int max_calls, const int2* frames, const double2* tw2048, const uint16_t* qpsk_of_carrier, const uint16_t* /*carrier_of_qpsk*/,
-                               const int* frame_slot, const int* frame_cif_row, bool planar, uint32_t* fic_bits, uint32_t* msc_bits, hipStream_t stream)
+hipError_t launch_exact_decide(const uint4* list, const unsigned* counter, unsigned cap, const FrameListArgs& f, const double2* tw2048, bool planar, hipStream_t stream)
 {
   static const int samplewise = std::getenv("DABHIP_EXACT_SAMPLEWISE") ? std::atoi(std::getenv("DABHIP_EXACT_SAMPLEWISE")) : 0;
-  hipLaunchKernelGGL(exact_decide_kernel, dim3(2048), dim3(256), 0, stream, list, counter, cap, iq, descs, max_calls, frames, tw2048,
-                     qpsk_of_carrier, frame_slot, frame_cif_row, planar ? 1 : 0, fic_bits, msc_bits, samplewise);
+  hipLaunchKernelGGL(exact_decide_kernel, dim3(2048), dim3(256), 0, stream, list, counter, cap, f.iq, f.descs, f.max_calls, f.frames, tw2048,
+                     f.qpsk_of_carrier, f.frame_slot, f.frame_cif_row, planar ? 1 : 0, f.fic_bits, f.msc_bits, samplewise);
   return hipGetLastError();
 }
 
-hipError_t launch_exact_decide_all(const unsigned* counter, unsigned cap, const uint8_t* const* iq, const CallDesc* descs, int max_calls, const int2* frames,
-                                   int first, int nframes, int sym_a, int sym_b, const double2* tw2048, const uint16_t* qpsk_of_carrier,
-                                   const int* frame_slot, const int* frame_cif_row, bool planar, bool skip_fic, uint32_t* fic_bits, uint32_t* msc_bits,
-                                   hipStream_t stream)
+hipError_t launch_exact_decide_all(const unsigned* counter, unsigned cap, const FrameListArgs& f, int first, int nframes, int sym_a, int sym_b, const double2* tw2048,
+                                   bool planar, bool skip_fic, hipStream_t stream)
 {
   if (nframes <= 0) return hipSuccess;
   static std::once_flag once[64];
@@ -509,8 +504,8 @@ hipError_t launch_exact_decide_all(const unsigned* counter, unsigned cap, const 
     return hipFuncSetAttribute(reinterpret_cast<const void*>(exact_decide_all_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
   });
   if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL(exact_decide_all_kernel, dim3(std::min(nframes, 512)), dim3(kFft64Threads), lds, stream, counter, cap, iq, descs, max_calls, frames, first,
-                     nframes, sym_a, sym_b, tw2048, qpsk_of_carrier, frame_slot, frame_cif_row, planar ? 1 : 0, skip_fic ? 1 : 0, fic_bits, msc_bits);
+  hipLaunchKernelGGL(exact_decide_all_kernel, dim3(std::min(nframes, 512)), dim3(kFft64Threads), lds, stream, counter, cap, f.iq, f.descs, f.max_calls, f.frames, first,
+                     nframes, sym_a, sym_b, tw2048, f.qpsk_of_carrier, f.frame_slot, f.frame_cif_row, planar ? 1 : 0, skip_fic ? 1 : 0, f.fic_bits, f.msc_bits);
   return hipGetLastError();
 }
 

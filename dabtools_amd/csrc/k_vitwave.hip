@@ -301,16 +301,17 @@ __global__ __launch_bounds__(256) void viterbi_wave_kernel(const WaveGroup* __re
 }  // namespace
 
 // every (group, valid lane) becomes one wave; decisions: rows of 64 x 8 bytes, group g's at groups[g].dec_base, 64 x ceil(nsteps / 60) of them
-hipError_t launch_viterbi_wave(int soft_bits, const WaveGroup* groups, int ngroups, const int* job_ids, const CodewordPlan* plans,
-                               const uint32_t* grouped, int row_words, uint2* decisions, const uint32_t* prbs_words, uint8_t* out, int record_stride,
-                               hipStream_t stream)
+// (reached through launch_viterbi_form, k_decode.hip)
+hipError_t launch_viterbi_wave(int soft_bits, const ViterbiLaunch& v, hipStream_t stream)
 {
-  if (ngroups <= 0) return hipSuccess;
-  const dim3 grid(static_cast<unsigned>(ngroups) * 16u), block(256);
+  if (v.ngroups <= 0) return hipSuccess;
+  const dim3 grid(static_cast<unsigned>(v.ngroups) * 16u), block(256);
   if (soft_bits)
-    hipLaunchKernelGGL(viterbi_wave_kernel<4>, grid, block, 0, stream, groups, ngroups, job_ids, plans, grouped, row_words, decisions, prbs_words, out, record_stride);
+    hipLaunchKernelGGL(viterbi_wave_kernel<4>, grid, block, 0, stream, v.groups, v.ngroups, v.job_ids, v.plans, v.grouped, v.row_words, v.decisions, v.prbs_words, v.out,
+                       v.record_stride);
   else
-    hipLaunchKernelGGL(viterbi_wave_kernel<1>, grid, block, 0, stream, groups, ngroups, job_ids, plans, grouped, row_words, decisions, prbs_words, out, record_stride);
+    hipLaunchKernelGGL(viterbi_wave_kernel<1>, grid, block, 0, stream, v.groups, v.ngroups, v.job_ids, v.plans, v.grouped, v.row_words, v.decisions, v.prbs_words, v.out,
+                       v.record_stride);
   return hipGetLastError();
 }
 

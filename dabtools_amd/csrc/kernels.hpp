@@ -53,6 +53,7 @@ struct HostWordsArgs {
   uint32_t nwords[4];
   uint32_t* zero;
   uint32_t nzero;
+  void set(int k, const void* from, void* to, size_t n) { src[k] = static_cast<const uint32_t*>(from); dst[k] = static_cast<uint32_t*>(to); nwords[k] = static_cast<uint32_t>(n); }
 };
 hipError_t launch_host_words(const HostWordsArgs& a, hipStream_t stream);
 // K1: synchronisation scan, one workgroup per stream, calls [call_begin, call_end) (call_end < 0: all).
@@ -93,10 +94,17 @@ hipError_t launch_sync_ahead(const uint8_t* const* iq, const int64_t* nbytes, co
 hipError_t launch_sync_verify(const uint8_t* const* iq, const int64_t* nbytes, const int* calls_before, StreamState* states, CallDesc* descs,
                               int nstreams, int max_calls, const double2* tw2048, const uint8_t* prs_q, int* violation, bool carry_only, hipStream_t stream);
 
+// What every launch over the frame list shares: the streams' samples, the calls' descriptors (descs[stream * max_calls + call]), the list itself
+// (frames[i] = {stream, call}, FIC rows at TF slot frame_slot[i], MSC rows from logical CIF row frame_cif_row[i]), the fp32 twiddles, the
+// carrier -> QPSK symbol map and the bit rows.  Such a launch covers frames [first, first + nframes) of the list.
+struct FrameListArgs {
+  const uint8_t* const* iq; const CallDesc* descs; int max_calls; const int2* frames; const float2* tw;
+  const int *frame_slot, *frame_cif_row; const uint16_t* qpsk_of_carrier; uint32_t *fic_bits, *msc_bits;
+};
+
 // delta != nullptr: the kernel also leaves the guard's per-symbol error bound delta_c sqrt(sum |x|^2) at delta[(first + j) * 76 + symbol]
 // (delta_c = GuardArgs::c of the launches that will read it: the guard level's constant, or kSoftNormC for soft decisions)
-hipError_t launch_ofdm_fft(const uint8_t* const* iq, const CallDesc* descs, int max_calls, const int2* frames, int first,
-                           int nframes, float2* spectra, const float2* tw, hipStream_t stream, float* delta = nullptr, float delta_c = kGuardC);
+hipError_t launch_ofdm_fft(const FrameListArgs& f, int first, int nframes, float2* spectra, hipStream_t stream, float* delta = nullptr, float delta_c = kGuardC);
 
 // K2b: DQPSK + demap + frequency de-interleave -> bit-packed rows.  FIC rows at TF slot frame_slot[first + j];
 // MSC rows start at CIF row frame_cif_row[first + j]: planar = scattered into time-de-interleaved logical rows
@@ -106,9 +114,7 @@ hipError_t launch_demap(bool planar, int soft_bits, const float2* spectra, int f
                         const GuardArgs& guard, hipStream_t stream);
 
 // FIC pre-pass: DFT of symbols 0..3 of every frame + demap of the three FIC symbols (spectra4: [nframes][4][2048])
-hipError_t launch_fic_prepass(int soft_bits, const uint8_t* const* iq, const CallDesc* descs, int max_calls, const int2* frames, int first,
-                              int nframes, float2* spectra4, const float2* tw, const int* frame_slot, const uint16_t* qpsk_of_carrier,
-                              uint32_t* fic_bits, const GuardArgs& guard, hipStream_t stream);
+hipError_t launch_fic_prepass(int soft_bits, const FrameListArgs& f, int first, int nframes, float2* spectra4, const GuardArgs& guard, hipStream_t stream);
 
 // S1 seam: Viterbi on explicit per-step symbol bytes (forward pass + chain-back + pack)
 hipError_t launch_viterbi(const WaveGroup* groups, int ngroups, const int* job_ids, const CodewordPlan* plans, const uint4* steps,
@@ -119,52 +125,38 @@ hipError_t launch_viterbi(const WaveGroup* groups, int ngroups, const int* job_i
 hipError_t launch_regroup(int soft_bits, const int* job_ids, int ntiles, const DecodeJob* jobs, const int* stream_cif_base,
                           const uint32_t* rows, uint32_t* grouped, hipStream_t stream);
 hipError_t launch_fic_group(const uint32_t* fic_rows, int first_block, int nblocks, int block_words, uint32_t* grouped, hipStream_t stream);
-hipError_t launch_viterbi_fused(int soft_bits, const WaveGroup* groups, int ngroups, const int* job_ids, const CodewordPlan* plans,
-                                const uint32_t* grouped, int row_words, uint2* decisions, const uint32_t* prbs_words, uint8_t* out,
-                                int record_stride, hipStream_t stream);
-hipError_t launch_viterbi_fused_lanes(int lanes, const WaveGroup* groups, int ngroups, const int* job_ids, const CodewordPlan* plans, const uint32_t* grouped,
-                                      int row_words, uint2* decisions, const uint32_t* prbs_words, uint8_t* out, int record_stride, hipStream_t stream);
-hipError_t launch_viterbi_fused_two(const WaveGroup* groups, int ngroups, const int* job_ids, const CodewordPlan* plans, const uint32_t* grouped, int row_words,
-                                    uint2* decisions, const uint32_t* prbs_words, uint8_t* out, int record_stride, hipStream_t stream);
+// One launch of the decoder over ngroups wave-groups (worklist.hpp), whatever its form: rows of row_words words per record in `grouped`, survivor
+// records in `decisions`, decoded bytes de-scrambled with prbs_words into out + record * record_stride.
+struct ViterbiLaunch {
+  const WaveGroup* groups; int ngroups; const int* job_ids; const CodewordPlan* plans; const uint32_t* grouped; int row_words;
+  uint2* decisions; const uint32_t* prbs_words; uint8_t* out; int record_stride;
+};
+// form: DABHIP_FORM_WAVE / LANE (hard and soft decisions) / TWO / TWO_PLAIN / FOUR (hard only: hipErrorInvalidValue with soft_bits); decoder_form.hpp has the rule
+hipError_t launch_viterbi_form(int form, int soft_bits, const ViterbiLaunch& v, hipStream_t stream);
 
 // The low-latency form of the same decoder (k_vitwave.hip): one WAVE per code word, lane = trellis state -- a fraction of the fused kernel's
 // time per code word at four times its lane-ops, for small batches.  Same groups / plans / rows / output; decisions: rows of 64 x 8 bytes, one per
 // code word and chunk of kWaveChunk steps: group g's 64 x ceil(nsteps / kWaveChunk) rows start at groups[g].dec_base.
 constexpr int kWaveChunk = 60;
-hipError_t launch_viterbi_wave(int soft_bits, const WaveGroup* groups, int ngroups, const int* job_ids, const CodewordPlan* plans,
-                               const uint32_t* grouped, int row_words, uint2* decisions, const uint32_t* prbs_words, uint8_t* out, int record_stride,
-                               hipStream_t stream);
 
 // the one-kernel OFDM stage (k_fused.hip, compiled three times): with the parity guard's test in its symbol loop, without it, and
 // with 4-bit soft values instead of hard decisions.
 // Data symbols [sym_a, sym_b) of every frame (1..3 = FIC, 4..75 = MSC), nparts workgroups per frame; each transforms the symbol before
 // its first data symbol as differential reference.
-hipError_t launch_ofdm_demap_fused_guarded(const uint8_t* const* iq, const CallDesc* descs, int max_calls, const int2* frames, int first, int nframes,
-                                           const float2* tw, const int* frame_slot, const int* frame_cif_row, const uint16_t* qpsk_of_carrier,
-                                           uint32_t* fic_bits, uint32_t* msc_bits, const GuardArgs& guard, hipStream_t stream, int sym_a = 1, int sym_b = 76, int nparts = 4);
+hipError_t launch_ofdm_demap_fused_guarded(const FrameListArgs& f, int first, int nframes, const GuardArgs& guard, hipStream_t stream, int sym_a = 1, int sym_b = 76,
+                                           int nparts = 4);
 // the guarded kernel's audit build (k_fused.hip with -DDABHIP_FUSED_AUDIT=1): also leaves dump_bins[frame][76][2048] (by raw bin) and
 // dump_prod[frame][76][2048] ((re, im) of cur conj(prev) of the data symbols as the kernel computed them)
-hipError_t launch_ofdm_demap_fused_audit(const uint8_t* const* iq, const CallDesc* descs, int max_calls, const int2* frames, int first, int nframes,
-                                         const float2* tw, const int* frame_slot, const int* frame_cif_row, const uint16_t* qpsk_of_carrier,
-                                         uint32_t* fic_bits, uint32_t* msc_bits, const GuardArgs& guard, hipStream_t stream, int sym_a, int sym_b, int nparts,
+hipError_t launch_ofdm_demap_fused_audit(const FrameListArgs& f, int first, int nframes, const GuardArgs& guard, hipStream_t stream, int sym_a, int sym_b, int nparts,
                                          float2* dump_bins, float2* dump_prod);
-hipError_t launch_ofdm_demap_fused_soft(bool afc, const uint8_t* const* iq, const CallDesc* descs, int max_calls, const int2* frames, int first, int nframes,
-                                        const float2* tw, const int* frame_slot, const int* frame_cif_row, const uint16_t* qpsk_of_carrier,
-                                        uint32_t* fic_bits, uint32_t* msc_bits, hipStream_t stream, int sym_a = 1, int sym_b = 76, int nparts = 4);
-hipError_t launch_ofdm_demap_fused_plain(bool afc, const uint8_t* const* iq, const CallDesc* descs, int max_calls, const int2* frames, int first, int nframes,
-                                         const float2* tw, const int* frame_slot, const int* frame_cif_row, const uint16_t* qpsk_of_carrier,
-                                         uint32_t* fic_bits, uint32_t* msc_bits, hipStream_t stream, int sym_a = 1, int sym_b = 76, int nparts = 4);
+hipError_t launch_ofdm_demap_fused_soft(bool afc, const FrameListArgs& f, int first, int nframes, hipStream_t stream, int sym_a = 1, int sym_b = 76, int nparts = 4);
+hipError_t launch_ofdm_demap_fused_plain(bool afc, const FrameListArgs& f, int first, int nframes, hipStream_t stream, int sym_a = 1, int sym_b = 76, int nparts = 4);
 // parity guard (k_parity.hip): per-symbol error bounds, fp64 re-decision of the flagged carriers, and the audit
-hipError_t launch_symbol_delta(const uint8_t* const* iq, const CallDesc* descs, int max_calls, const int2* frames, int first, int nframes,
-                               int nsym, float* delta, int delta_stride, float delta_c, hipStream_t stream);
-hipError_t launch_exact_decide(const uint4* list, const unsigned* counter, unsigned cap, const uint8_t* const* iq, const CallDesc* descs,
-                               int max_calls, const int2* frames, const double2* tw2048, const uint16_t* qpsk_of_carrier, const uint16_t* carrier_of_qpsk,
-                               const int* frame_slot, const int* frame_cif_row, bool planar, uint32_t* fic_bits, uint32_t* msc_bits, hipStream_t stream);
+hipError_t launch_symbol_delta(const FrameListArgs& f, int first, int nframes, int nsym, float* delta, int delta_stride, float delta_c, hipStream_t stream);
+hipError_t launch_exact_decide(const uint4* list, const unsigned* counter, unsigned cap, const FrameListArgs& f, const double2* tw2048, bool planar, hipStream_t stream);
 // list overflow of a guarded launch: its frames' symbols [sym_a, sym_b) decided again in full from fp64 transforms (returns at once otherwise)
-hipError_t launch_exact_decide_all(const unsigned* counter, unsigned cap, const uint8_t* const* iq, const CallDesc* descs, int max_calls, const int2* frames,
-                                   int first, int nframes, int sym_a, int sym_b, const double2* tw2048, const uint16_t* qpsk_of_carrier,
-                                   const int* frame_slot, const int* frame_cif_row, bool planar, bool skip_fic, uint32_t* fic_bits, uint32_t* msc_bits,
-                                   hipStream_t stream);
+hipError_t launch_exact_decide_all(const unsigned* counter, unsigned cap, const FrameListArgs& f, int first, int nframes, int sym_a, int sym_b, const double2* tw2048,
+                                   bool planar, bool skip_fic, hipStream_t stream);
 hipError_t launch_decision_audit(const uint8_t* frames_iq, int nframes, const float2* spectra, const uint32_t* fic_bits, const uint32_t* msc_bits,
                                  const double2* tw2048, const uint16_t* qpsk_of_carrier, void* out, hipStream_t stream,
                                  const float2* fused_prods = nullptr, int row_lead = 0, int guard_level = 1);   // fused_prods != null: the fused kernel's audit (spectra = its bins by raw bin)

@@ -5,6 +5,9 @@
 //                      uses them: a lane task that calls parallel_for while the posting thread waits; several engines' worth at once
 //   control_plane.hpp  FIG parse, lock rule, CIF ring, ETI headers over the FIBs of synthetic ensembles, streams in parallel
 //   worklist.hpp       frame records, header rows, wave-groups and slices of the MSC decode (with plain std::allocator lists)
+//   segment_layout.hpp the frame list, TF slots and logical CIF rows of random segments (with and without the lock-in skip, mis-numbered
+//                      ordinals under ASan) and the session carry over runs of segments, against a per-TF list kept here
+//   decoder_form.hpp   the decoder-form rule at both sides of every documented crossover, each knob's 0 / 1 / N reading, every forced form
 //   fifo_view.hpp      the closed-form FIFO / stale-tail views under random timing corrections, against a byte-level replay of
 //                      cbWrite / sdr_read_fifo's copying rule (sdr_fifo.c:26-61)
 //   synth.cpp          the modulator's bit content and sample generation (bounds, UB)
@@ -16,12 +19,16 @@
 #include <cstring>
 #include <memory>
 #include <random>
+#include <set>
+#include <tuple>
 #include <thread>
 #include <vector>
 
 #include "../../include/dabhip.h"
 #include "../../dabtools_amd/csrc/control_plane.hpp"
+#include "../../dabtools_amd/csrc/decoder_form.hpp"
 #include "../../dabtools_amd/csrc/fifo_view.hpp"
+#include "../../dabtools_amd/csrc/segment_layout.hpp"
 #include "../../dabtools_amd/csrc/thread_pool.hpp"
 #include "../../dabtools_amd/csrc/worklist.hpp"
 
@@ -247,6 +254,205 @@ static void test_control_and_worklist()
   for (auto& l : lanes) l->wait();
 }
 
+// one random segment: the scan's records as K1 writes them ({status, ordinal}; a stream's demodulated TFs numbered densely from ord_done on)
+struct RandomSegment {
+  int nstreams, max_calls;
+  std::vector<IntPair> info;
+  std::vector<int> ncalls, nnew, defer;
+  std::vector<StreamCarry> carry;
+};
+static RandomSegment random_segment(std::mt19937& rng)
+{
+  RandomSegment r;
+  r.nstreams = 1 + static_cast<int>(rng() % 64);
+  r.max_calls = 1 + static_cast<int>(rng() % 12);
+  r.info.assign(static_cast<size_t>(r.nstreams) * r.max_calls, IntPair{0, -1});
+  r.ncalls.resize(r.nstreams);
+  r.nnew.assign(r.nstreams, 0);
+  r.defer.resize(r.nstreams);
+  r.carry.resize(r.nstreams);
+  for (int b = 0; b < r.nstreams; ++b) {
+    StreamCarry& c = r.carry[b];
+    c.keep = static_cast<int>(rng() % 5);
+    c.ord_done = static_cast<int>(rng() % 1000);
+    r.ncalls[b] = static_cast<int>(rng() % (r.max_calls + 1));
+    for (int k = 0; k < r.ncalls[b]; ++k) {
+      const int status = static_cast<int>(rng() % 3);
+      r.info[static_cast<size_t>(b) * r.max_calls + k] = IntPair{status, status == 2 ? c.ord_done + r.nnew[b]++ : -1};
+    }
+    r.defer[b] = static_cast<int>(rng() % (r.nnew[b] + 1));
+  }
+  return r;
+}
+
+static void test_layout()
+{
+  std::mt19937 rng(11);
+  using Frame = std::tuple<int, int, int, int>;            // stream, call, slot, row
+  for (int trial = 0; trial < 400; ++trial) {
+    const RandomSegment r = random_segment(rng);
+    const size_t nd = static_cast<size_t>(r.nstreams) * r.max_calls;
+    const std::vector<int> no_defer(r.nstreams, 0);
+    std::multiset<Frame> with_skip, without_skip;
+    for (int pass = 0; pass < 2; ++pass) {                 // 0: the lock-in skip as drawn, 1: every deferred count 0
+      SegmentLayout L;
+      std::vector<IntPair> frames(nd, IntPair{-1, -1});    // exactly the engine's sizes: ASan sees a write beyond them
+      std::vector<int> slot(nd, -1), row(nd, -1);
+      std::string error;
+      CHECK(layout_segment(r.info.data(), r.max_calls, r.ncalls.data(), r.carry, pass ? no_defer.data() : r.defer.data(), L, frames.data(), slot.data(), row.data(), &error));
+      int ntf = 0, ndefer = 0;
+      for (int b = 0; b < r.nstreams; ++b) {
+        CHECK(L.nnew[b] == r.nnew[b] && L.ndefer_of[b] == (pass ? 0 : r.defer[b]));
+        ntf += r.nnew[b];
+        ndefer += L.ndefer_of[b];
+        CHECK(L.tf_base[b + 1] == L.tf_base[b] + r.carry[b].keep + r.nnew[b] && L.fib_base[b] == 4 * L.tf_base[b]);
+        if (b + 1 < r.nstreams) CHECK(L.row_base[b + 1] - L.row_base[b] == kRowLead + 4 * (r.carry[b].keep + r.nnew[b]));
+      }
+      CHECK(L.tf_base[0] == 0 && L.row_base[0] == kRowLead && L.ntf == ntf && L.nmsc == ntf - ndefer);
+      CHECK(L.next_row == L.row_base[r.nstreams - 1] - kRowLead + kRowLead + 4 * (r.carry[r.nstreams - 1].keep + r.nnew[r.nstreams - 1]));
+      // every list index in [0, ntf) written, nothing behind it, every demodulated call of every stream there once
+      std::set<std::pair<int, int>> calls;
+      std::vector<std::vector<std::pair<int, int>>> of_stream(r.nstreams);   // (call, list index)
+      for (size_t i = 0; i < nd; ++i) {
+        if (i >= static_cast<size_t>(ntf)) { CHECK(frames[i].x == -1 && slot[i] == -1 && row[i] == -1); continue; }
+        const int b = frames[i].x, k = frames[i].y;
+        CHECK(b >= 0 && b < r.nstreams && k >= 0 && k < r.ncalls[b] && r.info[static_cast<size_t>(b) * r.max_calls + k].x == 2);
+        CHECK(calls.insert({b, k}).second);
+        of_stream[b].push_back({k, static_cast<int>(i)});
+        (pass ? without_skip : with_skip).insert(Frame{b, k, slot[i], row[i]});
+      }
+      CHECK(static_cast<int>(calls.size()) == ntf);
+      for (int b = 0; b < r.nstreams; ++b) {
+        std::sort(of_stream[b].begin(), of_stream[b].end());
+        CHECK(static_cast<int>(of_stream[b].size()) == r.nnew[b]);
+        for (int i = 0; i < r.nnew[b]; ++i) {
+          const int at = of_stream[b][i].second, local = r.carry[b].keep + i;
+          CHECK(slot[at] == L.tf_base[b] + local && row[at] == L.row_base[b] + 4 * local);      // contiguous from tf_base[b] + keep, in call order
+          CHECK((at >= L.nmsc) == (i < L.ndefer_of[b]));                                        // the deferred ones: the stream's first new TFs, behind nmsc
+        }
+      }
+    }
+    CHECK(with_skip == without_skip);                      // the skip only re-orders the list
+    // mis-numbered ordinals (one of them off by one, either way): refused with the error text, nothing written out of bounds
+    std::vector<size_t> demodulated;
+    for (size_t i = 0; i < nd; ++i)
+      if (r.info[i].x == 2) demodulated.push_back(i);
+    if (!demodulated.empty()) {
+      std::vector<IntPair> bad = r.info;
+      bad[demodulated[rng() % demodulated.size()]].y += (rng() & 1) ? 1 : -1;
+      SegmentLayout L;
+      std::vector<IntPair> frames(nd);
+      std::vector<int> slot(nd), row(nd);
+      std::string error;
+      CHECK(!layout_segment(bad.data(), r.max_calls, r.ncalls.data(), r.carry, r.defer.data(), L, frames.data(), slot.data(), row.data(), &error));
+      CHECK(error == "decode: the calls' ordinals do not number this segment's transmission frames");
+    }
+  }
+}
+
+// a session: StreamCarry::advance over a random run of segments against one flag per TF of the whole session, kept here
+static void test_carry()
+{
+  std::mt19937 rng(13);
+  for (int trial = 0; trial < 60; ++trial) {
+    const int nstreams = 1 + static_cast<int>(rng() % 8), max_calls = 9;
+    std::vector<StreamCarry> carry(nstreams);
+    for (StreamCarry& c : carry) {
+      c.keep = 3;                                          // (stale values: reset() is what a fresh decode starts from)
+      c.msc_missing.assign(5, 1);
+      c.reset();
+      CHECK(c.keep == 0 && c.prev_used == 0 && c.calls_done == 0 && c.ord_done == 0 && c.last_keep == 0 && c.msc_missing.empty());
+    }
+    std::vector<std::vector<uint8_t>> missing(nstreams);   // per stream: TF i of the session had its MSC part deferred
+    for (int segment = 0; segment < 40; ++segment) {
+      std::vector<IntPair> info(static_cast<size_t>(nstreams) * max_calls, IntPair{0, -1});
+      std::vector<int> ncalls(nstreams), defer(nstreams), nnew(nstreams, 0), keep_before(nstreams);
+      for (int b = 0; b < nstreams; ++b) {
+        ncalls[b] = static_cast<int>(rng() % (max_calls + 1));
+        for (int k = 0; k < ncalls[b]; ++k)
+          if (rng() % 3) info[static_cast<size_t>(b) * max_calls + k] = IntPair{2, static_cast<int>(missing[b].size()) + nnew[b]++};
+        defer[b] = (rng() % 4 == 0) ? static_cast<int>(rng() % (nnew[b] + 1)) : 0;
+        keep_before[b] = carry[b].keep;
+      }
+      SegmentLayout L;
+      std::vector<IntPair> frames(info.size());
+      std::vector<int> slot(info.size()), row(info.size());
+      std::string error;
+      CHECK(layout_segment(info.data(), max_calls, ncalls.data(), carry, defer.data(), L, frames.data(), slot.data(), row.data(), &error));
+      for (int b = 0; b < nstreams; ++b) {
+        carry[b].advance(L, b);
+        for (int i = 0; i < nnew[b]; ++i) missing[b].push_back(i < defer[b] ? 1 : 0);
+        const StreamCarry& c = carry[b];
+        const int total = static_cast<int>(missing[b].size());
+        CHECK(c.last_keep == keep_before[b] && c.prev_used == keep_before[b] + nnew[b] && c.keep == std::min(4, c.prev_used) && c.ord_done == total);
+        CHECK(c.prev_tf_base == L.tf_base[b] && c.prev_row_base == L.row_base[b]);
+        // the flags follow a TF from "deferred in this segment" to "carried slot of the next" to gone: slot j of the layout is TF total - prev_used + j
+        CHECK(static_cast<int>(c.msc_missing.size()) == c.prev_used);
+        for (int j = 0; j < c.prev_used; ++j) CHECK(c.msc_missing[j] == missing[b][static_cast<size_t>(total - c.prev_used + j)]);
+      }
+    }
+  }
+}
+
+// The decoder-form rule: the expected forms are the rule as engine.cpp spelled it out before it moved to decoder_form.hpp (launch_decode_batch,
+// fic_decode_slots_async, msc_prepare), at the documented crossovers (include/dabhip.h)
+static void test_forms()
+{
+  const int AUTO = DABHIP_FORM_AUTO, WAVE = DABHIP_FORM_WAVE, LANE = DABHIP_FORM_LANE, TWO = DABHIP_FORM_TWO, PLAIN = DABHIP_FORM_TWO_PLAIN, FOUR = DABHIP_FORM_FOUR;
+  const FormKnobs def;
+  CHECK(def.wave_max_codewords == 12288 && def.wave_max_fic_blocks == 3072 && def.two_lanes_max_groups == 1536 && def.four_lanes_max_groups == 800 &&
+        !def.two_lanes_plain && def.fic_four_lanes_max_tiles == 128);
+  // MSC, defaults: a batch in the wave form runs it whatever else holds; then four lanes up to 800 groups, two up to 1,536, one above
+  struct { int forced; bool soft, wave_batch; int ngroups, want; } msc[] = {
+      {AUTO, false, true, 10, WAVE},  {AUTO, true, true, 10, WAVE},    {FOUR, false, true, 10, WAVE},   {AUTO, false, false, 1, FOUR},
+      {AUTO, false, false, 800, FOUR}, {AUTO, false, false, 801, TWO}, {AUTO, false, false, 1536, TWO}, {AUTO, false, false, 1537, LANE},
+      {AUTO, false, false, 100000, LANE},
+      // soft decisions: the lane form whatever the size and whatever is forced (the wave form apart: that is the batch's)
+      {AUTO, true, false, 1, LANE},   {AUTO, true, false, 801, LANE},  {TWO, true, false, 5, LANE},     {PLAIN, true, false, 5, LANE},
+      {FOUR, true, false, 5, LANE},   {LANE, true, false, 5, LANE},    {WAVE, true, false, 5, LANE},
+      // forced forms, hard decisions, at sizes where the rule would say otherwise (WAVE forced on a batch that is not in the wave form: lanes)
+      {LANE, false, false, 5, LANE},  {TWO, false, false, 5, TWO},     {TWO, false, false, 5000, TWO},  {PLAIN, false, false, 5, PLAIN},
+      {PLAIN, false, false, 5000, PLAIN}, {FOUR, false, false, 5000, FOUR}, {WAVE, false, false, 5, LANE}};
+  for (const auto& t : msc) CHECK(msc_form(def, t.forced, t.soft, t.wave_batch, t.ngroups) == t.want);
+  // each knob's 0 / 1 / N reading
+  struct { int two, four; bool plain; int ngroups, want; } knobs[] = {
+      {0, 0, false, 1, LANE},     {0, 0, true, 1, LANE},      {1, 0, false, 100000, TWO}, {1, 0, true, 100000, PLAIN}, {0, 1, false, 100000, FOUR},
+      {1, 1, false, 100000, FOUR}, {40, 0, false, 40, TWO},   {40, 0, false, 41, LANE},   {40, 20, false, 20, FOUR},   {40, 20, false, 21, TWO},
+      {40, 20, true, 21, PLAIN},  {40, 20, true, 20, FOUR},   {20, 40, false, 30, FOUR},  {20, 40, false, 41, LANE},   {1536, 800, true, 801, PLAIN}};
+  for (const auto& t : knobs) {
+    FormKnobs k;
+    k.two_lanes_max_groups = t.two;
+    k.four_lanes_max_groups = t.four;
+    k.two_lanes_plain = t.plain;
+    CHECK(msc_form(k, AUTO, false, false, t.ngroups) == t.want);
+    CHECK(msc_form(k, AUTO, true, false, t.ngroups) == LANE);
+  }
+  // the work-list build's bound: the knob, or all / nothing under a forced form
+  CHECK(msc_wave_max(def, AUTO) == 12288 && msc_wave_max(def, WAVE) == INT64_MAX);
+  for (int f : {LANE, TWO, PLAIN, FOUR}) CHECK(msc_wave_max(def, f) == 0);
+  // FIC, defaults: the wave form up to 3,072 blocks (hard and soft), four lanes per block up to 128 tiles (hard only), one lane above
+  struct { int forced; bool soft; int nblocks, ntiles, want; } fic[] = {
+      {AUTO, false, 4, 1, WAVE},       {AUTO, false, 3072, 48, WAVE},   {AUTO, true, 3072, 48, WAVE},    {AUTO, false, 3073, 49, FOUR},
+      {AUTO, false, 3076, 49, FOUR},   {AUTO, false, 8192, 128, FOUR},  {AUTO, false, 8196, 129, LANE},  {AUTO, true, 3076, 49, LANE},
+      {AUTO, true, 8196, 129, LANE},   {WAVE, false, 100000, 1563, WAVE}, {WAVE, true, 100000, 1563, WAVE}, {LANE, false, 4, 1, LANE},
+      {LANE, true, 4, 1, LANE},        {FOUR, false, 4, 1, FOUR},       {FOUR, false, 100000, 1563, FOUR}, {FOUR, true, 4, 1, LANE}};
+  for (const auto& t : fic) CHECK(fic_form(def, t.forced, t.soft, t.nblocks, t.ntiles) == t.want);
+  struct { int wave, four, nblocks, ntiles, want; } fknobs[] = {
+      {0, 0, 4, 1, LANE},     {0, 1, 400000, 6250, FOUR}, {0, 10, 640, 10, FOUR}, {0, 10, 644, 11, LANE}, {640, 0, 640, 10, WAVE},
+      {640, 0, 644, 11, LANE}, {640, 128, 644, 11, FOUR}, {3, 128, 4, 1, FOUR}};
+  for (const auto& t : fknobs) {
+    FormKnobs k;
+    k.wave_max_fic_blocks = t.wave;
+    k.fic_four_lanes_max_tiles = t.four;
+    CHECK(fic_form(k, AUTO, false, t.nblocks, t.ntiles) == t.want);
+  }
+  // what set_decoder_forms admits
+  for (int f = -3; f < 8; ++f) {
+    CHECK(msc_form_valid(f) == (f >= -1 && f <= 4));
+    CHECK(fic_form_valid(f) == (f == AUTO || f == WAVE || f == LANE || f == FOUR));
+  }
+}
+
 // byte-level replay of what sdr_read_fifo does to the 393216-byte frame buffer (sdr_fifo.c:43-61), on a stream whose byte at
 // offset x is the tag x itself (64-bit), so a view can be compared position by position
 static void test_fifo_views()
@@ -344,7 +550,8 @@ int main(int argc, char** argv)
 {
   const char* only = argc > 1 ? argv[1] : "";
   struct { const char* name; void (*fn)(); } tests[] = {
-      {"pool", test_pool_and_lane}, {"worklist", test_control_and_worklist}, {"fifo", test_fifo_views}, {"synth", test_synth}};
+      {"pool", test_pool_and_lane}, {"worklist", test_control_and_worklist}, {"fifo", test_fifo_views}, {"synth", test_synth},
+      {"layout", test_layout}, {"carry", test_carry}, {"forms", test_forms}};
   for (const auto& t : tests) {
     if (*only && std::strcmp(only, t.name) != 0) continue;
     t.fn();
