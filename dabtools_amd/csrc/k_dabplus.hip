@@ -41,12 +41,14 @@ __global__ void __launch_bounds__(256) dabplus_locate_kernel(DabPlusFrames fr, c
   DabPlusLoc* out = loc + t * nsub;
   for (int q = 0; q < nsub; ++q) out[q] = DabPlusLoc{nullptr, 0, fct, 0, {0, 0}};
   int off = 12 + 4 * nst + 96 * ficf;
+  uint64_t seen = 0;                                 // a SubChId listed twice in the STC: its first entry counts (nsub <= 64)
   for (int i = 0; i < nst; ++i) {
     const int scid = f[8 + 4 * i] >> 2;
     const int stl = ((f[8 + 4 * i + 2] & 3) << 8) | f[8 + 4 * i + 3];
     const bool fits = off + 8 * stl <= kEti;
     for (int q = 0; q < nsub; ++q) {
-      if (subch[q] != scid) continue;
+      if (subch[q] != scid || (seen >> q & 1)) continue;
+      seen |= uint64_t{1} << q;
       out[q].stl = stl;
       if (fits && stl > 0 && stl % 3 == 0 && stl <= 3 * kMaxS) {      // s <= 72: the au kernel's LDS copy of a superframe
         const uint8_t* p = f + off;

@@ -534,7 +534,9 @@ typedef struct dabhip_dabplus_sf {  /* one superframe of the last push */
 dabhip_dabplus *dabhip_dabplus_create(int device, int nstreams, const int32_t *subch_ids, int nsub);
 void dabhip_dabplus_destroy(dabhip_dabplus *d);
 /* counts[s] ETI frames of stream s, stream after stream in `frames` (dabhip_engine_eti_device_ptr's layout): DEVICE memory when on_device != 0,
- * host memory otherwise.  Returns the superframes completed by this call, <0 on error. */
+ * host memory otherwise (device frames need no alignment).  Returns the superframes completed by this call, <0 on error.
+ * A frame carries a requested SubChId when its STC lists it, FICF set or not; if the STC lists the id more than once, the first entry counts
+ * and the later ones are ignored, also when the first is no DAB+ sub-channel (STL 0, not a multiple of 3, above 216, or past byte 6144). */
 int64_t dabhip_dabplus_push(dabhip_dabplus *d, const uint8_t *frames, const int64_t *counts, int on_device);
 /* The superframes of the last push of one (stream, sub-channel index), in order: copies min(n, cap) records, returns n. */
 int64_t dabhip_dabplus_superframes(const dabhip_dabplus *d, int stream, int sub, dabhip_dabplus_sf *out, int64_t cap);

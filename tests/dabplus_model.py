@@ -272,15 +272,16 @@ def good_aus(data, rec):
 
 
 # ---- ETI frames and the sync rule ---------------------------------------------------------------------
-def eti_frame(fct, subs, fill=0x55):
-    """An ETI(NI) frame with FCT fct and sub-channels subs = [(SubChId, payload bytes (8 STL of them))], FIC present (zeros)."""
+def eti_frame(fct, subs, fill=0x55, ficf=1):
+    """An ETI(NI) frame with FCT fct and sub-channels subs = [(SubChId, payload bytes (8 STL of them))]; ficf = 1: 96 FIC bytes (fill) before
+    the sub-channels, ficf = 0: none."""
     f = bytearray([fill]) * ETI_BYTES
     odd = fct & 1
     f[0:4] = bytes([0xFF, 0xF8, 0xC5, 0x49]) if odd else bytes([0xFF, 0x07, 0x3A, 0xB6])
     f[4] = fct % FCT_MOD
     nst = len(subs)
-    f[5] = 0x80 | nst
-    pos = 12 + 4 * nst + 96
+    f[5] = (ficf << 7) | nst
+    pos = 12 + 4 * nst + 96 * ficf
     for i, (scid, pay) in enumerate(subs):
         stl = len(pay) // 8
         assert len(pay) == 8 * stl
