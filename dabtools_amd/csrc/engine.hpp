@@ -13,10 +13,10 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <chrono>
 #include <cstdint>
 #include <cstdlib>
 #include <map>
-#include <functional>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -27,6 +27,7 @@
 #include "control_plane.hpp"
 #include "decoder_form.hpp"
 #include "device_types.hpp"
+#include "scan_plan.hpp"
 #include "segment_layout.hpp"
 #include "thread_pool.hpp"
 #include "worklist.hpp"
@@ -34,6 +35,7 @@
 namespace dabhip {
 
 struct FrameListArgs;     // kernels.hpp
+struct SyncArgs;
 void set_error(const std::string& msg);
 
 // The HIP runtime keeps its records of a stream's finished commands until somebody synchronises THAT STREAM: an event or a blocking copy that waits
@@ -302,12 +304,33 @@ class Engine {
   bool record(hipEvent_t e, hipStream_t s);
   bool elapsed(float* ms, hipEvent_t a, hipEvent_t b);
   bool hard_only(const char* what);
+  // one decode_impl call: what its stages share
+  struct DecodeRun {
+    const size_t* nbytes;
+    int nstreams;
+    bool cont;                               // a session's further segment
+    std::chrono::steady_clock::time_point wall0;
+    std::unique_lock<std::mutex> heavy;      // the heavy lock, held from stage A to the drain
+    int chunk = 1;                           // frames per launch of the OFDM stage
+    bool host_ok = true;                     // the control-plane pass's outcome
+    std::string host_error;
+    void mark(const char* what) const;       // DABHIP_TRACE_HOST: a line with the time since wall0
+  };
   int64_t decode_impl(const uint8_t* const* iq, const size_t* nbytes, int nstreams, bool on_device, bool cont, bool full_scan = false);
   bool begin_decode(int nstreams, bool cont);
+  bool stage_a(DecodeRun& run);              // layout's buffers, then the FIC symbols of every TF through the OFDM stage
+  void control_pass(DecodeRun& run);         // control plane + work lists, on the host lane
   bool layout_frames(const size_t* nbytes, int nstreams);
-  // layout: called when the calls' {status, ordinal} are on the host (h_info_) -- early in the split scan, again after a re-scan
-  bool scan_streams(const uint8_t* const* iq, const size_t* nbytes, int nstreams, bool on_device, bool cont, bool full_scan,
-                    const std::function<bool()>& layout);
+  // called when the calls' {status, ordinal} are on the host (h_info_) -- early in the split scan, again after a re-scan.  A fresh decode runs stage A from here
+  bool layout_and_a(DecodeRun& run) { return layout_frames(run.nbytes, run.nstreams) && (run.cont || stage_a(run)); }
+  // K1 (engine_scan.cpp): scan_begin = buffers, the plan (scan_) and the set-up launch; scan_chain = the split scan's launches; scan_fetch = the results the
+  // host needs, awaited; scan_again = the streams that broke the chain's assumption once more, in the reference's order
+  bool scan_streams(const uint8_t* const* iq, bool on_device, bool full_scan, DecodeRun& run);
+  bool scan_begin(const uint8_t* const* iq, bool on_device, bool full_scan, const DecodeRun& run);
+  bool scan_chain(bool cont);
+  bool scan_fetch();
+  bool scan_again(DecodeRun& run);
+  SyncArgs sync_args(int nstreams, int max_calls) const;   // the block K1's launches share (kernels.hpp)
   // host-fed decode: the streams' bytes into d_iq_own_ (ptrs[b] = where stream b landed), queued on the main stream
   bool upload_iq(const uint8_t* const* iq, const size_t* nbytes, int nstreams, const uint8_t** ptrs);
   bool carry_and_reserve(const SegmentLayout& seg);
@@ -350,6 +373,13 @@ class Engine {
   // ofdm_msc_part = the 72 MSC symbols through the configured stage (fused / two-kernel, hard / soft, guard as set) in chunks of `chunk` frames,
   // with three timing events per chunk from chunk_ev_[3 * ev_base] on when ev_base >= 0
   FrameListArgs frame_list() const;    // the block those launches share, from the buffers as they stand now (kernels.hpp)
+  // stage entries and the S2 seam: n frames of ONE stream (d_iq) become the frame list -- frame j = call j (descs[j]: the caller's, alive until it has
+  // awaited the stream; null: slots and rows only), TF slot j, MSC rows from row_lead + 4 j; bit_rows: those slots' rows are reserved
+  bool set_frame_list(const uint8_t* d_iq, const CallDesc* descs, int n, int row_lead, bool bit_rows);
+  const uint8_t* frames_on_device(const uint8_t* frames, int nframes, bool on_device);   // host frames into d_iq_own_; null: failed
+  // a new run of guarded launches: their counters start over (guard_new_count: the flagged decisions' count too)
+  void guard_new_run() { guard_launches_ = 0; guard_counters_clear_ = false; }
+  void guard_new_count() { guard_new_run(); guard_flagged_ = 0; }
   GuardArgs soft_guard_args() const;   // soft decisions, two-kernel stage: K2b reads the energies K2 left, lists nothing
   bool fused_parts(int first, int n, int sym_a, int sym_b, int nparts);
   bool ofdm_msc_part(int first, int n, int chunk, int ev_base);
@@ -441,6 +471,7 @@ class Engine {
   SegmentLayout seg_;
   struct { int chunk = 1, deferred = 0; bool pending = false; } last_;
   std::vector<int> seg_ncalls_, seg_defer_max_;   // layout_segment's per-stream inputs
+  std::vector<int> scan_ncalls_;                  // plan_scan's: the complete calls every stream holds
   DeviceBuffer<float> d_delta_;
   DeviceBuffer<uint4> d_guard_list_;
   DeviceBuffer<uint32_t> d_guard_counter_;
@@ -460,7 +491,9 @@ class Engine {
   PinnedBuffer<CallDesc> h_descs_;
   PinnedBuffer<int2> h_info_;
   PinnedBuffer<uint8_t> h_fibs_, h_fib_ok_;
-  int max_calls_ = 0, nstreams_ = 0;
+  ScanPlan scan_;                    // the last scan's schedule (scan_plan.hpp); h_descs_ and h_info_ are [nstreams_][scan_.max_calls]
+  int list_max_calls_ = 0;           // descriptor stride of the frame list now on the device (a decode's: scan_.max_calls; a stage entry's: its frames)
+  int nstreams_ = 0;
   float scan_setup_ms_ = 0, layout_ms_ = 0;
   std::vector<int64_t> eti_base_, eti_count_;
   std::vector<uint32_t> stream_status_;

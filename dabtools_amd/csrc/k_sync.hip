@@ -1113,40 +1113,38 @@ hipError_t launch_scan_setup(const ScanSetupArgs& a, hipStream_t stream)
   return hipGetLastError();
 }
 
-hipError_t launch_sync_scan(const uint8_t* const* iq, const int64_t* nbytes, StreamState* states, CallDesc* descs, int2* info,
-                            int nstreams, int max_calls, int call_begin, int call_end, const double2* tw2048,
-                            const double2* tw1536, const uint8_t* prs_q, int afc, hipStream_t stream, bool chain_only,
-                            const StreamState* states_in, const int* stream_list, SyncTails tails, SpecArgs spec)
+hipError_t launch_sync_scan(const SyncArgs& a, const SyncScanOpts& o, hipStream_t stream)
 {
+  SyncTails tails = o.tails;
   if (tails.chunk < 0) tails.chunk = kChunkBytes;
-  if (nstreams <= 0) return hipSuccess;
+  const int nblocks = a.nstreams;                          // (with a stream_list: its length)
+  if (nblocks <= 0) return hipSuccess;
   hipError_t e = sync_attr();
   if (e != hipSuccess) return e;
   const size_t lds = sync_scan_lds_bytes();
-  if (!states_in) states_in = states;
-  if (chain_only)
-    hipLaunchKernelGGL(sync_scan_kernel<true>, dim3(nstreams), dim3(kThreads), lds, stream, iq, nbytes, states_in, states, stream_list, descs, info,
-                       max_calls, call_begin, call_end, tw2048, tw1536, prs_q, afc, tails, spec);
+  const StreamState* const states_in = o.states_in ? o.states_in : a.states;
+  if (o.chain_only)
+    hipLaunchKernelGGL(sync_scan_kernel<true>, dim3(nblocks), dim3(kThreads), lds, stream, a.iq, a.nbytes, states_in, a.states, o.stream_list, a.descs, a.info,
+                       a.max_calls, o.call_begin, o.call_end, a.tw2048, a.tw1536, a.prs_q, o.afc, tails, o.spec);
   else
-    hipLaunchKernelGGL(sync_scan_kernel<false>, dim3(nstreams), dim3(kThreads), lds, stream, iq, nbytes, states_in, states, stream_list, descs, info,
-                       max_calls, call_begin, call_end, tw2048, tw1536, prs_q, afc, tails, spec);
+    hipLaunchKernelGGL(sync_scan_kernel<false>, dim3(nblocks), dim3(kThreads), lds, stream, a.iq, a.nbytes, states_in, a.states, o.stream_list, a.descs, a.info,
+                       a.max_calls, o.call_begin, o.call_end, a.tw2048, a.tw1536, a.prs_q, o.afc, tails, o.spec);
   return hipGetLastError();
 }
 
-hipError_t launch_sync_ahead(const uint8_t* const* iq, const int64_t* nbytes, const StreamState* states, int nstreams, const double2* tw2048, const double2* tw1536,
-                             const uint8_t* prs_q, hipStream_t stream, const SpecArgs& spec)
+hipError_t launch_sync_ahead(const SyncArgs& a, const SpecArgs& spec, hipStream_t stream)
 {
-  if (nstreams <= 0 || spec.nspec <= 0 || spec.nhyp <= 0) return hipSuccess;
+  if (a.nstreams <= 0 || spec.nspec <= 0 || spec.nhyp <= 0) return hipSuccess;
   hipError_t e = sync_attr();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(sync_ahead_kernel, dim3(spec.nhyp, spec.nspec, nstreams), dim3(kThreads), sync_scan_lds_bytes(), stream, iq, nbytes, states, tw2048, tw1536, prs_q,
-                     kChunkBytes, spec);
+  hipLaunchKernelGGL(sync_ahead_kernel, dim3(spec.nhyp, spec.nspec, a.nstreams), dim3(kThreads), sync_scan_lds_bytes(), stream, a.iq, a.nbytes, a.states, a.tw2048,
+                     a.tw1536, a.prs_q, kChunkBytes, spec);
   return hipGetLastError();
 }
 
-hipError_t launch_sync_verify(const uint8_t* const* iq, const int64_t* nbytes, const int* calls_before, StreamState* states, CallDesc* descs,
-                              int nstreams, int max_calls, const double2* tw2048, const uint8_t* prs_q, int* violation, bool carry_only, hipStream_t stream)
+hipError_t launch_sync_verify(const SyncArgs& a, const int* calls_before, int* violation, bool carry_only, hipStream_t stream)
 {
+  const int nstreams = a.nstreams, max_calls = a.max_calls;
   if (nstreams <= 0 || max_calls <= 0) return hipSuccess;
   hipError_t e = sync_attr();
   if (e != hipSuccess) return e;
@@ -1157,17 +1155,16 @@ hipError_t launch_sync_verify(const uint8_t* const* iq, const int64_t* nbytes, c
     static const int mode = std::getenv("DABHIP_VERIFY_FP32") ? std::atoi(std::getenv("DABHIP_VERIFY_FP32")) : 1;
     const bool fp32_first = mode != 0;
     if (fp32_first)
-      hipLaunchKernelGGL(sync_verify32_kernel, dim3(blocks), dim3(kThreads), sync_verify32_lds_bytes(), stream, iq, descs, max_calls, nstreams, tw2048, prs_q, violation,
-                         mode == 2 ? 1 : 0);
+      hipLaunchKernelGGL(sync_verify32_kernel, dim3(blocks), dim3(kThreads), sync_verify32_lds_bytes(), stream, a.iq, a.descs, max_calls, nstreams, a.tw2048, a.prs_q,
+                         violation, mode == 2 ? 1 : 0);
     // behind the fp32 pass the fp64 kernel normally finds nothing to do: a small persistent grid looks through the descriptors then
-    hipLaunchKernelGGL(sync_verify_kernel, dim3(fp32_first ? std::min(blocks, 1024) : blocks), dim3(kThreads), sync_scan_lds_bytes(), stream, iq, descs, max_calls,
-                       nstreams, tw2048, prs_q, violation, fp32_first ? 1 : 0);
+    hipLaunchKernelGGL(sync_verify_kernel, dim3(fp32_first ? std::min(blocks, 1024) : blocks), dim3(kThreads), sync_scan_lds_bytes(), stream, a.iq, a.descs, max_calls,
+                       nstreams, a.tw2048, a.prs_q, violation, fp32_first ? 1 : 0);
   } else {
-    hipLaunchKernelGGL(sync_carry_kernel, dim3((nstreams + 3) / 4), dim3(256), 0, stream, descs, max_calls, nbytes, calls_before, states, violation, nstreams);
+    hipLaunchKernelGGL(sync_carry_kernel, dim3((nstreams + 3) / 4), dim3(256), 0, stream, a.descs, max_calls, a.nbytes, calls_before, a.states, violation, nstreams);
   }
   return hipGetLastError();
 }
-
 
 #if DABHIP_SYNC_TIMES
 }  // namespace dabhip

@@ -59,8 +59,7 @@ hipError_t launch_host_words(const HostWordsArgs& a, hipStream_t stream);
 // K1: synchronisation scan, one workgroup per stream, calls [call_begin, call_end) (call_end < 0: all).
 // chain_only: FIFO bookkeeping, coarse and fine time only, assuming every frame's coarse frequency offset stays within +-1
 // carrier; launch_sync_verify then computes both frequency estimates for all frames in parallel and records the first call
-// of each stream that breaks the assumption.  states_in (default: states): where the incoming state is read from;
-// stream_list (default: all, block b = stream b): the streams to scan.
+// of each stream that breaks the assumption.  states_in: where the incoming state is read from; stream_list: the streams to scan.
 // tails: the streams' tail bytes (device_types.hpp: kTailBytes) -- carried in from state_in, out to state_out, one copy per call that reads a frame
 // into images[(stream * max_calls + call) * kTailBytes] (FrameView::tail of that call's view points there); chunk: bytes appended per call (< 0: 262144)
 struct SyncTails {
@@ -81,18 +80,28 @@ struct SpecArgs {
   int call_limit = -1;                  // chain launches: at most this many calls per stream (< 0: to the end)
   int record_base = 0;
 };
-hipError_t launch_sync_scan(const uint8_t* const* iq, const int64_t* nbytes, StreamState* states, CallDesc* descs, int2* info,
-                            int nstreams, int max_calls, int call_begin, int call_end, const double2* tw2048,
-                            const double2* tw1536, const uint8_t* prs_q, int afc, hipStream_t stream, bool chain_only = false,
-                            const StreamState* states_in = nullptr, const int* stream_list = nullptr, SyncTails tails = SyncTails{nullptr, nullptr, nullptr, -1},
-                            SpecArgs spec = SpecArgs{});
+// What every K1 launch shares: the streams' samples and sizes, their front-end states, the calls' descriptors (descs[stream * max_calls + call]) and
+// {status, ordinal} records, the fp64 twiddles and the phase reference symbol.
+struct SyncArgs {
+  const uint8_t* const* iq; const int64_t* nbytes; StreamState* states; CallDesc* descs; int2* info; int nstreams, max_calls;
+  const double2 *tw2048, *tw1536; const uint8_t* prs_q;
+};
+// ... and what differs from one scan launch to the next
+struct SyncScanOpts {
+  int call_begin = -1, call_end = -1;     // the calls to run (call_end < 0: all)
+  int afc = 0;
+  bool chain_only = false;
+  const StreamState* states_in = nullptr; // null: a.states
+  const int* stream_list = nullptr;       // null: block b = stream b; else the a.nstreams streams to scan
+  SyncTails tails{nullptr, nullptr, nullptr, -1};
+  SpecArgs spec;
+};
+hipError_t launch_sync_scan(const SyncArgs& a, const SyncScanOpts& o, hipStream_t stream);
 // the look-ahead pass over the calls every stream has left from where it stands (at most spec.nspec of them)
-hipError_t launch_sync_ahead(const uint8_t* const* iq, const int64_t* nbytes, const StreamState* states, int nstreams, const double2* tw2048, const double2* tw1536,
-                             const uint8_t* prs_q, hipStream_t stream, const SpecArgs& spec);
+hipError_t launch_sync_ahead(const SyncArgs& a, const SpecArgs& spec, hipStream_t stream);
 // carry_only = false: the verification pass (violation[b] = first offending call, untouched otherwise);
 // carry_only = true: fine_freq_shift carried through the calls that did not demodulate, for the streams without a violation
-hipError_t launch_sync_verify(const uint8_t* const* iq, const int64_t* nbytes, const int* calls_before, StreamState* states, CallDesc* descs,
-                              int nstreams, int max_calls, const double2* tw2048, const uint8_t* prs_q, int* violation, bool carry_only, hipStream_t stream);
+hipError_t launch_sync_verify(const SyncArgs& a, const int* calls_before, int* violation, bool carry_only, hipStream_t stream);
 
 // What every launch over the frame list shares: the streams' samples, the calls' descriptors (descs[stream * max_calls + call]), the list itself
 // (frames[i] = {stream, call}, FIC rows at TF slot frame_slot[i], MSC rows from logical CIF row frame_cif_row[i]), the fp32 twiddles, the

@@ -1,7 +1,7 @@
 // segment_layout.hpp — where the transmission frames of one decode() / one segment of a session go, and what a session carries from segment to segment.
 //
 // No GPU call and no HIP type in here (like worklist.hpp): pure integer arithmetic, run by the CPU suite under ThreadSanitizer / AddressSanitizer / UBSan
-// (tests/host_sanitize).  It is the contract of every kernel of the OFDM stage, the carry-over copies, read_demapped_tf and complete_deferred (engine.cpp).
+// (tests/host_sanitize).  It is the contract of every kernel of the OFDM stage, the carry-over copies, read_demapped_tf (engine_msc.cpp) and complete_deferred (engine_ofdm.cpp).
 #pragma once
 
 #include <algorithm>

@@ -8,6 +8,7 @@
 //   segment_layout.hpp the frame list, TF slots and logical CIF rows of random segments (with and without the lock-in skip, mis-numbered
 //                      ordinals under ASan) and the session carry over runs of segments, against a per-TF list kept here
 //   decoder_form.hpp   the decoder-form rule at both sides of every documented crossover, each knob's 0 / 1 / N reading, every forced form
+//   scan_plan.hpp      the K1 scan's schedule (split scan, look-ahead pass, its table and passes) at both sides of every crossover
 //   fifo_view.hpp      the closed-form FIFO / stale-tail views under random timing corrections, against a byte-level replay of
 //                      cbWrite / sdr_read_fifo's copying rule (sdr_fifo.c:26-61)
 //   synth.cpp          the modulator's bit content and sample generation (bounds, UB)
@@ -28,6 +29,7 @@
 #include "../../dabtools_amd/csrc/control_plane.hpp"
 #include "../../dabtools_amd/csrc/decoder_form.hpp"
 #include "../../dabtools_amd/csrc/fifo_view.hpp"
+#include "../../dabtools_amd/csrc/scan_plan.hpp"
 #include "../../dabtools_amd/csrc/segment_layout.hpp"
 #include "../../dabtools_amd/csrc/thread_pool.hpp"
 #include "../../dabtools_amd/csrc/worklist.hpp"
@@ -394,7 +396,7 @@ static void test_carry()
   }
 }
 
-// The decoder-form rule: the expected forms are the rule as engine.cpp spelled it out before it moved to decoder_form.hpp (launch_decode_batch,
+// The decoder-form rule: the expected forms are the rule as the engine spelled it out before it moved to decoder_form.hpp (launch_decode_batch,
 // fic_decode_slots_async, msc_prepare), at the documented crossovers (include/dabhip.h)
 static void test_forms()
 {
@@ -450,6 +452,75 @@ static void test_forms()
   for (int f = -3; f < 8; ++f) {
     CHECK(msc_form_valid(f) == (f >= -1 && f <= 4));
     CHECK(fic_form_valid(f) == (f == AUTO || f == WAVE || f == LANE || f == FOUR));
+  }
+}
+
+// The scan's schedule: the expected values are the rule as Engine::scan_streams spelled it out before it moved to scan_plan.hpp (use_spec, nspec, passes,
+// call_limit, the fetch's word count), at every crossover
+static void test_scan()
+{
+  const ScanKnobs def;
+  CHECK(def.hypotheses == 33 && def.spec_max_streams == 4);
+  // nstreams streams of `calls` complete calls each, `done` of them scanned by an earlier segment
+  auto plan = [](int nstreams, int calls, int done, bool afc, bool full_scan, bool cont, int mode, const ScanKnobs& k) {
+    const std::vector<int> ncalls(static_cast<size_t>(nstreams), calls), calls_done(static_cast<size_t>(nstreams), done);
+    return plan_scan(nstreams, ncalls.data(), calls_done.data(), afc, full_scan, cont, mode, k);
+  };
+  const size_t state_words = sizeof(StreamState) / 4;
+  // default mode: the pass for at most 4 streams of at least 16 calls; forced: up to 512 streams, however few calls; off: never.  The split scan runs in all three
+  struct { int nstreams, calls, mode; bool ahead; } rule[] = {
+      {4, 16, -1, true},  {5, 16, -1, false},  {4, 15, -1, false}, {1, 16, -1, true},  {1, 15, -1, false}, {4, 1000, -1, true}, {5, 1000, -1, false},
+      {512, 1, 1, true},  {513, 1, 1, false},  {513, 1000, 1, false}, {5, 15, 1, true}, {1, 1000, 0, false}, {4, 16, 0, false}};
+  for (const auto& t : rule) {
+    const ScanPlan p = plan(t.nstreams, t.calls, 0, false, false, false, t.mode, def);
+    CHECK(p.split && p.ahead == t.ahead && p.max_calls == t.calls && p.ndesc == static_cast<size_t>(t.nstreams) * t.calls && p.nhyp == 33);
+    CHECK(p.result_words == static_cast<size_t>(t.nstreams) + 1 + (t.ahead ? 1 : 0) + p.ndesc * 2 + t.nstreams * state_words);
+  }
+  // the software AFC and the full scan: the reference's order -- no split, no pass, whatever the mode; no violation marks in the fetch
+  for (int mode : {-1, 0, 1})
+    for (int which = 0; which < 2; ++which) {
+      const ScanPlan p = plan(2, 64, 0, which == 0, which == 1, false, mode, def);
+      CHECK(!p.split && !p.ahead && p.max_calls == 64 && p.ndesc == 128 && p.result_words == 128 * 2 + 2 * state_words);
+    }
+  // the table: nspec = min(max_calls, clamp(2^20 / nstreams, 64, 4096)) -- 2^20 / nstreams crosses 4096 at 256 streams and 64 at 16,384
+  struct { int nstreams, calls, nspec; } table[] = {{1, 5000, 4096},   {255, 5000, 4096},  {256, 5000, 4096},  {257, 5000, 4080},   {512, 5000, 2048},
+                                                    {16000, 100, 65},  {16384, 100, 64},   {16385, 100, 64},   {20000, 100, 64},    {4, 100, 100},
+                                                    {4, 1, 1},         {20000, 10, 10}};
+  for (const auto& t : table) CHECK(plan(t.nstreams, t.calls, 0, false, false, false, 1, def).nspec == t.nspec);
+  // the passes: ceil(max_calls / nspec), at most 16; every pass but the last is followed by a chain of nspec calls, the last by one to the end
+  struct { int nstreams, calls, nspec, passes; } passes[] = {{1, 4096, 4096, 1},   {1, 4097, 4096, 2},   {1, 65536, 4096, 16}, {1, 65537, 4096, 16}, {1, 200000, 4096, 16},
+                                                            {512, 2048, 2048, 1}, {512, 2049, 2048, 2}, {512, 32768, 2048, 16}, {512, 32769, 2048, 16}, {4, 16, 16, 1}};
+  for (const auto& t : passes) {
+    const ScanPlan p = plan(t.nstreams, t.calls, 0, false, false, false, 1, def);
+    CHECK(p.ahead && p.nspec == t.nspec && p.passes == t.passes);
+    for (int r = 0; r < p.passes; ++r) CHECK(p.pass_limit(r) == (r + 1 < t.passes ? t.nspec : -1));
+  }
+  // the chain in front of the first pass: seven calls of a fresh decode, none of a session's further segment
+  CHECK(plan(2, 64, 0, false, false, false, -1, def).first_limit == 7 && plan(2, 64, 0, false, false, true, -1, def).first_limit == 0);
+  CHECK(plan(2, 64, 0, false, false, true, -1, def).ahead && plan(2, 64, 0, false, false, true, 0, def).first_limit == 0);
+  // a session's segments: the calls that became complete since the last one, at least one descriptor per stream
+  {
+    const ScanPlan one = plan(3, 40, 39, false, false, true, -1, def), none = plan(3, 40, 40, false, false, true, -1, def);
+    CHECK(one.max_calls == 1 && one.ndesc == 3 && !one.ahead && one.nspec == 1 && one.passes == 1);
+    CHECK(none.max_calls == 1 && none.ndesc == 3 && !none.ahead);
+    const int ncalls[3] = {40, 10, 57}, done[3] = {39, 10, 40};
+    const ScanPlan mixed = plan_scan(3, ncalls, done, false, false, true, -1, def);
+    CHECK(mixed.max_calls == 17 && mixed.ndesc == 51 && mixed.ahead && mixed.nspec == 17 && mixed.first_limit == 0);
+    const int done16[3] = {39, 10, 42};
+    CHECK(!plan_scan(3, ncalls, done16, false, false, true, -1, def).ahead);      // 15 calls left
+  }
+  // the knobs: the window is odd within 3 .. 63; the default mode's largest batch within 0 .. 512
+  struct { int hyp, want; } windows[] = {{33, 33}, {32, 33}, {0, 3}, {1, 3}, {2, 3}, {3, 3}, {4, 5}, {62, 63}, {63, 63}, {64, 63}, {1000, 63}, {-5, 3}};
+  for (const auto& t : windows) {
+    ScanKnobs k;
+    k.hypotheses = t.hyp;
+    CHECK(plan(1, 16, 0, false, false, false, -1, k).nhyp == t.want);
+  }
+  struct { int knob, nstreams; bool ahead; } batches[] = {{0, 1, false}, {-3, 1, false}, {1, 1, true}, {1, 2, false}, {8, 8, true}, {8, 9, false}, {1000, 512, true}, {1000, 513, false}};
+  for (const auto& t : batches) {
+    ScanKnobs k;
+    k.spec_max_streams = t.knob;
+    CHECK(plan(t.nstreams, 16, 0, false, false, false, -1, k).ahead == t.ahead);
   }
 }
 
@@ -551,7 +622,7 @@ int main(int argc, char** argv)
   const char* only = argc > 1 ? argv[1] : "";
   struct { const char* name; void (*fn)(); } tests[] = {
       {"pool", test_pool_and_lane}, {"worklist", test_control_and_worklist}, {"fifo", test_fifo_views}, {"synth", test_synth},
-      {"layout", test_layout}, {"carry", test_carry}, {"forms", test_forms}};
+      {"layout", test_layout}, {"carry", test_carry}, {"forms", test_forms}, {"scan", test_scan}};
   for (const auto& t : tests) {
     if (*only && std::strcmp(only, t.name) != 0) continue;
     t.fn();
