@@ -194,6 +194,14 @@ _SIGNATURES = {
     "dabhip_engine_guard_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "dabhip_engine_guard_overflows": (C.c_int, [C.c_void_p]),
     "dabhip_engine_set_guard_list_cap": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "dabhip_engine_set_launch_limits": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "dabhip_engine_launch_report": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "dabhip_engine_msc_plan": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int64)]),
+    "dabhip_host_stream_state_bytes": (C.c_int, []),
+    "dabhip_dab_set_launch_limits": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "dabhip_dab_launch_report": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "dabhip_stream_set_launch_limits": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "dabhip_stream_launch_report": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
     "dabhip_stream_set_parity_guard": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_stage_decision_audit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "dabhip_stage_decision_audit_fused": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
@@ -300,6 +308,26 @@ def _decoder_forms(fn, h):
     m, f = C.c_uint32(0), C.c_uint32(0)
     _need(fn(h, C.byref(m), C.byref(f)) == 0, "decoder_forms")
     return m.value, f.value
+
+
+# launch limits (dabhip.h: DABHIP_LIMIT_*) and the launch report (DABHIP_REPORT_*), in the C ABI's order
+LAUNCH_LIMITS = ("decision_rows", "regroup_tiles", "fic_group_tiles", "gather_descs", "fetch_words", "fft_chunk_tfs")
+LAUNCH_REPORT = ("decoder", "regroup", "fic_group", "gather", "ofdm_chunks", "fic_prepass", "fetch_form", "fetches", "gather_calls", "decoder_planned")
+FETCH_NONE, FETCH_KERNEL, FETCH_COPY_ENGINE = 0, 1, 2
+
+
+def _set_launch_limits(fn, h, limits):
+    unknown = set(limits) - set(LAUNCH_LIMITS)
+    if unknown:
+        raise ValueError("no such launch limit: %s" % ", ".join(sorted(unknown)))
+    arr = (C.c_int64 * len(LAUNCH_LIMITS))(*[int(limits.get(k, 0)) for k in LAUNCH_LIMITS])
+    _need(fn(h, arr, len(LAUNCH_LIMITS)) == 0, "set_launch_limits")
+
+
+def _launch_report(fn, h):
+    out = (C.c_int64 * len(LAUNCH_REPORT))()
+    _need(fn(h, out, len(LAUNCH_REPORT)) == len(LAUNCH_REPORT), "launch_report")
+    return dict(zip(LAUNCH_REPORT, list(out)))
 
 
 def _need(cond, what):
@@ -472,6 +500,11 @@ def host_eti_header(hdr, sub):
     n = lib().dabhip_host_eti_header(hdr.ctypes.data_as(C.POINTER(C.c_int32)), sub.ctypes.data_as(C.POINTER(C.c_int32)), _p(out), out.size)
     _need(n > 0, "host_eti_header")
     return out[:n].copy()
+
+
+def host_stream_state_bytes():
+    """sizeof the front end's per-stream state (dabhip_host_stream_state_bytes)"""
+    return lib().dabhip_host_stream_state_bytes()
 
 
 def host_lockin_deferred(locked, okcount, ntf):
@@ -648,6 +681,14 @@ class Dab:
         """The forms that ran in the last process_frame: ({MSC form names}, {FIC form names}), or the two bit masks."""
         m, f = _decoder_forms(lib().dabhip_dab_decoder_forms, self._h)
         return (m, f) if masks else (_form_names(m), _form_names(f))
+
+    def set_launch_limits(self, **limits):
+        """see Engine.set_launch_limits"""
+        _set_launch_limits(lib().dabhip_dab_set_launch_limits, self._h, limits)
+
+    def launch_report(self):
+        """The launches of the last process_frame (see Engine.launch_report)."""
+        return _launch_report(lib().dabhip_dab_launch_report, self._h)
 
     def process_frame(self):
         r = lib().dabhip_dab_process_frame(self._h)
@@ -859,6 +900,24 @@ class Engine:
     def set_guard_list_cap(self, cap):
         """Test knob: capacity of the guard's list per launch (0 = automatic)."""
         _need(lib().dabhip_engine_set_guard_list_cap(self._h, cap) == 0, "set_guard_list_cap")
+
+    def set_launch_limits(self, **limits):
+        """Test knob: the sizes past which a decode is split into several launches (LAUNCH_LIMITS; a limit left out or 0 = its default).  The output
+        does not depend on them.  A value no launch could be made with is refused (DabhipError) and the limits stay as they were."""
+        _set_launch_limits(lib().dabhip_engine_set_launch_limits, self._h, limits)
+
+    def launch_report(self):
+        """{loop: launches it made} of the last decode / stage entry (LAUNCH_REPORT), and how the scan's results came back (fetch_form: FETCH_*)."""
+        return _launch_report(lib().dabhip_engine_launch_report, self._h)
+
+    def msc_plan(self):
+        """(trellis steps of every wave-group of the last decode's MSC batch in launch order, tiles of 64 records its regroup covers): dabhip_engine_msc_plan"""
+        tiles = C.c_int64(0)
+        n = lib().dabhip_engine_msc_plan(self._h, None, 0, C.byref(tiles))
+        _need(n >= 0, "msc_plan")
+        steps = np.zeros(max(n, 1), dtype=np.int32)
+        _need(lib().dabhip_engine_msc_plan(self._h, steps.ctypes.data_as(C.POINTER(C.c_int32)), n, C.byref(tiles)) == n, "msc_plan")
+        return steps[:n], tiles.value
 
     def decision_audit(self, frames=None, device_ptr=None, nframes=None, guard=False, fused=False):
         """fp32 OFDM stage vs fp64 on contiguous cu8 frames -> dict (see dabhip_stage_decision_audit); fused: the default decode's one-kernel stage
@@ -1184,15 +1243,32 @@ class Stream:
         """see Engine.set_parity_guard"""
         _need(self._f("set_parity_guard")(self._h, _guard_level(level)) == 0, "stream_set_parity_guard")
 
+    def _single_device(self, what):
+        """The entries that exist for dabhip_stream handles only: a multi-device session's handle is another type."""
+        if self._PREFIX != "dabhip_stream_":
+            raise DabhipError("%s: single-device sessions only" % what)
+
     def set_demod_all(self, on):
         """see Engine.set_demod_all (single-device sessions)"""
+        self._single_device("set_demod_all")
         _need(lib().dabhip_stream_set_demod_all(self._h, 1 if on else 0) == 0, "stream_set_demod_all")
 
     def msc_deferred(self):
         """TFs of the segment fed last whose MSC symbols were deferred by the lock-in skip (single-device sessions)."""
+        self._single_device("msc_deferred")
         n = lib().dabhip_stream_msc_deferred(self._h)
         _need(n >= 0, "stream_msc_deferred")
         return n
+
+    def set_launch_limits(self, **limits):
+        """see Engine.set_launch_limits (single-device sessions)"""
+        self._single_device("set_launch_limits")
+        _set_launch_limits(lib().dabhip_stream_set_launch_limits, self._h, limits)
+
+    def launch_report(self):
+        """The launches of the segment fed last, its device gathers included (see Engine.launch_report; single-device sessions)."""
+        self._single_device("launch_report")
+        return _launch_report(lib().dabhip_stream_launch_report, self._h)
 
     def log(self, stream):
         """The reference's operator messages for one stream since the last call (dabhip_stream_log): 'Locked', 'Lock lost, resetting ringbuffer', ensemble dump."""

@@ -373,6 +373,34 @@ int dabhip_engine_set_guard_list_cap(dabhip_engine* e, uint32_t cap)
   for (auto& l : e->lanes) l->set_guard_list_cap(cap);
   return 0;
 }
+static void report_to_words(const LaunchReport& r, int64_t* out, int cap)
+{
+  const int64_t v[kLaunchReportCount] = {r.decoder, r.regroup, r.fic_group, r.gather, r.ofdm_chunks, r.fic_prepass, r.fetch_form, r.fetches, r.gather_calls, r.decoder_planned};
+  for (int i = 0; i < cap && i < kLaunchReportCount; ++i) out[i] = v[i];
+}
+int dabhip_engine_set_launch_limits(dabhip_engine* e, const int64_t* limits, int n)
+{
+  if (!e || !limits || n != kLaunchLimitCount) { set_error("set_launch_limits: bad argument"); return -1; }
+  LaunchLimits probe;
+  if (const char* wrong = launch_limits_from(limits, &probe)) { set_error(std::string("set_launch_limits: ") + wrong); return -1; }   // (all lanes or none)
+  for (auto& l : e->lanes)
+    if (!l->set_launch_limits(limits)) return -1;
+  return 0;
+}
+int dabhip_engine_launch_report(const dabhip_engine* e, int64_t* out, int cap)
+{
+  if (!e || !out || cap < 0) { set_error("launch_report: bad argument"); return -1; }
+  if (e->lanes.size() != 1) { set_error("launch_report: one lane only (DABHIP_LANES unset)"); return -1; }
+  report_to_words(e->lanes[0]->launch_report(), out, cap);
+  return std::min(cap, kLaunchReportCount);
+}
+int dabhip_engine_msc_plan(const dabhip_engine* e, int32_t* nsteps, int cap, int64_t* ntiles)
+{
+  if (!e || cap < 0) { set_error("msc_plan: bad argument"); return -1; }
+  if (e->lanes.size() != 1) { set_error("msc_plan: one lane only (DABHIP_LANES unset)"); return -1; }
+  return e->lanes[0]->msc_plan(nsteps, cap, ntiles);
+}
+int dabhip_host_stream_state_bytes(void) { return static_cast<int>(sizeof(StreamState)); }
 int dabhip_engine_set_fused(dabhip_engine* e, int enable)
 {
   if (!e) return -1;
@@ -611,6 +639,17 @@ int dabhip_dab_decoder_forms(const dabhip_dab* d, uint32_t* msc_mask, uint32_t* 
   if (fic_mask) *fic_mask = d->eng.fic_forms_ran();
   return 0;
 }
+int dabhip_dab_set_launch_limits(dabhip_dab* d, const int64_t* limits, int n)
+{
+  if (!d || !limits || n != kLaunchLimitCount) { set_error("dab_set_launch_limits: bad argument"); return -1; }
+  return d->eng.set_launch_limits(limits) ? 0 : -1;
+}
+int dabhip_dab_launch_report(const dabhip_dab* d, int64_t* out, int cap)
+{
+  if (!d || !out || cap < 0) { set_error("dab_launch_report: bad argument"); return -1; }
+  report_to_words(d->eng.launch_report(), out, cap);
+  return std::min(cap, kLaunchReportCount);
+}
 int dabhip_dab_last_fibs(const dabhip_dab* d, uint8_t* fibs, uint8_t* crc_ok)
 {
   if (!d || !fibs || !crc_ok) return -1;
@@ -623,6 +662,7 @@ int dabhip_dab_process_frame(dabhip_dab* d)
 {
   if (!d) { set_error("dab_process_frame: null handle"); return -1; }
   d->eng.clear_forms_ran();
+  d->eng.clear_launch_report();
   if (d->slot == kDabSlots) {        // keep the 4 most recent TFs (16 CIFs of interleaver history)
     if (!d->eng.recycle_tf_slots(kDabSlots, 4)) return -1;
     d->plane.rebase(4 * (kDabSlots - 4));
@@ -821,6 +861,13 @@ struct dabhip_stream {
   uint64_t fed = 0, queued = 0;                // segments fed / handed over (fed <= queued <= fed + 2)
   bool queued_ever = false;                    // dabhip_stream_prefetch has been used: its stream has work to forget (reap_stream)
   uint32_t up_uses = 0;
+  // device-gather launches and the gathers they belong to: counted since the last feed returned, reported for the segment fed last (launch_limits.hpp)
+  int64_t gather_launches = 0, gather_calls = 0, fed_gather_launches = 0, fed_gather_calls = 0;
+  bool device_gather(const CopyDesc* descs, int count, uint32_t longest, hipStream_t st)
+  {
+    ++gather_calls;
+    return launch_device_gather(descs, count, longest, st, eng.launch_limits().gather_descs, &gather_launches) == hipSuccess;
+  }
   // A feed that fails after it has started to move the session on (windows, offsets, the engine's carried state) leaves a session nobody can
   // re-feed correctly: it is marked and refuses everything but its destruction -- an honest error instead of frames decoded at the wrong offsets.
   bool failed = false;
@@ -903,7 +950,7 @@ struct dabhip_stream {
       longest = std::max(longest, static_cast<uint32_t>(nbytes[b]));
     }
     if (descs.empty()) return true;
-    return d_gather_descs[w].upload(descs, st) && launch_device_gather(d_gather_descs[w].get(), static_cast<int>(descs.size()), longest, st) == hipSuccess;
+    return d_gather_descs[w].upload(descs, st) && device_gather(d_gather_descs[w].get(), static_cast<int>(descs.size()), longest, st);
   }
   HostList<CopyDesc> history_descs;            // the bytes of earlier segments moved in front of the segment being fed (dabhip_stream_feed)
   DeviceBuffer<CopyDesc> d_history_descs;
@@ -954,6 +1001,20 @@ extern "C" int dabhip_stream_set_parity_guard(dabhip_stream* s, int on) { if (!s
 extern "C" int dabhip_stream_set_sync_speculation(dabhip_stream* s, int mode) { if (!s) return -1; s->eng.set_sync_speculation(mode); return 0; }
 extern "C" int dabhip_stream_set_demod_all(dabhip_stream* s, int on) { if (!s) return -1; s->eng.set_demod_all(on != 0); return 0; }
 extern "C" int dabhip_stream_msc_deferred(const dabhip_stream* s) { return s ? s->eng.msc_deferred() : -1; }
+extern "C" int dabhip_stream_set_launch_limits(dabhip_stream* s, const int64_t* limits, int n)
+{
+  if (!s || !limits || n != kLaunchLimitCount) { set_error("stream_set_launch_limits: bad argument"); return -1; }
+  return s->eng.set_launch_limits(limits) ? 0 : -1;
+}
+extern "C" int dabhip_stream_launch_report(const dabhip_stream* s, int64_t* out, int cap)
+{
+  if (!s || !out || cap < 0) { set_error("stream_launch_report: bad argument"); return -1; }
+  LaunchReport r = s->eng.launch_report();
+  r.gather = s->fed_gather_launches;
+  r.gather_calls = s->fed_gather_calls;
+  report_to_words(r, out, cap);
+  return std::min(cap, kLaunchReportCount);
+}
 extern "C" int dabhip_stream_set_soft(dabhip_stream* s, int on)
 {
   if (!s) return -1;
@@ -1040,9 +1101,12 @@ extern "C" int64_t dabhip_stream_feed(dabhip_stream* s, const uint8_t* const* iq
     avail[b] = static_cast<size_t>(s->avail[b]);
   }
   if (!moves.empty() && !(s->d_history_descs.upload(moves, st) &&
-                          launch_device_gather(s->d_history_descs.get(), static_cast<int>(moves.size()), longest_move, st) == hipSuccess))
+                          s->device_gather(s->d_history_descs.get(), static_cast<int>(moves.size()), longest_move, st)))
     return broken("stream_feed: window move failed");
   ++s->fed;
+  s->fed_gather_launches = s->gather_launches;
+  s->fed_gather_calls = s->gather_calls;
+  s->gather_launches = s->gather_calls = 0;
   const int64_t frames = s->eng.feed(virt.data(), avail.data(), s->n, s->first);
   if (frames < 0) return broken(nullptr);        // (the engine's error text stands)
   // the prefetch stream is only ever waited for through events (engine.hpp: blocking_copy): every 32nd segment, wait for the stream itself -- at

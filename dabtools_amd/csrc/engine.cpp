@@ -137,6 +137,18 @@ bool Engine::set_decoder_forms(int msc_form, int fic_form)
   return true;
 }
 
+bool Engine::set_launch_limits(const int64_t* v)
+{
+  LaunchLimits l;
+  const char* const wrong = v ? launch_limits_from(v, &l) : "null argument";
+  if (wrong) {
+    set_error(std::string("set_launch_limits: ") + wrong);
+    return false;
+  }
+  limits_ = l;
+  return true;
+}
+
 Engine::~Engine()
 {
   if (d2h_stream_) { (void)hipStreamSynchronize(d2h_stream_); (void)hipStreamDestroy(d2h_stream_); }
@@ -267,7 +279,7 @@ bool Engine::stage_a(DecodeRun& run)
   if (heavy_mu_ && !run.heavy.owns_lock()) run.heavy = std::unique_lock<std::mutex>(*heavy_mu_);
   const bool guard = guard_active(), soft = soft_bits_ != 0;
   const bool energies = guard || soft;                    // the per-symbol sample energies: the guard's error bounds, the soft scale
-  const int chunk = run.chunk = fused_ ? std::max(ntf, 1) : std::min(ntf, kFftChunkTfs);   // only the spectra buffer of the two-kernel stage calls for chunks
+  const int chunk = run.chunk = fused_ ? std::max(ntf, 1) : std::min(ntf, limits_.fft_chunk_tfs);   // only the spectra buffer of the two-kernel stage calls for chunks
   if (!fused_ && !d_spectra_.reserve(static_cast<size_t>(chunk) * kSymbolsPerTf * 2048)) return false;
   if (!h_fibs_.resize(static_cast<size_t>(nslots) * 384) || !h_fib_ok_.resize(static_cast<size_t>(nslots) * 12)) return false;
   if (!record(ev_[3], stream_)) return false;
@@ -277,8 +289,10 @@ bool Engine::stage_a(DecodeRun& run)
     for (int first = 0; first < ntf; first += chunk)
       if (!fused_parts(first, std::min(chunk, ntf - first), 1, 4, 1)) return false;      // the three FIC symbols (and symbol 0, their reference)
   } else {
-    for (int first = 0; first < ntf; first += chunk * 19) {       // 4 of 76 symbols: 19 x as many TFs fit the spectra buffer
-      const int n = std::min(chunk * 19, ntf - first);
+    const Pieces cut{ntf, int64_t(chunk) * 19};                   // 4 of 76 symbols: 19 x as many TFs fit the spectra buffer
+    for (int64_t p = 0; p < cut.count(); ++p) {
+      const int first = static_cast<int>(cut.first(p)), n = static_cast<int>(cut.size(p));
+      ++report_.fic_prepass;
       GuardArgs ga = soft ? soft_guard_args() : GuardArgs{};   // (hard decisions: a non-null delta switches the guard's listing on)
       if (guard && !guard_begin(n, &ga)) return false;
       if (energies && !check(launch_symbol_delta(frame_list(), first, n, 4, d_delta_.get(), kSymbolsPerTf, soft ? kSoftNormC : guard_c_of(guard_rule_level()), stream_), "symbol delta launch"))
@@ -347,6 +361,7 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
   guard_new_count();
   guard_decisions_ = 0;
   guard_overflows_ = 0;
+  report_ = LaunchReport{};
   last_.pending = false;                     // the scan overwrites the descriptors the deferred frames of the last decode would be completed from
   last_.deferred = 0;
   layout_ms_ = 0;

@@ -27,6 +27,7 @@
 #include "control_plane.hpp"
 #include "decoder_form.hpp"
 #include "device_types.hpp"
+#include "launch_limits.hpp"
 #include "scan_plan.hpp"
 #include "segment_layout.hpp"
 #include "thread_pool.hpp"
@@ -235,6 +236,21 @@ class Engine {
   void guard_stats(int64_t* flagged, int64_t* decisions) const { if (flagged) *flagged = guard_flagged_; if (decisions) *decisions = guard_decisions_; }
   int guard_overflows() const { return guard_overflows_; }
   void set_guard_list_cap(uint32_t cap) { guard_cap_override_ = cap; }   // test knob: a tiny list makes the overflow path run
+  // test knob (launch_limits.hpp): v[0 .. kLaunchLimitCount), 0 = the default.  False, with the limits as they were, for a value no launch could be made with
+  bool set_launch_limits(const int64_t* v);
+  const LaunchLimits& launch_limits() const { return limits_; }
+  // the launches of the last decode / segment / stage entry, loop by loop (the session's device gathers: dabhip_stream_launch_report adds them)
+  const LaunchReport& launch_report() const { return report_; }
+  void clear_launch_report() { report_ = LaunchReport{}; }
+  // the MSC batch of the last decode as the host planned it: trellis steps of every wave-group in launch order (at most cap), tiles of 64 records; returns the groups
+  int msc_plan(int32_t* nsteps, int cap, int64_t* ntiles) const
+  {
+    const DecodeBatch& b = work_.batch;
+    if (ntiles) *ntiles = work_.nframes ? static_cast<int64_t>(b.job_ids.size() / 64) : 0;
+    if (work_.nframes == 0) return 0;
+    for (size_t g = 0; nsteps && g < b.groups.size() && static_cast<int>(g) < cap; ++g) nsteps[g] = b.groups[g].nsteps;
+    return static_cast<int>(b.groups.size());
+  }
 
   // -- batch path ---------------------------------------------------------------------------
   int64_t decode(const uint8_t* const* iq, const size_t* nbytes, int nstreams, bool on_device);
@@ -479,6 +495,8 @@ class Engine {
   int guard_launches_ = 0;
   bool guard_counters_clear_ = false;   // the layout kernel of this decode has cleared the device counters
   uint32_t guard_cap_ = 0, guard_cap_override_ = 0;
+  LaunchLimits limits_;
+  LaunchReport report_;
   std::vector<uint32_t> guard_caps_;   // per guarded launch of the decode: the list capacity it ran with
   int64_t guard_flagged_ = 0, guard_decisions_ = 0;
   int guard_overflows_ = 0;          // launches of the last decode whose list overflowed (decided again in full, fp64)

@@ -12,7 +12,6 @@
 
 namespace dabhip {
 
-constexpr int kFftChunkTfs = 4096;                        // spectra buffer: 4096 TF x 1.19 MiB = 4.75 GiB (measured: 1024 -> 4096 shortens K2 by 5 %, launch tails)
 constexpr int kFicWords = kFicBits / 32;                  // 288
 constexpr int kMscWords = kMscBits / 32;                  // 6912
 constexpr int kCifWords = kCifBits / 32;                  // 1728 words per (logical) CIF row

@@ -4,8 +4,6 @@
 namespace dabhip {
 
 namespace {
-constexpr int64_t kMaxDecisionRows = int64_t(48) << 20;   // x 512 B = 24 GiB of survivor decisions per launch
-
 void unpack_bits(const uint32_t* words, int nbits, uint8_t* bytes)
 {
   for (int i = 0; i < nbits; ++i) bytes[i] = static_cast<uint8_t>((words[i >> 5] >> (i & 31)) & 1u);
@@ -65,16 +63,18 @@ bool Engine::launch_decode_batch(const DecodeBatch& b, const uint32_t* bits, con
   const int row_words = kCifWords * (soft_bits_ ? 4 : 1);
   const int ntiles = static_cast<int>(b.job_ids.size() / 64);
   if (!record(ev_msc_[0], stream_)) return false;
-  if (!check(launch_regroup(soft_bits_, ids, ntiles, d_jobs_.get(), d_stream_cif_base, bits, d_grouped_.get(), stream_), "regroup launch")) return false;
+  if (!check(launch_regroup(soft_bits_, ids, ntiles, d_jobs_.get(), d_stream_cif_base, bits, d_grouped_.get(), stream_, limits_.regroup_tiles, &report_.regroup), "regroup launch")) return false;
   if (!record(ev_msc_[1], stream_)) return false;
   // the form the knobs' rule or set_decoder_forms picks (decoder_form.hpp), slice by slice (a small batch -- one wave per code word, all lengths longest
   // first, its decisions in the survivor-record buffer -- is one slice: worklist.hpp)
   const int form = msc_form(knobs_, msc_form_, soft_bits_ != 0, b.wave_form, static_cast<int>(b.groups.size()));
   msc_ran_ |= 1u << form;
+  report_.decoder_planned = static_cast<int64_t>(b.slice_start.size()) - 1;
   for (size_t sl = 0; sl + 1 < b.slice_start.size(); ++sl) {
     const int g0 = b.slice_start[sl];
     const ViterbiLaunch v{d_groups_.get() + g0, b.slice_start[sl + 1] - g0, ids, d_plans_.get(), d_grouped_.get(), row_words, d_decisions_.get(), prbs, out, record_stride};
     if (!check(launch_viterbi_form(form, soft_bits_, v, stream_), "viterbi launch")) return false;
+    ++report_.decoder;
   }
   if (!record(ev_msc_[2], stream_)) return false;
   return true;
@@ -231,7 +231,7 @@ bool Engine::fic_decode_slots_async(int first, int n, uint8_t* fibs_host, uint8_
                                   {ids.data(), d_job_ids_.get(), ids.size() * sizeof(int), false}};
     if (!upload_small(items, 3, ks, h_small_fic_)) return false;
   }
-  if (!check(launch_fic_group(d_fic_bits_.get(), 4 * first, nblocks, block_words, d_grouped_.get(), ks), "fic group launch") ||
+  if (!check(launch_fic_group(d_fic_bits_.get(), 4 * first, nblocks, block_words, d_grouped_.get(), ks, limits_.fic_group_tiles, &report_.fic_group), "fic group launch") ||
       !check(launch_viterbi_form(form, soft_bits_, ViterbiLaunch{d_groups_.get(), ntiles, d_job_ids_.get(), d_plans_.get(), d_grouped_.get(), block_words,
                                                                  d_decisions_.get(), d_prbs_.get(), d_fibs_.get(), 96}, ks),
              "fic viterbi launch"))
@@ -256,7 +256,7 @@ bool Engine::msc_prepare(const std::vector<const JobList*>& stream_jobs, const s
   const auto t_in = std::chrono::steady_clock::now();
   auto mark = [&](const char* what) { host_mark("[host]   msc_prepare %-14s %8.3f ms\n", what, t_in); };
   std::string error;
-  if (prepare_msc_work(plan_table_, *pool_, stream_jobs, planes, stream_row_base, stream_fib_base, kMaxDecisionRows, out, &error, mark, msc_wave_max(knobs_, msc_form_)))
+  if (prepare_msc_work(plan_table_, *pool_, stream_jobs, planes, stream_row_base, stream_fib_base, limits_.decision_rows, out, &error, mark, msc_wave_max(knobs_, msc_form_)))
     return true;
   set_error(error);
   return false;

@@ -41,7 +41,7 @@ bool Engine::guard_begin(int ntf_in_launch, GuardArgs* out)
 // the counters' host and device arrays for a decode of ntf frames (the layout kernel clears the device side)
 bool Engine::guard_reserve_counters(int ntf)
 {
-  const size_t words = (static_cast<size_t>(kGuardMinLaunches) + 2 * static_cast<size_t>(ntf / kFftChunkTfs + 1)) * kGuardSlotWords;
+  const size_t words = (static_cast<size_t>(kGuardMinLaunches) + 2 * static_cast<size_t>(ntf / limits_.fft_chunk_tfs + 1)) * kGuardSlotWords;
   return (h_guard_counts_.size() >= words || h_guard_counts_.resize(words)) && d_guard_counter_.reserve(h_guard_counts_.size());
 }
 bool Engine::guard_finish(bool planar, int first, int n, int sym_a, int sym_b, bool skip_fic)
@@ -120,8 +120,10 @@ bool Engine::ofdm_msc_part(int first, int n, int chunk, int ev_base)
 {
   const bool guard = guard_active(), soft = soft_bits_ != 0, energies = guard || soft;
   bool gpu_ok = true;
-  for (int c = 0; c * chunk < n && gpu_ok; ++c) {
-    const int f0 = first + c * chunk, nf = std::min(chunk, n - c * chunk);
+  const Pieces cut{n, chunk};
+  for (int c = 0; c < cut.count() && gpu_ok; ++c) {
+    const int f0 = first + static_cast<int>(cut.first(c)), nf = static_cast<int>(cut.size(c));
+    ++report_.ofdm_chunks;
     Event* const ev = ev_base >= 0 ? &chunk_ev_[static_cast<size_t>(3) * (ev_base + c)] : nullptr;
     gpu_ok = !ev || record(ev[0], stream_);
     if (fused_) {

@@ -233,7 +233,9 @@ bool Engine::scan_fetch()
   StreamState* const states = h_states_.data();
   // Small scans: the four downloads as ONE kernel that writes the page-locked host arrays itself (launch_host_words works in either direction: both
   // sides are addresses the device can reach) instead of four copy-engine commands in a row, each some microseconds of the host waiting.
-  if (p.result_words <= (size_t(1) << 18)) {
+  ++report_.fetches;
+  report_.fetch_form = p.result_words <= static_cast<size_t>(limits_.fetch_words) ? kFetchKernel : kFetchCopyEngine;
+  if (report_.fetch_form == kFetchKernel) {
     HostWordsArgs hw{};
     int k = 0;
     auto add = [&](const void* src, void* dst, size_t n) { hw.set(k++, src, dst, n); };

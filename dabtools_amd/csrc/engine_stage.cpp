@@ -36,21 +36,22 @@ void pack_bits(const uint8_t* bytes, int nbits, uint32_t* words)
 }  // namespace
 
 // K2 (ofdm_fft_kernel) alone over the frames of the last decode: the same IQ, the same frame list and the same launch
-// shape (chunks of kFftChunkTfs) as the two-kernel OFDM stage, whatever stage the decode itself used.  This is the
+// shape (chunks of LaunchLimits::fft_chunk_tfs) as the two-kernel OFDM stage, whatever stage the decode itself used.  This is the
 // HBM-roofline measurement of SURVEY.md 8(d): 311,296 B read + 1,245,184 B written per TF.
 int Engine::fft_roofline(int reps, int64_t* launches, int64_t* tfs, double* ms)
 {
   if (!ok_) { set_error("engine not initialised (no GPU?)"); return -1; }
   if (seg_.ntf <= 0) { set_error("fft_roofline: no decode to measure on"); return -1; }
   if (!check(hipSetDevice(device_), "hipSetDevice")) return -1;
-  const int ntf = seg_.ntf, chunk = std::min(ntf, kFftChunkTfs);
+  const int ntf = seg_.ntf, chunk = std::min(ntf, limits_.fft_chunk_tfs);      // (the launch report stays that of the decode: this entry returns its own count)
   if (!d_spectra_.reserve(static_cast<size_t>(chunk) * kSymbolsPerTf * 2048)) return -1;
   reps = std::max(reps, 1);
   int64_t nl = 0, nt = 0;
   double total = 0;
   for (int r = -1; r < reps; ++r) {                      // r = -1: untimed
-    for (int first = 0; first < ntf; first += chunk) {
-      const int n = std::min(chunk, ntf - first);
+    const Pieces cut{ntf, chunk};
+    for (int64_t p = 0; p < cut.count(); ++p) {
+      const int first = static_cast<int>(cut.first(p)), n = static_cast<int>(cut.size(p));
       if (!record(ev_[0], stream_)) return -1;
       if (!check(launch_ofdm_fft(frame_list(), first, n, d_spectra_.get(), stream_), "fft launch")) return -1;
       if (!record(ev_[1], stream_)) return -1;
@@ -118,6 +119,7 @@ int Engine::stage_demap(const float* spectra, int nframes, uint8_t* fic, uint8_t
 int Engine::stage_fic_decode(const uint8_t* fic, int nframes, uint8_t* fibs, uint8_t* crc_ok)
 {
   clear_forms_ran();
+  report_ = LaunchReport{};
   if (!hard_only("stage_fic_decode")) return -1;
   if (!ok_) { set_error("engine not initialised (no GPU?)"); return -1; }
   if (nframes <= 0) return 0;
@@ -145,12 +147,15 @@ int Engine::stage_decision_audit(const uint8_t* frames, int nframes, bool on_dev
   if (fused) return stage_decision_audit_fused(frames, nframes, on_device, guard_on, out8, out_extra);
   DeviceBuffer<uint8_t> d_out;
   if (!d_out.reserve(sizeof(AuditOut)) || !check(hipMemsetAsync(d_out.get(), 0, sizeof(AuditOut), stream_), "audit memset")) return -1;
-  const int chunk = 256;
+  const int chunk = std::min(256, limits_.fft_chunk_tfs);      // (its own spectra buffer: never more than the decode's chunk)
   uint64_t listed = 0;
   const uint8_t* const d_in = frames_on_device(frames, nframes, on_device);
   if (!d_in) return -1;
-  for (int first = 0; first < nframes; first += chunk) {
-    const int n = std::min(chunk, nframes - first);
+  report_ = LaunchReport{};
+  const Pieces cut{nframes, chunk};
+  for (int64_t p = 0; p < cut.count(); ++p) {
+    const int first = static_cast<int>(cut.first(p)), n = static_cast<int>(cut.size(p));
+    ++report_.ofdm_chunks;
     const std::vector<CallDesc> descs = contiguous_descs(first, n);
     if (!set_frame_list(d_in, descs.data(), n, 0, true) || !d_spectra_.reserve(static_cast<size_t>(n) * kSymbolsPerTf * 2048)) return -1;
     GuardArgs ga{};

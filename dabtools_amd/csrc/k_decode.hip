@@ -1032,12 +1032,16 @@ hipError_t launch_host_gather(const CopyDesc* descs, int n, int workgroups, hipS
   return hipGetLastError();
 }
 
-hipError_t launch_device_gather(const CopyDesc* descs, int n, uint32_t max_bytes, hipStream_t stream)
+hipError_t launch_device_gather(const CopyDesc* descs, int n, uint32_t max_bytes, hipStream_t stream, int max_descs, int64_t* launches)
 {
   if (n <= 0) return hipSuccess;
+  if (max_descs < 1 || max_descs > kMaxGatherDescs) return hipErrorInvalidValue;      // (grid.y holds 65,535 descriptors)
   const uint32_t pieces = static_cast<uint32_t>((static_cast<uint64_t>(max_bytes) + (64u << 10) - 1) >> 16);   // (no wrap for sizes close to 2^32)
-  for (int i = 0; i < n; i += 65535)          // (grid.y holds 65,535 descriptors)
-    hipLaunchKernelGGL(device_gather_kernel, dim3(std::max(1u, std::min(pieces, 64u)), std::min(n - i, 65535)), dim3(256), 0, stream, descs + i);
+  const Pieces cut{n, max_descs};
+  for (int64_t p = 0; p < cut.count(); ++p) {
+    hipLaunchKernelGGL(device_gather_kernel, dim3(std::max(1u, std::min(pieces, 64u)), static_cast<uint32_t>(cut.size(p))), dim3(256), 0, stream, descs + cut.first(p));
+    if (launches) ++*launches;
+  }
   return hipGetLastError();
 }
 
@@ -1058,28 +1062,35 @@ hipError_t launch_viterbi(const WaveGroup* groups, int ngroups, const int* job_i
 }
 
 hipError_t launch_regroup(int soft_bits, const int* job_ids, int ntiles, const DecodeJob* jobs, const int* stream_cif_base,
-                          const uint32_t* rows, uint32_t* grouped, hipStream_t stream)
+                          const uint32_t* rows, uint32_t* grouped, hipStream_t stream, int max_tiles, int64_t* launches)
 {
   if (ntiles <= 0) return hipSuccess;
+  if (max_tiles < 8 || max_tiles % 8 != 0) return hipErrorInvalidValue;      // tiles in eights (see the kernel)
   const int bits = soft_bits ? 4 : 1;
-  for (int t0 = 0; t0 < ntiles; t0 += 32768) {
-    const int nt = min(32768, ntiles - t0);
+  const Pieces cut{ntiles, max_tiles};
+  for (int64_t p = 0; p < cut.count(); ++p) {
+    const int t0 = static_cast<int>(cut.first(p)), nt = static_cast<int>(cut.size(p));
     const dim3 grid(((27 * bits + 3) / 4) * 8 * ((nt + 7) / 8));   // 108 x bits plane words, 16 per workgroup; tiles in eights (see the kernel)
     uint32_t* dst = grouped + static_cast<size_t>(t0) * 1728 * bits * 64;
     if (soft_bits) hipLaunchKernelGGL(regroup_kernel<4>, grid, dim3(256), 0, stream, job_ids + static_cast<size_t>(t0) * 64, jobs, stream_cif_base, rows, dst, nt);
     else hipLaunchKernelGGL(regroup_kernel<1>, grid, dim3(256), 0, stream, job_ids + static_cast<size_t>(t0) * 64, jobs, stream_cif_base, rows, dst, nt);
+    if (launches) ++*launches;
   }
   return hipGetLastError();
 }
 
-hipError_t launch_fic_group(const uint32_t* fic_rows, int first_block, int nblocks, int block_words, uint32_t* grouped, hipStream_t stream)
+hipError_t launch_fic_group(const uint32_t* fic_rows, int first_block, int nblocks, int block_words, uint32_t* grouped, hipStream_t stream, int max_tiles,
+                            int64_t* launches)
 {
   if (nblocks <= 0) return hipSuccess;
+  if (max_tiles < 1 || max_tiles > kMaxGridY) return hipErrorInvalidValue;
   const int ntiles = (nblocks + 63) / 64;
-  for (int t0 = 0; t0 < ntiles; t0 += 32768) {
-    const int nt = min(32768, ntiles - t0);
+  const Pieces cut{ntiles, max_tiles};
+  for (int64_t p = 0; p < cut.count(); ++p) {
+    const int t0 = static_cast<int>(cut.first(p)), nt = static_cast<int>(cut.size(p));
     hipLaunchKernelGGL(fic_group_kernel, dim3(8, nt), dim3(256), 0, stream, fic_rows, first_block + t0 * 64, nblocks - t0 * 64, block_words,
                        grouped + static_cast<size_t>(t0) * block_words * 64);
+    if (launches) ++*launches;
   }
   return hipGetLastError();
 }

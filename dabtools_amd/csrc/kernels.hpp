@@ -9,6 +9,7 @@
 
 #include "dabplus.hpp"
 #include "device_types.hpp"
+#include "launch_limits.hpp"
 
 namespace dabhip {
 
@@ -131,9 +132,11 @@ hipError_t launch_viterbi(const WaveGroup* groups, int ngroups, const int* job_i
 
 // K3/K4: lane-interleave the received rows 64 records at a time (soft_bits: 0 = hard bits, 4 = 4-bit soft values),
 // then Viterbi with fused de-puncturing
+// (max_tiles: tiles per launch, launch_limits.hpp -- a multiple of 8 for the regroup; launches: counts the launches made, when not null)
 hipError_t launch_regroup(int soft_bits, const int* job_ids, int ntiles, const DecodeJob* jobs, const int* stream_cif_base,
-                          const uint32_t* rows, uint32_t* grouped, hipStream_t stream);
-hipError_t launch_fic_group(const uint32_t* fic_rows, int first_block, int nblocks, int block_words, uint32_t* grouped, hipStream_t stream);
+                          const uint32_t* rows, uint32_t* grouped, hipStream_t stream, int max_tiles = kMaxRegroupTiles, int64_t* launches = nullptr);
+hipError_t launch_fic_group(const uint32_t* fic_rows, int first_block, int nblocks, int block_words, uint32_t* grouped, hipStream_t stream,
+                            int max_tiles = kMaxFicGroupTiles, int64_t* launches = nullptr);
 // One launch of the decoder over ngroups wave-groups (worklist.hpp), whatever its form: rows of row_words words per record in `grouped`, survivor
 // records in `decisions`, decoded bytes de-scrambled with prbs_words into out + record * record_stride.
 struct ViterbiLaunch {
@@ -172,8 +175,8 @@ hipError_t launch_decision_audit(const uint8_t* frames_iq, int nframes, const fl
 hipError_t launch_batched_copy(const CopyDesc* descs, int n, hipStream_t stream);
 // the descriptors' sources may be page-locked HOST memory (read over PCIe by a small persistent grid); nbytes < 4 GiB each
 hipError_t launch_host_gather(const CopyDesc* descs, int n, int workgroups, hipStream_t stream);
-// n copies inside the device in one launch, any alignment; max_bytes = the longest of them
-hipError_t launch_device_gather(const CopyDesc* descs, int n, uint32_t max_bytes, hipStream_t stream);
+// n copies inside the device in one launch per max_descs of them (at most 65535: grid.y), any alignment; max_bytes = the longest of them
+hipError_t launch_device_gather(const CopyDesc* descs, int n, uint32_t max_bytes, hipStream_t stream, int max_descs = kMaxGatherDescs, int64_t* launches = nullptr);
 hipError_t launch_fib_crc(const uint8_t* fibs, int nfib, const uint16_t* crc_tab, uint8_t* ok, hipStream_t stream);
 
 // K5: ETI header/FIB copy, EOF CRC, trailer

@@ -97,6 +97,9 @@ int dabhip_dab_set_soft(dabhip_dab *d, int enable);
 /* Decoder forms of this seam (dabhip_engine_set_decoder_forms, DABHIP_FORM_*; any time); the report covers the last dabhip_dab_process_frame. */
 int dabhip_dab_set_decoder_forms(dabhip_dab *d, int msc_form, int fic_form);
 int dabhip_dab_decoder_forms(const dabhip_dab *d, uint32_t *msc_mask, uint32_t *fic_mask);
+/* launch limits and the last process_frame's launches: see dabhip_engine_set_launch_limits */
+int dabhip_dab_set_launch_limits(dabhip_dab *d, const int64_t *limits, int n);
+int dabhip_dab_launch_report(const dabhip_dab *d, int64_t *out, int cap);
 /* FIBs (12 x 32 bytes) and CRC flags (12) of the TF processed last (struct tf_fibs_t, dab.h:21-25). */
 int dabhip_dab_last_fibs(const dabhip_dab *d, uint8_t *fibs, uint8_t *crc_ok);
 
@@ -218,6 +221,45 @@ int dabhip_engine_guard_stats(const dabhip_engine *e, int64_t *flagged, int64_t 
 int dabhip_engine_guard_overflows(const dabhip_engine *e);
 int dabhip_engine_set_guard_list_cap(dabhip_engine *e, uint32_t cap);
 
+/* Launch limits (test knob, per engine).  A decode larger than one launch can hold is split: the MSC decoder into slices by survivor-record rows, the
+ * regroup and the FIC group by tiles of 64 records, a session's device gather by descriptors, the two-kernel OFDM stage into chunks of transmission frames
+ * (its FIC pre-pass: 19 x as many); and scan results of more than a number of 32-bit words come back by copy-engine commands instead of one kernel.  No
+ * test-sized input reaches the defaults, so the limits can be lowered: limits[0 .. DABHIP_LAUNCH_LIMITS) in the order of the DABHIP_LIMIT_* indices, 0 = the
+ * default (48 << 20 rows, 32768 tiles, 32768 tiles, 65535 descriptors, 1 << 18 words, 4096 frames).  The output does not depend on them.  Refused (-1, the
+ * limits stay as they were): a negative value, a regroup limit that is not a multiple of 8 or above 32768, a FIC-group or device-gather limit above 65535,
+ * an OFDM chunk above 1 << 20.
+ * dabhip_*_launch_report: what the last decode / segment / stage entry / process_frame did -- out[DABHIP_REPORT_*], at most cap values; returns their number.
+ * DABHIP_REPORT_FETCH_FORM: 0 = no scan ran, 1 = one kernel, 2 = copy-engine commands.  A session counts the device gathers since the previous feed returned.
+ * The counts are launches MADE: when a stream breaks the split scan's assumption and is scanned again, the frames are laid out and stage A runs a second
+ * time, so DABHIP_REPORT_FIC_PREPASS (two-kernel stage) is twice the pieces of the final frame list and DABHIP_REPORT_FETCHES is 2; dabhip_engine_demapped_tf
+ * completing deferred frames adds its launches to DABHIP_REPORT_OFDM_CHUNKS.  DABHIP_REPORT_DECODER_PLANNED: the slices the host's plan of the MSC batch
+ * holds; DABHIP_REPORT_DECODER (launches made) equals it. */
+#define DABHIP_LAUNCH_LIMITS 6
+#define DABHIP_LIMIT_DECISION_ROWS 0
+#define DABHIP_LIMIT_REGROUP_TILES 1
+#define DABHIP_LIMIT_FIC_GROUP_TILES 2
+#define DABHIP_LIMIT_GATHER_DESCS 3
+#define DABHIP_LIMIT_FETCH_WORDS 4
+#define DABHIP_LIMIT_FFT_CHUNK_TFS 5
+#define DABHIP_REPORT_VALUES 10
+#define DABHIP_REPORT_DECODER 0
+#define DABHIP_REPORT_REGROUP 1
+#define DABHIP_REPORT_FIC_GROUP 2
+#define DABHIP_REPORT_GATHER 3
+#define DABHIP_REPORT_OFDM_CHUNKS 4
+#define DABHIP_REPORT_FIC_PREPASS 5
+#define DABHIP_REPORT_FETCH_FORM 6
+#define DABHIP_REPORT_FETCHES 7
+#define DABHIP_REPORT_GATHER_CALLS 8
+#define DABHIP_REPORT_DECODER_PLANNED 9
+int dabhip_engine_set_launch_limits(dabhip_engine *e, const int64_t *limits, int n);
+int dabhip_engine_launch_report(const dabhip_engine *e, int64_t *out, int cap);
+/* The MSC batch of the last decode as the host planned it: the trellis steps of every wave-group of 64 code words in launch order (nsteps, at most cap
+ * values; a group takes ceil(steps / 8) * 8 survivor-record rows) and the tiles of 64 records the regroup covers.  Returns the number of groups. */
+int dabhip_engine_msc_plan(const dabhip_engine *e, int32_t *nsteps, int cap, int64_t *ntiles);
+/* sizeof the front end's per-stream state: a scan fetches nstreams * max_calls * 2 + nstreams + 1 + nstreams * this / 4 words at most */
+int dabhip_host_stream_state_bytes(void);
+
 /* Sub-channel filter (the reference's TODO.md:28-31, "save CPU time by not decoding data which will later be discarded"):
  * only the listed SubChIds (0..63) are decoded and carried; the ETI frames then list exactly those in their STC (NST, FL,
  * HCRC and EOF CRC follow; the FIC is passed on unchanged), each one's payload identical to the unfiltered frame's.
@@ -333,6 +375,9 @@ int dabhip_stream_set_parity_guard(dabhip_stream *s, int level);   /* see dabhip
 int dabhip_stream_set_sync_speculation(dabhip_stream *s, int mode);   /* default -1, see dabhip_engine_set_sync_speculation */
 int dabhip_stream_set_demod_all(dabhip_stream *s, int on);            /* see dabhip_engine_set_demod_all */
 int dabhip_stream_msc_deferred(const dabhip_stream *s);               /* TFs of the segment fed last whose MSC symbols were deferred */
+/* launch limits and the launches of the segment fed last (single-device sessions): see dabhip_engine_set_launch_limits */
+int dabhip_stream_set_launch_limits(dabhip_stream *s, const int64_t *limits, int n);
+int dabhip_stream_launch_report(const dabhip_stream *s, int64_t *out, int cap);
 /* ---- sessions over several devices of one node -----------------------------------------------------------------------
  * dab2eti.c:60-130,237 is a session on ONE device: calls arrive for ever from one demod thread.  B independent unbounded streams shard like a batch
  * does: the streams are dealt ONCE, at creation, to the listed devices in contiguous slices (the rule of dabhip_multi_plan: slice i of n takes

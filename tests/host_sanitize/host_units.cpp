@@ -5,6 +5,7 @@
 //                      uses them: a lane task that calls parallel_for while the posting thread waits; several engines' worth at once
 //   control_plane.hpp  FIG parse, lock rule, CIF ring, ETI headers over the FIBs of synthetic ensembles, streams in parallel
 //   worklist.hpp       frame records, header rows, wave-groups and slices of the MSC decode (with plain std::allocator lists)
+//   launch_limits.hpp  the cut of [0, n) into launches of at most `limit` that the launch loops share, and which limits are refused
 //   segment_layout.hpp the frame list, TF slots and logical CIF rows of random segments (with and without the lock-in skip, mis-numbered
 //                      ordinals under ASan) and the session carry over runs of segments, against a per-TF list kept here
 //   decoder_form.hpp   the decoder-form rule at both sides of every documented crossover, each knob's 0 / 1 / N reading, every forced form
@@ -29,6 +30,7 @@
 #include "../../dabtools_amd/csrc/control_plane.hpp"
 #include "../../dabtools_amd/csrc/decoder_form.hpp"
 #include "../../dabtools_amd/csrc/fifo_view.hpp"
+#include "../../dabtools_amd/csrc/launch_limits.hpp"
 #include "../../dabtools_amd/csrc/scan_plan.hpp"
 #include "../../dabtools_amd/csrc/segment_layout.hpp"
 #include "../../dabtools_amd/csrc/thread_pool.hpp"
@@ -245,8 +247,47 @@ static void control_and_worklist(int nstreams, int ntf, int64_t max_rows, unsign
   }
 }
 
+// Pieces: [0, n) in order, without gap or overlap, every piece but the last full, none empty -- at the sizes where a launch loop can go wrong
+static void launch_pieces(int64_t limit)
+{
+  for (int64_t n : {int64_t(0), int64_t(1), limit - 1, limit, limit + 1, 2 * limit + 3}) {
+    const Pieces cut{n, limit};
+    CHECK(cut.count() == (n + limit - 1) / limit);
+    int64_t at = 0;
+    for (int64_t i = 0; i < cut.count(); ++i) {
+      CHECK(cut.first(i) == at);
+      CHECK(cut.size(i) >= 1 && cut.size(i) <= limit);
+      CHECK(i + 1 == cut.count() || cut.size(i) == limit);
+      at += cut.size(i);
+    }
+    CHECK(at == n);
+  }
+}
+static void test_launch_limits()
+{
+  for (int64_t limit : {int64_t(1), int64_t(3), int64_t(8), int64_t(32768), int64_t(65535), kMaxDecisionRows}) launch_pieces(limit);
+  CHECK((Pieces{-5, 8}.count() == 0));
+  // the defaults are today's constants; 0 keeps a default; what no launch could be made with is refused and leaves *out alone
+  const int64_t zeros[kLaunchLimitCount] = {0, 0, 0, 0, 0, 0};
+  LaunchLimits l;
+  CHECK(launch_limits_from(zeros, &l) == nullptr);
+  CHECK(l.decision_rows == (int64_t(48) << 20) && l.regroup_tiles == 32768 && l.fic_group_tiles == 32768 && l.gather_descs == 65535 &&
+        l.fetch_words == (int64_t(1) << 18) && l.fft_chunk_tfs == 4096);
+  const int64_t low[kLaunchLimitCount] = {1, 8, 1, 3, 1, 5};
+  CHECK(launch_limits_from(low, &l) == nullptr);
+  CHECK(l.decision_rows == 1 && l.regroup_tiles == 8 && l.fic_group_tiles == 1 && l.gather_descs == 3 && l.fetch_words == 1 && l.fft_chunk_tfs == 5);
+  const LaunchLimits before = l;
+  const int64_t bad[][kLaunchLimitCount] = {{-1, 0, 0, 0, 0, 0}, {0, 12, 0, 0, 0, 0}, {0, 4, 0, 0, 0, 0}, {0, 32776, 0, 0, 0, 0}, {0, -8, 0, 0, 0, 0}, {0, 0, 65536, 0, 0, 0},
+                                            {0, 0, 0, 65536, 0, 0}, {0, 0, 0, -3, 0, 0}, {0, 0, 0, 0, -1, 0}, {0, 0, 0, 0, 0, -5}, {0, 0, 0, 0, 0, (int64_t(1) << 20) + 1}};
+  for (const auto& v : bad) {
+    CHECK(launch_limits_from(v, &l) != nullptr);
+    CHECK(std::memcmp(&l, &before, sizeof l) == 0);
+  }
+}
+
 static void test_control_and_worklist()
 {
+  test_launch_limits();
   control_and_worklist(24, 30, int64_t(48) << 20, 0);
   control_and_worklist(9, 22, 20000, 1);                 // a small record cap: many slices
   // several engines' host sides at once in one process (dabhip_multi: one lane + one pool per slice)

@@ -13,8 +13,8 @@ dabhip_engine_set_decoder_forms / dabhip_dab_set_decoder_forms and confirmed by 
 (d) the default rule picks the forms engine.hpp documents for the batch sizes README and DESIGN quote;
 (e) a multi-lane form asked of a soft-decision engine runs, and reports, the lane form.
 
-Not covered: a launch split into several slices (Engine::launch_decode_batch's slice_start), which happens only past kMaxDecisionRows
-(24 GiB of survivor records per launch) -- no test-sized batch gets there."""
+A launch split into several slices (Engine::launch_decode_batch's slice_start; by default only past 24 GiB of survivor records per launch) is held by
+tests/test_gpu_launch_splits.py, which lowers the row limit until every form runs in many slices."""
 import ctypes as C
 
 import numpy as np
