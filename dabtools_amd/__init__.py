@@ -115,6 +115,7 @@ _SIGNATURES = {
     "dabhip_multi_wall_ms": (C.c_float, [C.c_void_p, C.c_int]),
     "dabhip_multi_set_afc": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_multi_set_soft": (C.c_int, [C.c_void_p, C.c_int]),
+    "dabhip_multi_set_soft_lanes": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_multi_set_parity_guard": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_multi_set_fused": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_multi_set_subchannels": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
@@ -125,6 +126,7 @@ _SIGNATURES = {
     "dabhip_engine_eti_device_ptr": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_int64)]),
     "dabhip_engine_set_afc": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_engine_set_soft": (C.c_int, [C.c_void_p, C.c_int]),
+    "dabhip_engine_set_soft_lanes": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_engine_trace": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int]),
     "dabhip_engine_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
     "dabhip_engine_fft_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
@@ -160,6 +162,7 @@ _SIGNATURES = {
     "dabhip_multi_stream_eti_fetch_wait": (C.c_int, [C.c_void_p]),
     "dabhip_multi_stream_set_afc": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_multi_stream_set_soft": (C.c_int, [C.c_void_p, C.c_int]),
+    "dabhip_multi_stream_set_soft_lanes": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_multi_stream_set_parity_guard": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_multi_stream_set_sync_speculation": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_multi_stream_set_subchannels": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int]),
@@ -216,6 +219,7 @@ _SIGNATURES = {
     "dabhip_stream_eti_drain": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "dabhip_stream_set_afc": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_stream_set_soft": (C.c_int, [C.c_void_p, C.c_int]),
+    "dabhip_stream_set_soft_lanes": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_stream_ceiling": (C.c_int, [C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
     "dabhip_device_alloc": (C.c_void_p, [C.c_size_t, C.c_int]),
     "dabhip_device_free": (None, [C.c_void_p]),
@@ -224,6 +228,7 @@ _SIGNATURES = {
     "dabhip_host_free": (None, [C.c_void_p]),
     "dabhip_synth_generate_device": (C.c_int, [C.POINTER(SynthCfg), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_int]),
     "dabhip_dab_set_soft": (C.c_int, [C.c_void_p, C.c_int]),
+    "dabhip_dab_set_soft_lanes": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_dab_set_decoder_forms": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "dabhip_dab_decoder_forms": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "dabhip_engine_set_decoder_forms": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -660,7 +665,7 @@ class Sdr:
 class Dab:
     """init_dab_state + dab_process_frame (dab.h:91-92) for one stream."""
 
-    def __init__(self, device=0, soft=False, forms=None):
+    def __init__(self, device=0, soft=False, forms=None, soft_lanes=False):
         self.frames = []
         self._cb = ETI_CALLBACK(lambda p: self.frames.append(np.frombuffer(C.string_at(p, ETI_BYTES), np.uint8)))
         self._h = lib().dabhip_dab_init(device, self._cb)
@@ -670,12 +675,18 @@ class Dab:
         if soft:       # extension: the hand-off carries signed 4-bit values (int8 views of the same arrays)
             _need(lib().dabhip_dab_set_soft(self._h, 1) == 0, "dab_set_soft")
             self.fic, self.msc = self.fic.view(np.int8), self.msc.view(np.int8)
+        if soft_lanes:
+            self.set_soft_lanes(True)
         if forms is not None:
             self.set_decoder_forms(*forms)
 
     def set_decoder_forms(self, msc=None, fic=None):
         """Force the Viterbi form of the MSC / FIC decodes (names or FORM_* numbers; None = the default rule)."""
         _need(lib().dabhip_dab_set_decoder_forms(self._h, _form(msc), _form(fic)) == 0, "dab_set_decoder_forms")
+
+    def set_soft_lanes(self, enable):
+        """see Engine.set_soft_lanes"""
+        _need(lib().dabhip_dab_set_soft_lanes(self._h, 1 if enable else 0) == 0, "dab_set_soft_lanes")
 
     def decoder_forms(self, masks=False):
         """The forms that ran in the last process_frame: ({MSC form names}, {FIC form names}), or the two bit masks."""
@@ -849,6 +860,11 @@ class Engine:
     def set_decoder_forms(self, msc=None, fic=None):
         """Force the Viterbi form of every MSC / FIC launch (names or FORM_* numbers; None = the default rule, engine.hpp)."""
         _need(lib().dabhip_engine_set_decoder_forms(self._h, _form(msc), _form(fic)) == 0, "set_decoder_forms")
+
+    def set_soft_lanes(self, enable):
+        """Let soft decisions run the four-lane and table-free two-lane decoder forms (dabhip.h; default off: a soft engine runs the lane
+        form whatever is forced).  Any time; changes which kernel a later launch takes, never the bytes."""
+        _need(lib().dabhip_engine_set_soft_lanes(self._h, 1 if enable else 0) == 0, "set_soft_lanes")
 
     def decoder_forms(self, masks=False):
         """The forms that ran since the last decode / stage_fic_decode began: ({MSC form names}, {FIC form names}), or the two bit masks."""
@@ -1111,6 +1127,10 @@ class Multi:
     def set_soft(self, enable):
         self._set(lib().dabhip_multi_set_soft, enable)
 
+    def set_soft_lanes(self, enable):
+        """see Engine.set_soft_lanes"""
+        self._set(lib().dabhip_multi_set_soft_lanes, enable)
+
     def set_parity_guard(self, level=True):
         _need(lib().dabhip_multi_set_parity_guard(self._h, _guard_level(level)) == 0, "multi_set_parity_guard")
 
@@ -1242,6 +1262,10 @@ class Stream:
     def set_parity_guard(self, level=True):
         """see Engine.set_parity_guard"""
         _need(self._f("set_parity_guard")(self._h, _guard_level(level)) == 0, "stream_set_parity_guard")
+
+    def set_soft_lanes(self, enable):
+        """see Engine.set_soft_lanes (any time; single- and multi-device sessions)"""
+        _need(self._f("set_soft_lanes")(self._h, 1 if enable else 0) == 0, "stream_set_soft_lanes")
 
     def _single_device(self, what):
         """The entries that exist for dabhip_stream handles only: a multi-device session's handle is another type."""

@@ -306,6 +306,12 @@ int dabhip_engine_set_decoder_forms(dabhip_engine* e, int msc_form, int fic_form
     if (!l->set_decoder_forms(msc_form, fic_form)) return -1;
   return 0;
 }
+int dabhip_engine_set_soft_lanes(dabhip_engine* e, int enable)
+{
+  if (!e) { set_error("set_soft_lanes: null handle"); return -1; }
+  for (auto& l : e->lanes) l->set_soft_lanes(enable != 0);
+  return 0;
+}
 int dabhip_engine_decoder_forms(const dabhip_engine* e, uint32_t* msc_mask, uint32_t* fic_mask)
 {
   if (!e) { set_error("decoder_forms: null handle"); return -1; }
@@ -631,6 +637,12 @@ int dabhip_dab_set_decoder_forms(dabhip_dab* d, int msc_form, int fic_form)
 {
   if (!d) { set_error("dab_set_decoder_forms: null handle"); return -1; }
   return d->eng.set_decoder_forms(msc_form, fic_form) ? 0 : -1;
+}
+int dabhip_dab_set_soft_lanes(dabhip_dab* d, int enable)
+{
+  if (!d) { set_error("dab_set_soft_lanes: null handle"); return -1; }
+  d->eng.set_soft_lanes(enable != 0);
+  return 0;
 }
 int dabhip_dab_decoder_forms(const dabhip_dab* d, uint32_t* msc_mask, uint32_t* fic_mask)
 {
@@ -1020,6 +1032,12 @@ extern "C" int dabhip_stream_set_soft(dabhip_stream* s, int on)
   if (!s) return -1;
   if (!s->first) { set_error("stream_set_soft: only before the first segment"); return -1; }
   s->eng.set_soft(on != 0);
+  return 0;
+}
+extern "C" int dabhip_stream_set_soft_lanes(dabhip_stream* s, int on)
+{
+  if (!s) { set_error("stream_set_soft_lanes: null handle"); return -1; }
+  s->eng.set_soft_lanes(on != 0);
   return 0;
 }
 

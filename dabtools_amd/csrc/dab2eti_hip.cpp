@@ -88,6 +88,7 @@ bool map_file(const char* name, Mapped* m)
 // (dab2eti.c:132-135), stream by stream within a segment.
 bool g_stats = false;                            // --stats: phase times on stderr (one JSON line), for tools/cli_throughput.py
 bool g_quiet = false;                            // --quiet: no operator messages
+bool g_soft_lanes = false;                       // --soft-lanes: soft decisions may run the multi-lane decoder forms (dabhip_engine_set_soft_lanes)
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // the reference's operator messages of one input (dabhip_*_log text) on stderr: as they are for a single input, every line prefixed otherwise
@@ -116,6 +117,7 @@ struct Session {
   void destroy() { if (one) dabhip_stream_destroy(one); if (many) dabhip_multi_stream_destroy(many); one = nullptr; many = nullptr; }
   void set_afc() { if (one) dabhip_stream_set_afc(one, 1); else dabhip_multi_stream_set_afc(many, 1); }
   void set_soft() { if (one) dabhip_stream_set_soft(one, 1); else dabhip_multi_stream_set_soft(many, 1); }
+  void set_soft_lanes() { if (one) dabhip_stream_set_soft_lanes(one, 1); else dabhip_multi_stream_set_soft_lanes(many, 1); }
   void set_subchannels(const std::vector<int32_t>& ids)
   {
     if (one) dabhip_stream_set_subchannels(one, ids.data(), static_cast<int>(ids.size()));
@@ -149,6 +151,7 @@ int run_streaming(const std::vector<const char*>& names, size_t seg_bytes, bool 
   if (!ses.create(devices, n)) { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); return 2; }
   if (afc) ses.set_afc();
   if (soft) ses.set_soft();
+  if (g_soft_lanes) ses.set_soft_lanes();
   if (!subch.empty()) ses.set_subchannels(subch);
   constexpr int kBufs = 3, kOut = 2;
   uint8_t* buf[kBufs];
@@ -305,6 +308,7 @@ int main(int argc, char** argv)
     else if (std::strcmp(argv[i], "--quiet") == 0) g_quiet = true;
     else if (std::strcmp(argv[i], "--afc") == 0) afc = true;          // software AFC: captures with a carrier offset (no tuner to steer)
     else if (std::strcmp(argv[i], "--soft") == 0) soft = true;        // 4-bit soft decisions (not the reference's hard ones)
+    else if (std::strcmp(argv[i], "--soft-lanes") == 0) g_soft_lanes = true;   // ... through the multi-lane decoder forms where the rule picks them (dabhip.h)
     else if (std::strcmp(argv[i], "--subch") == 0 && i + 1 < argc) {
       for (const char* p = argv[++i]; *p;) {
         subch.push_back(static_cast<int32_t>(std::strtol(p, const_cast<char**>(&p), 10)));
@@ -329,7 +333,7 @@ int main(int argc, char** argv)
     else { names.push_back(argv[i]); streaming = streaming || std::strcmp(argv[i], "-") == 0; }
   }
   if (names.empty()) {
-    std::fprintf(stderr, "Usage: dab2eti-hip [--stream] [--segment-calls N] [--afc] [--soft] [--quiet] [--subch ID[,ID...]] [--devices A-B|A,B,...] capture.cu8|- [more.cu8 ...] > out.eti\n");
+    std::fprintf(stderr, "Usage: dab2eti-hip [--stream] [--segment-calls N] [--afc] [--soft] [--soft-lanes] [--quiet] [--subch ID[,ID...]] [--devices A-B|A,B,...] capture.cu8|- [more.cu8 ...] > out.eti\n");
     return 1;
   }
   if (streaming) {
@@ -358,6 +362,7 @@ int main(int argc, char** argv)
     if (!m) { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); return 2; }
     if (afc) dabhip_multi_set_afc(m, 1);
     if (soft) dabhip_multi_set_soft(m, 1);
+    if (g_soft_lanes) dabhip_multi_set_soft_lanes(m, 1);
     if (!subch.empty()) dabhip_multi_set_subchannels(m, subch.data(), static_cast<int>(subch.size()));
     const int64_t n = dabhip_multi_decode(m, ptrs.data(), sizes.data(), static_cast<int>(ptrs.size()), 0);
     if (n < 0) { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); return 2; }
@@ -377,6 +382,7 @@ int main(int argc, char** argv)
   if (!e) { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); return 2; }
   if (afc) dabhip_engine_set_afc(e, 1);
   if (soft) dabhip_engine_set_soft(e, 1);
+  if (g_soft_lanes) dabhip_engine_set_soft_lanes(e, 1);
   if (!subch.empty()) dabhip_engine_set_subchannels(e, subch.data(), static_cast<int>(subch.size()));
   const double t_ready = now_s();
   const int64_t n = dabhip_engine_decode(e, ptrs.data(), sizes.data(), static_cast<int>(ptrs.size()), 0);

@@ -219,8 +219,11 @@ class Engine {
   void set_soft(bool on) { soft_bits_ = on ? 4 : 0; tf_slots_ = 0; msc_rows_ = 0; }
   // Viterbi decoder forms (include/dabhip.h: DABHIP_FORM_*; test plumbing): -1 = the rule of the knobs and defaults below, else that form for
   // every MSC / FIC launch.  False for a form the decoder does not have (TWO, TWO_PLAIN for the FIC).  forms_ran: bit f = form f ran in a
-  // launch since clear_forms_ran() (a multi-lane form asked of a soft engine runs, and reports, the lane form).
+  // launch since clear_forms_ran() (a multi-lane form asked of a soft engine runs, and reports, the lane form -- with set_soft_lanes on only TWO does:
+  // FOUR, and TWO_PLAIN for the MSC, then run as asked).
   bool set_decoder_forms(int msc_form, int fic_form);
+  // soft decisions through the four-lane and table-free two-lane forms (decoder_form.hpp: FormKnobs::soft_lanes); any time, like set_decoder_forms
+  void set_soft_lanes(bool on) { knobs_.soft_lanes = on; }
   void clear_forms_ran() { msc_ran_ = 0; fic_ran_ = 0; }
   uint32_t msc_forms_ran() const { return msc_ran_.load(); }
   uint32_t fic_forms_ran() const { return fic_ran_.load(); }

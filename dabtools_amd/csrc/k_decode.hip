@@ -851,6 +851,7 @@ namespace {
 
 #include "vit_two_lanes.hpp"
 #include "vit_four_lanes.hpp"
+#include "vit_soft_lanes.hpp"
 
 // ---------------------------------------------------------------------------------------
 // batched device-to-device copy (session carry-over of slots and rows): grid (piece, slice)
@@ -1098,7 +1099,8 @@ hipError_t launch_fic_group(const uint32_t* fic_rows, int first_block, int nbloc
 hipError_t launch_viterbi_wave(int soft_bits, const ViterbiLaunch& v, hipStream_t stream);      // k_vitwave.hip
 
 // lane: one lane per code word; two: two lanes (vit_two_lanes.hpp), two waves per group; two plain / four: 2^NL lanes without per-lane tables
-// (vit_four_lanes.hpp), 2 or 4 waves' worth of lanes per group.  The multi-lane forms take hard decisions only.
+// (vit_four_lanes.hpp), 2 or 4 waves' worth of lanes per group.  Soft decisions: two plain / four run vit_soft_lanes.hpp's kernels (the rule asks for
+// them only with FormKnobs::soft_lanes on); two, with its per-lane tables of hard metrics, is hard-only.
 hipError_t launch_viterbi_form(int form, int soft_bits, const ViterbiLaunch& v, hipStream_t stream)
 {
   if (v.ngroups <= 0) return hipSuccess;
@@ -1109,6 +1111,12 @@ hipError_t launch_viterbi_form(int form, int soft_bits, const ViterbiLaunch& v, 
                        v.decisions, v.prbs_words, v.out, v.record_stride);
   else if (form == DABHIP_FORM_LANE)
     hipLaunchKernelGGL(viterbi_fused_kernel<1>, dim3((ngroups + 3) / 4), dim3(256), 0, stream, v.groups, ngroups, v.job_ids, v.plans, v.grouped, v.row_words,
+                       v.decisions, v.prbs_words, v.out, v.record_stride);
+  else if (soft_bits && form == DABHIP_FORM_FOUR)
+    hipLaunchKernelGGL(viterbi_soft_lanes_kernel<2>, dim3(ngroups), dim3(256), 0, stream, v.groups, ngroups, v.job_ids, v.plans, v.grouped, v.row_words, v.decisions,
+                       v.prbs_words, v.out, v.record_stride);
+  else if (soft_bits && form == DABHIP_FORM_TWO_PLAIN)
+    hipLaunchKernelGGL(viterbi_soft_lanes_kernel<1>, dim3((2 * ngroups + 3) / 4), dim3(256), 0, stream, v.groups, ngroups, v.job_ids, v.plans, v.grouped, v.row_words,
                        v.decisions, v.prbs_words, v.out, v.record_stride);
   else if (soft_bits)
     return hipErrorInvalidValue;

@@ -143,7 +143,7 @@ struct ViterbiLaunch {
   const WaveGroup* groups; int ngroups; const int* job_ids; const CodewordPlan* plans; const uint32_t* grouped; int row_words;
   uint2* decisions; const uint32_t* prbs_words; uint8_t* out; int record_stride;
 };
-// form: DABHIP_FORM_WAVE / LANE (hard and soft decisions) / TWO / TWO_PLAIN / FOUR (hard only: hipErrorInvalidValue with soft_bits); decoder_form.hpp has the rule
+// form: DABHIP_FORM_WAVE / LANE / TWO_PLAIN / FOUR (hard and soft decisions) / TWO (hard only: hipErrorInvalidValue with soft_bits); decoder_form.hpp has the rule
 hipError_t launch_viterbi_form(int form, int soft_bits, const ViterbiLaunch& v, hipStream_t stream);
 
 // The low-latency form of the same decoder (k_vitwave.hip): one WAVE per code word, lane = trellis state -- a fraction of the fused kernel's

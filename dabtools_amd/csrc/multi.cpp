@@ -249,6 +249,7 @@ float dabhip_multi_wall_ms(const dabhip_multi* m, int slice)
   }
 DABHIP_MULTI_FORWARD(dabhip_multi_set_afc(dabhip_multi* m, int enable), dabhip_engine_set_afc(s.eng, enable))
 DABHIP_MULTI_FORWARD(dabhip_multi_set_soft(dabhip_multi* m, int enable), dabhip_engine_set_soft(s.eng, enable))
+DABHIP_MULTI_FORWARD(dabhip_multi_set_soft_lanes(dabhip_multi* m, int enable), dabhip_engine_set_soft_lanes(s.eng, enable))
 DABHIP_MULTI_FORWARD(dabhip_multi_set_parity_guard(dabhip_multi* m, int enable), dabhip_engine_set_parity_guard(s.eng, enable))
 DABHIP_MULTI_FORWARD(dabhip_multi_set_fused(dabhip_multi* m, int enable), dabhip_engine_set_fused(s.eng, enable))
 DABHIP_MULTI_FORWARD(dabhip_multi_set_subchannels(dabhip_multi* m, const int32_t* ids, int n), dabhip_engine_set_subchannels(s.eng, ids, n))
@@ -516,6 +517,7 @@ int dabhip_multi_stream_eti_fetch_wait(dabhip_multi_stream* m)
   }
 DABHIP_MULTI_STREAM_FORWARD(dabhip_multi_stream_set_afc(dabhip_multi_stream* m, int enable), dabhip_stream_set_afc(sl.s, enable))
 DABHIP_MULTI_STREAM_FORWARD(dabhip_multi_stream_set_soft(dabhip_multi_stream* m, int enable), dabhip_stream_set_soft(sl.s, enable))
+DABHIP_MULTI_STREAM_FORWARD(dabhip_multi_stream_set_soft_lanes(dabhip_multi_stream* m, int enable), dabhip_stream_set_soft_lanes(sl.s, enable))
 DABHIP_MULTI_STREAM_FORWARD(dabhip_multi_stream_set_parity_guard(dabhip_multi_stream* m, int level), dabhip_stream_set_parity_guard(sl.s, level))
 DABHIP_MULTI_STREAM_FORWARD(dabhip_multi_stream_set_sync_speculation(dabhip_multi_stream* m, int mode), dabhip_stream_set_sync_speculation(sl.s, mode))
 DABHIP_MULTI_STREAM_FORWARD(dabhip_multi_stream_set_subchannels(dabhip_multi_stream* m, const int32_t* ids, int n), dabhip_stream_set_subchannels(sl.s, ids, n))

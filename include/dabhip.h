@@ -96,6 +96,7 @@ uint32_t dabhip_dab_status(const dabhip_dab *d);
 int dabhip_dab_set_soft(dabhip_dab *d, int enable);
 /* Decoder forms of this seam (dabhip_engine_set_decoder_forms, DABHIP_FORM_*; any time); the report covers the last dabhip_dab_process_frame. */
 int dabhip_dab_set_decoder_forms(dabhip_dab *d, int msc_form, int fic_form);
+int dabhip_dab_set_soft_lanes(dabhip_dab *d, int enable);   /* dabhip_engine_set_soft_lanes for this seam; any time */
 int dabhip_dab_decoder_forms(const dabhip_dab *d, uint32_t *msc_mask, uint32_t *fic_mask);
 /* launch limits and the last process_frame's launches: see dabhip_engine_set_launch_limits */
 int dabhip_dab_set_launch_limits(dabhip_dab *d, const int64_t *limits, int n);
@@ -175,9 +176,16 @@ int dabhip_engine_set_soft(dabhip_engine *e, int enable);
  * FIC: DABHIP_FORM_WAVE (default up to 3,072 blocks), DABHIP_FORM_LANE, DABHIP_FORM_FOUR (default up to 128 tiles of 64 blocks).
  * dabhip_engine_set_decoder_forms sets the form of every MSC and every FIC launch of all of the engine's lanes, over the environment knobs
  * (DABHIP_VIT_WAVE_MAX and its kin); DABHIP_FORM_AUTO restores the rule of the knobs and defaults.  -1 with error text for a
- * form the decoder does not have (TWO and TWO_PLAIN for the FIC).  The multi-lane forms take hard decisions only: on a soft engine
- * (dabhip_engine_set_soft) a forced TWO, TWO_PLAIN or FOUR runs the lane form, and the report says LANE.  A forced WAVE decodes every batch in one
- * launch (the lane forms split a launch past 24 GiB of survivor records).
+ * form the decoder does not have (TWO and TWO_PLAIN for the FIC).  A forced WAVE decodes every batch in one launch (the lane forms split a launch
+ * past 24 GiB of survivor records).
+ * Soft decisions (dabhip_engine_set_soft) and the multi-lane forms, by dabhip_engine_set_soft_lanes (default off; DABHIP_SOFT_LANES=1):
+ *   off: the multi-lane forms take hard decisions only.  A soft launch outside the wave form runs the lane form; a forced TWO, TWO_PLAIN or FOUR
+ *        runs the lane form too, and the report says LANE.
+ *   on:  a forced FOUR or TWO_PLAIN (FIC: FOUR) runs vit_soft_lanes.hpp's soft four-lane / table-free two-lane decoder and is reported as such; a
+ *        forced TWO (per-lane tables of hard metrics) still runs and reports LANE.  Under DABHIP_FORM_AUTO the knobs DABHIP_VIT_SOFT_FOUR_LANES and
+ *        DABHIP_FIC_SOFT_FOUR_LANES (0 / 1 / N groups resp. tiles; defaults in decoder_form.hpp from profiles/r08_soft_lanes_curve.json: 1176 groups, 0 tiles) choose
+ *        between FOUR and LANE.  Hard-decision engines are not affected.
+ * dabhip_engine_set_soft_lanes may be called at any time; it only changes which kernel a later launch takes, never the bytes.
  * dabhip_engine_decoder_forms: bit f of *msc_mask / *fic_mask is set when form f ran in at least one launch since the last
  * dabhip_engine_decode or dabhip_stage_fic_decode began (0: no such launch, e.g. no MSC frame).  Either pointer may be NULL. */
 #define DABHIP_FORM_AUTO (-1)
@@ -187,6 +195,7 @@ int dabhip_engine_set_soft(dabhip_engine *e, int enable);
 #define DABHIP_FORM_TWO_PLAIN 3
 #define DABHIP_FORM_FOUR 4
 int dabhip_engine_set_decoder_forms(dabhip_engine *e, int msc_form, int fic_form);
+int dabhip_engine_set_soft_lanes(dabhip_engine *e, int enable);
 int dabhip_engine_decoder_forms(const dabhip_engine *e, uint32_t *msc_mask, uint32_t *fic_mask);
 
 /* Parity guard (default ON).  The reference takes its hard decisions as sign tests on fp64 FFTW spectra (input_sdr.c:132-162);
@@ -328,6 +337,7 @@ dabhip_engine *dabhip_multi_engine(dabhip_multi *m, int slice);
 float dabhip_multi_wall_ms(const dabhip_multi *m, int slice);
 int dabhip_multi_set_afc(dabhip_multi *m, int enable);
 int dabhip_multi_set_soft(dabhip_multi *m, int enable);
+int dabhip_multi_set_soft_lanes(dabhip_multi *m, int enable);   /* dabhip_engine_set_soft_lanes on every device */
 int dabhip_multi_set_parity_guard(dabhip_multi *m, int level);
 int dabhip_multi_set_fused(dabhip_multi *m, int enable);
 int dabhip_multi_set_subchannels(dabhip_multi *m, const int32_t *ids, int n);
@@ -371,6 +381,7 @@ int dabhip_stream_eti_fetch_wait(dabhip_stream *s);
 int dabhip_stream_set_afc(dabhip_stream *s, int enable);
 int dabhip_stream_set_subchannels(dabhip_stream *s, const int32_t *ids, int n);   /* before the first segment only */
 int dabhip_stream_set_soft(dabhip_stream *s, int enable);   /* before the first segment only */
+int dabhip_stream_set_soft_lanes(dabhip_stream *s, int enable);   /* dabhip_engine_set_soft_lanes for the session; any time */
 int dabhip_stream_set_parity_guard(dabhip_stream *s, int level);   /* see dabhip_engine_set_parity_guard */
 int dabhip_stream_set_sync_speculation(dabhip_stream *s, int mode);   /* default -1, see dabhip_engine_set_sync_speculation */
 int dabhip_stream_set_demod_all(dabhip_stream *s, int on);            /* see dabhip_engine_set_demod_all */
@@ -412,6 +423,7 @@ int64_t dabhip_multi_stream_eti_fetch(dabhip_multi_stream *m, uint8_t *dst, int6
 int dabhip_multi_stream_eti_fetch_wait(dabhip_multi_stream *m);
 int dabhip_multi_stream_set_afc(dabhip_multi_stream *m, int enable);
 int dabhip_multi_stream_set_soft(dabhip_multi_stream *m, int enable);                    /* before the first segment only */
+int dabhip_multi_stream_set_soft_lanes(dabhip_multi_stream *m, int enable);              /* any time */
 int dabhip_multi_stream_set_parity_guard(dabhip_multi_stream *m, int level);
 int dabhip_multi_stream_set_sync_speculation(dabhip_multi_stream *m, int mode);
 int dabhip_multi_stream_set_subchannels(dabhip_multi_stream *m, const int32_t *ids, int n);   /* before the first segment only */
