@@ -399,7 +399,7 @@ int main(int argc, char** argv)
     if (host && dabhip_engine_eti_fetch(e, host, n) == n && dabhip_engine_eti_fetch_wait(e) == 0) {
       write_all(host, static_cast<size_t>(n) * DABHIP_ETI_BYTES);
     } else {
-      // the one-download path serves one decode lane (DABHIP_LANES=1, the default); an engine of several lanes hands its frames over stream by stream
+      // the one-download path failed (no page-locked buffer, or the fetch itself): the frames are handed over stream by stream instead
       if (dabhip_engine_eti_drain(e, to_stdout, nullptr) != n) { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); return 2; }
       flush_stdout();
     }

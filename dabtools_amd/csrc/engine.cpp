@@ -276,7 +276,6 @@ bool Engine::stage_a(DecodeRun& run)
   const int ntf = seg.ntf, nslots = seg.tf_base[run.nstreams];
   if (ntf == 0) return true;
   if (!carry_and_reserve(seg)) return false;
-  if (heavy_mu_ && !run.heavy.owns_lock()) run.heavy = std::unique_lock<std::mutex>(*heavy_mu_);
   const bool guard = guard_active(), soft = soft_bits_ != 0;
   const bool energies = guard || soft;                    // the per-symbol sample energies: the guard's error bounds, the soft scale
   const int chunk = run.chunk = fused_ ? std::max(ntf, 1) : std::min(ntf, limits_.fft_chunk_tfs);   // only the spectra buffer of the two-kernel stage calls for chunks
@@ -424,7 +423,6 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
   run.mark("all queued");
   const bool drained = check(hipStreamSynchronize(stream_), "decode");      // also on the error paths: nothing may stay in flight
   run.mark("stream drained");
-  if (run.heavy.owns_lock()) run.heavy.unlock();
   if (!gpu_ok || !drained) return -1;
   if (!run.host_ok) { set_error(run.host_error); return -1; }
   for (int c = 0; c < nchunks; ++c) {

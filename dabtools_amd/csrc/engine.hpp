@@ -194,9 +194,6 @@ class Engine {
   Engine(const Engine&) = delete;
   Engine& operator=(const Engine&) = delete;
   bool ok() const { return ok_; }
-  // Lanes of one batch engine share this lock around their GPU-saturating phases (FFT/demap/FIC and MSC decode), so
-  // those never overlap each other; only the light phases (sync scan, host control plane) run beside them.
-  void set_heavy_lock(std::mutex* m) { heavy_mu_ = m; }
   const uint8_t* eti_buffer() const { return d_eti_.get(); }
   // software AFC: an NCO per stream steered by the reference's tuner rule; off = parity mode
   void set_afc(bool on) { afc_ = on; }
@@ -285,7 +282,7 @@ class Engine {
   int stage_decision_audit_fused(const uint8_t* frames, int nframes, bool on_device, bool guard_on, double* out8, double* out_extra);
   int viterbi_batch(const uint8_t* symbols, uint8_t* data, int framebits, int n);
 
-  // -- building blocks shared with the streaming seams (capi.cpp) ------------------------------
+  // -- building blocks shared with the streaming seams (capi_seams.cpp) ------------------------------
   // FIC rows / FIB records for nslots TFs and msc_rows logical CIF rows (default 4 per slot + 15 lead-in + 1)
   bool reserve_tf_slots(int nslots, int msc_rows = -1);
   // host 0/1 bytes of one demapped TF -> bit rows of TF slot `slot`
@@ -329,7 +326,6 @@ class Engine {
     int nstreams;
     bool cont;                               // a session's further segment
     std::chrono::steady_clock::time_point wall0;
-    std::unique_lock<std::mutex> heavy;      // the heavy lock, held from stage A to the drain
     int chunk = 1;                           // frames per launch of the OFDM stage
     bool host_ok = true;                     // the control-plane pass's outcome
     std::string host_error;
@@ -413,7 +409,6 @@ class Engine {
   FormKnobs knobs_;                            // decoder_form.hpp: the thresholds of the forms' rule, environment overrides applied
   int msc_form_ = -1, fic_form_ = -1;          // set_decoder_forms: -1 = the rules above
   std::atomic<uint32_t> msc_ran_{0}, fic_ran_{0};
-  std::mutex* heavy_mu_ = nullptr;
   std::unique_ptr<ThreadPool> pool_;   // host threads for per-stream control-plane work
   std::unique_ptr<AsyncLane> host_lane_;   // the control-plane pass of a decode, beside its GPU work
   int device_ = 0, numa_node_ = -1;

@@ -319,8 +319,6 @@ void Engine::msc_collect()
 
 bool Engine::msc_launch(const MscWork& w)
 {
-  std::unique_lock<std::mutex> heavy;
-  if (heavy_mu_) heavy = std::unique_lock<std::mutex>(*heavy_mu_);
   if (!msc_launch_async(w) || !check(hipStreamSynchronize(stream_), "msc decode")) return false;
   msc_collect();
   return true;

@@ -22,15 +22,53 @@
 
 #include <hip/hip_runtime_api.h>
 
-#include "../../include/dabhip.h"
+#include "capi_detail.hpp"
 #include "placement.hpp"
 #include "thread_pool.hpp"
 
-namespace dabhip {
-void set_error(const std::string& msg);
-}
 using dabhip::AsyncLane;
+using dabhip::Deal;
 using dabhip::set_error;
+
+namespace {
+
+// Where the host side of n slices runs, one per listed device.  host_threads: per slice -- the slices share the host, so that eight of them do not
+// start 8 x 24 busy threads (of the CPUs this process may use -- affinity mask and CFS quota, placement.hpp --, not of the machine's).  Placement
+// (placement.hpp): every slice's threads -- its decode thread here, the engine's control-plane pool and host lane -- on the NUMA node of its device, the
+// node's CPUs dealt to the slices on it in disjoint chunks; page-locked buffers are allocated by those threads, i.e. there.
+struct HostPlacement {
+  int host_threads;
+  std::vector<int> node;                 // per slice: its device's NUMA node, -1 = unknown
+  std::vector<std::vector<int>> cpus;    // per slice: the CPUs its host threads are bound to; empty = unbound
+};
+HostPlacement place_slices(const int* devices, int n)
+{
+  HostPlacement p;
+  p.host_threads = std::max(2, std::min(24, dabhip::usable_cpus() / (2 * n)));
+  p.node.assign(static_cast<size_t>(n), -1);
+  if (dabhip::numa_enabled())
+    for (int i = 0; i < n; ++i) {
+      char bdf[32] = {0};
+      if (hipDeviceGetPCIBusId(bdf, sizeof bdf, devices[i]) == hipSuccess) p.node[static_cast<size_t>(i)] = dabhip::numa_node_of_pci(bdf);
+      else (void)hipGetLastError();
+    }
+  const std::vector<std::vector<int>> node_cpus = dabhip::allowed_node_cpus();
+  int populated = 0;
+  for (const auto& c : node_cpus) populated += c.empty() ? 0 : 1;
+  p.cpus.resize(static_cast<size_t>(n));
+  if (populated > 1) p.cpus = dabhip::plan_placement(p.node, node_cpus);      // a single-socket machine: nothing to choose, nothing bound
+  return p;
+}
+
+// the slice of a handle that holds `stream` of its nstreams (null: no such stream); the slices follow the dealing rule
+template <class Handle>
+auto slice_holding(Handle& h, int stream) -> decltype(h.slices.data())
+{
+  if (stream < 0 || stream >= h.nstreams) return nullptr;
+  return &h.slices[static_cast<size_t>(Deal{h.nstreams, static_cast<int>(h.slices.size())}.slice_of(stream))];
+}
+
+}  // namespace
 
 struct dabhip_multi {
   struct Slice {
@@ -55,13 +93,7 @@ struct dabhip_multi {
       if (s.eng) dabhip_engine_destroy(s.eng);
     }
   }
-  const Slice* slice_of(int stream) const
-  {
-    if (stream < 0 || stream >= nstreams) return nullptr;
-    for (const Slice& s : slices)
-      if (stream >= s.first && stream < s.first + s.count) return &s;
-    return nullptr;
-  }
+  const Slice* slice_of(int stream) const { return slice_holding(*this, stream); }
 };
 
 extern "C" {
@@ -71,32 +103,15 @@ dabhip_multi* dabhip_multi_create(const int* devices, int n)
   if (!devices || n <= 0 || n > 64) { set_error("multi_create: need 1..64 devices"); return nullptr; }
   std::unique_ptr<dabhip_multi> m(new (std::nothrow) dabhip_multi);
   if (!m) return nullptr;
-  // host threads per slice: the slices share the host, so that eight of them do not start 8 x 24 busy threads
-  // (of the CPUs this process may use -- affinity mask and CFS quota, placement.hpp --, not of the machine's)
-  const int hw = dabhip::usable_cpus();
-  const int host_threads = std::max(2, std::min(24, hw / (2 * n)));
+  const HostPlacement place = place_slices(devices, n);
   m->slices.resize(n);
-  // host placement (placement.hpp): every slice's threads -- its decode thread here, the engine's control-plane pool and host lane -- on the NUMA
-  // node of its device, the node's CPUs dealt to the slices on it in disjoint chunks; page-locked buffers are allocated by those threads, i.e. there
-  std::vector<int> nodes(static_cast<size_t>(n), -1);
-  if (dabhip::numa_enabled())
-    for (int i = 0; i < n; ++i) {
-      char bdf[32] = {0};
-      if (hipDeviceGetPCIBusId(bdf, sizeof bdf, devices[i]) == hipSuccess) nodes[static_cast<size_t>(i)] = dabhip::numa_node_of_pci(bdf);
-      else (void)hipGetLastError();
-    }
-  const std::vector<std::vector<int>> node_cpus = dabhip::allowed_node_cpus();
-  int populated = 0;
-  for (const auto& c : node_cpus) populated += c.empty() ? 0 : 1;
-  std::vector<std::vector<int>> plan(static_cast<size_t>(n));
-  if (populated > 1) plan = dabhip::plan_placement(nodes, node_cpus);          // a single-socket machine: nothing to choose, nothing bound
   for (int i = 0; i < n; ++i) {
     dabhip_multi::Slice& s = m->slices[i];
     s.device = devices[i];
-    s.cpus = plan[static_cast<size_t>(i)];
-    s.numa_node = nodes[static_cast<size_t>(i)];
+    s.cpus = place.cpus[static_cast<size_t>(i)];
+    s.numa_node = place.node[static_cast<size_t>(i)];
     std::vector<int32_t> c32(s.cpus.begin(), s.cpus.end());
-    s.eng = dabhip_engine_create_on_cpus(devices[i], host_threads, c32.data(), static_cast<int>(c32.size()));
+    s.eng = dabhip_engine_create_on_cpus(devices[i], place.host_threads, c32.data(), static_cast<int>(c32.size()));
     if (!s.eng) return nullptr;            // dabhip_last_error() says why (bad index, no GPU: there is no CPU fallback)
     s.lane.reset(new AsyncLane(s.cpus));
   }
@@ -107,14 +122,12 @@ void dabhip_multi_destroy(dabhip_multi* m) { delete m; }
 
 int dabhip_multi_slices(const dabhip_multi* m) { return m ? static_cast<int>(m->slices.size()) : -1; }
 
-// The dealing rule as a pure function of (number of slices, batch size): usable BEFORE the first decode, e.g. to put stream b's samples on the
-// right device for an on_device decode.  Slice i takes nstreams / n streams, the first nstreams % n slices one more.
+// The dealing rule (placement.hpp: Deal) as a pure function of (number of slices, batch size): usable BEFORE the first decode, e.g. to put stream b's
+// samples on the right device for an on_device decode.
 int dabhip_multi_plan(const dabhip_multi* m, int nstreams, int stream, int* slice, int* device)
 {
   if (!m || nstreams <= 0 || stream < 0 || stream >= nstreams) { set_error("multi_plan: bad argument"); return -1; }
-  const int n = static_cast<int>(m->slices.size()), base = nstreams / n, rem = nstreams % n;
-  // the first rem slices hold base + 1 streams each
-  const int i = stream < rem * (base + 1) ? stream / (base + 1) : rem + (stream - rem * (base + 1)) / std::max(base, 1);
+  const int i = Deal{nstreams, static_cast<int>(m->slices.size())}.slice_of(stream);
   if (slice) *slice = i;
   if (device) *device = m->slices[static_cast<size_t>(i)].device;
   return 0;
@@ -142,14 +155,11 @@ int64_t dabhip_multi_decode(dabhip_multi* m, const uint8_t* const* iq, const siz
   if (!m || !iq || !nbytes) { set_error("multi_decode: null argument"); return -1; }
   if (nstreams <= 0) { set_error("multi_decode: no streams"); return -1; }
   const auto t0 = std::chrono::steady_clock::now();
-  const int n = static_cast<int>(m->slices.size());
-  const int base = nstreams / n, rem = nstreams % n;
-  int next = 0;
-  for (int i = 0; i < n; ++i) {
+  const Deal deal{nstreams, static_cast<int>(m->slices.size())};
+  for (int i = 0; i < deal.nslices; ++i) {
     dabhip_multi::Slice& s = m->slices[i];
-    s.first = next;
-    s.count = base + (i < rem ? 1 : 0);
-    next += s.count;
+    s.first = deal.first(i);
+    s.count = deal.count(i);
     s.frames = 0;
     s.wall_ms = 0;
     s.error.clear();
@@ -206,17 +216,9 @@ int64_t dabhip_multi_eti_read(dabhip_multi* m, int stream, uint8_t* dst, int64_t
 int64_t dabhip_multi_eti_drain(dabhip_multi* m, dabhip_eti_sink sink, void* user)
 {
   if (!m || !sink) { set_error("multi_eti_drain: null argument"); return -1; }
-  int64_t total = 0;
-  std::vector<uint8_t> buf;
-  for (int b = 0; b < m->nstreams; ++b) {   // stream order = slice order: the slices are contiguous
-    const int64_t n = dabhip_multi_eti_count(m, b);
-    if (n < 0) return -1;
-    buf.resize(static_cast<size_t>(n) * DABHIP_ETI_BYTES);
-    if (n && dabhip_multi_eti_read(m, b, buf.data(), n) != n) return -1;
-    for (int64_t f = 0; f < n; ++f) sink(buf.data() + f * DABHIP_ETI_BYTES, b, user);
-    total += n;
-  }
-  return total;
+  // stream order = slice order: the slices are contiguous
+  return dabhip::drain_eti(m->nstreams, sink, user, false, [m](int b) { return dabhip_multi_eti_count(m, b); },
+                           [m](int b, uint8_t* dst, int64_t n) { return dabhip_multi_eti_read(m, b, dst, n); });
 }
 
 int dabhip_multi_trace(const dabhip_multi* m, int stream, int32_t* ints6, double* ffs, int cap_calls)
@@ -289,14 +291,8 @@ struct dabhip_multi_stream {
       if (sl.s) dabhip_stream_destroy(sl.s);
     }
   }
-  Slice* slice_of(int stream)
-  {
-    if (stream < 0 || stream >= nstreams) return nullptr;
-    for (Slice& sl : slices)
-      if (stream >= sl.first && stream < sl.first + sl.count) return &sl;
-    return nullptr;
-  }
-  const Slice* slice_of(int stream) const { return const_cast<dabhip_multi_stream*>(this)->slice_of(stream); }
+  Slice* slice_of(int stream) { return slice_holding(*this, stream); }
+  const Slice* slice_of(int stream) const { return slice_holding(*this, stream); }
   // fn(slice) on every slice's host thread, all at once; false (and the text of the first failure) when one of them returned < 0
   template <class Fn>
   bool on_all(const char* what, Fn fn)
@@ -329,35 +325,20 @@ dabhip_multi_stream* dabhip_multi_stream_create(const int* devices, int n, int n
   if (nstreams <= 0) { set_error("multi_stream_create: no streams"); return nullptr; }
   std::unique_ptr<dabhip_multi_stream> m(new (std::nothrow) dabhip_multi_stream);
   if (!m) return nullptr;
-  const int hw = dabhip::usable_cpus();
-  const int host_threads = std::max(2, std::min(24, hw / (2 * n)));
-  std::vector<int> nodes(static_cast<size_t>(n), -1);
-  if (dabhip::numa_enabled())
-    for (int i = 0; i < n; ++i) {
-      char bdf[32] = {0};
-      if (hipDeviceGetPCIBusId(bdf, sizeof bdf, devices[i]) == hipSuccess) nodes[static_cast<size_t>(i)] = dabhip::numa_node_of_pci(bdf);
-      else (void)hipGetLastError();
-    }
-  const std::vector<std::vector<int>> node_cpus = dabhip::allowed_node_cpus();
-  int populated = 0;
-  for (const auto& c : node_cpus) populated += c.empty() ? 0 : 1;
-  std::vector<std::vector<int>> plan(static_cast<size_t>(n));
-  if (populated > 1) plan = dabhip::plan_placement(nodes, node_cpus);
+  const HostPlacement place = place_slices(devices, n);
   m->slices.resize(static_cast<size_t>(n));
   m->nstreams = nstreams;
-  const int base = nstreams / n, rem = nstreams % n;           // the dealing rule of dabhip_multi_plan
-  int next = 0;
+  const Deal deal{nstreams, n};
   for (int i = 0; i < n; ++i) {
     dabhip_multi_stream::Slice& sl = m->slices[static_cast<size_t>(i)];
     sl.device = devices[i];
-    sl.cpus = plan[static_cast<size_t>(i)];
-    sl.numa_node = nodes[static_cast<size_t>(i)];
-    sl.first = next;
-    sl.count = base + (i < rem ? 1 : 0);
-    next += sl.count;
+    sl.cpus = place.cpus[static_cast<size_t>(i)];
+    sl.numa_node = place.node[static_cast<size_t>(i)];
+    sl.first = deal.first(i);
+    sl.count = deal.count(i);
     if (sl.count == 0) continue;           // more devices than streams: the slice stays empty
     std::vector<int32_t> c32(sl.cpus.begin(), sl.cpus.end());
-    sl.s = dabhip_stream_create_on_cpus(devices[i], sl.count, host_threads, c32.data(), static_cast<int>(c32.size()));
+    sl.s = dabhip_stream_create_on_cpus(devices[i], sl.count, place.host_threads, c32.data(), static_cast<int>(c32.size()));
     if (!sl.s) return nullptr;             // dabhip_last_error() says why
     sl.lane.reset(new AsyncLane(sl.cpus));
   }
@@ -447,17 +428,9 @@ int64_t dabhip_multi_stream_eti_read(dabhip_multi_stream* m, int stream, uint8_t
 int64_t dabhip_multi_stream_eti_drain(dabhip_multi_stream* m, dabhip_eti_sink sink, void* user)
 {
   if (!m || !sink) { set_error("multi_stream_eti_drain: null argument"); return -1; }
-  int64_t total = 0;
-  std::vector<uint8_t> buf;
-  for (int b = 0; b < m->nstreams; ++b) {     // global stream order = slice order: the slices are contiguous
-    const int64_t n = dabhip_multi_stream_eti_count(m, b);
-    if (n < 0) return -1;
-    buf.resize(static_cast<size_t>(n) * DABHIP_ETI_BYTES);
-    if (n && dabhip_multi_stream_eti_read(m, b, buf.data(), n) != n) return -1;
-    for (int64_t f = 0; f < n; ++f) sink(buf.data() + f * DABHIP_ETI_BYTES, b, user);
-    total += n;
-  }
-  return total;
+  // global stream order = slice order: the slices are contiguous
+  return dabhip::drain_eti(m->nstreams, sink, user, false, [m](int b) { return dabhip_multi_stream_eti_count(m, b); },
+                           [m](int b, uint8_t* dst, int64_t n) { return dabhip_multi_stream_eti_read(m, b, dst, n); });
 }
 // The frames of the segment fed last, all slices, in global stream order, as one asynchronous download per slice into dst (page-locked): slice i's frames
 // follow those of slices 0 .. i - 1.  Returns their number; the copies have landed when dabhip_multi_stream_eti_fetch_wait returns.

@@ -71,6 +71,19 @@ inline std::vector<std::vector<int>> plan_placement(const std::vector<int>& slic
   return out;
 }
 
+// The dealing rule of a batch over several slices (multi.cpp): contiguous slices in stream order, slice i of n takes B / n streams, the first B % n
+// slices one more.  With more slices than streams the last n - B stay empty.
+struct Deal {
+  int nstreams, nslices;
+  int count(int i) const { return nstreams / nslices + (i < nstreams % nslices ? 1 : 0); }
+  int first(int i) const { return i * (nstreams / nslices) + std::min(i, nstreams % nslices); }
+  int slice_of(int stream) const       // of a stream in [0, nstreams)
+  {
+    const int base = nstreams / nslices, rem = nstreams % nslices, longer = rem * (base + 1);      // the first rem slices hold base + 1 streams each
+    return stream < longer ? stream / (base + 1) : rem + (stream - longer) / std::max(base, 1);     // (base = 0: every stream is below `longer`)
+  }
+};
+
 inline bool numa_enabled()
 {
   const char* e = std::getenv("DABHIP_NUMA");

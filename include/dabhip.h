@@ -174,7 +174,7 @@ int dabhip_engine_set_soft(dabhip_engine *e, int enable);
  *      DABHIP_FORM_TWO_PLAIN  two lanes per code word, table-free (vit_four_lanes.hpp; otherwise only with DABHIP_VIT_LANES_PLAIN=1)
  *      DABHIP_FORM_FOUR       four lanes per code word (vit_four_lanes.hpp; the default up to 800 groups)
  * FIC: DABHIP_FORM_WAVE (default up to 3,072 blocks), DABHIP_FORM_LANE, DABHIP_FORM_FOUR (default up to 128 tiles of 64 blocks).
- * dabhip_engine_set_decoder_forms sets the form of every MSC and every FIC launch of all of the engine's lanes, over the environment knobs
+ * dabhip_engine_set_decoder_forms sets the form of every MSC and every FIC launch of the engine, over the environment knobs
  * (DABHIP_VIT_WAVE_MAX and its kin); DABHIP_FORM_AUTO restores the rule of the knobs and defaults.  -1 with error text for a
  * form the decoder does not have (TWO and TWO_PLAIN for the FIC).  A forced WAVE decodes every batch in one launch (the lane forms split a launch
  * past 24 GiB of survivor records).

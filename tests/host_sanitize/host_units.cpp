@@ -13,6 +13,9 @@
 //   fifo_view.hpp      the closed-form FIFO / stale-tail views under random timing corrections, against a byte-level replay of
 //                      cbWrite / sdr_read_fifo's copying rule (sdr_fifo.c:26-61)
 //   synth.cpp          the modulator's bit content and sample generation (bounds, UB)
+//   session_windows.hpp a session's device windows replayed on byte arrays sized exactly as planned: every byte still needed where the plan says
+//   placement.hpp      the dealing rule of a batch over slices (Deal) and its inverse
+//   capi_host.cpp      the GPU-free entries as linked into the library: their buffer caps (the fifo case)
 // The reference's own data race (rtlsdr_callback writing sdr->input_buffer while the demod thread reads it, dab2eti.c:117-130)
 // has no counterpart here: segments are handed over by value of their pointers and never written while a decode runs.
 #include <atomic>
@@ -33,14 +36,11 @@
 #include "../../dabtools_amd/csrc/launch_limits.hpp"
 #include "../../dabtools_amd/csrc/scan_plan.hpp"
 #include "../../dabtools_amd/csrc/segment_layout.hpp"
+#include "../../dabtools_amd/csrc/session_windows.hpp"
 #include "../../dabtools_amd/csrc/thread_pool.hpp"
 #include "../../dabtools_amd/csrc/worklist.hpp"
 
 using namespace dabhip;
-
-namespace dabhip {
-void set_error(const std::string&) {}      // error.cpp's thread-local text is not linked into this binary
-}
 
 #define CHECK(cond)                                                                     \
   do {                                                                                  \
@@ -639,6 +639,137 @@ static void test_fifo_views()
   }
 }
 
+// the GPU-free entries of the C ABI (capi_host.cpp) with buffers of exactly the size they are told: a write beyond the cap is an overrun under ASan
+static void host_entries()
+{
+  dabhip_fifo* f = dabhip_host_fifo_new();
+  CHECK(f);
+  std::vector<uint8_t> stream(2 * kTfBytes);
+  for (size_t i = 0; i < stream.size(); ++i) stream[i] = static_cast<uint8_t>(i * 7);
+  std::vector<int32_t> seg_end(kMaxSeg);
+  std::vector<int64_t> seg_src(kMaxSeg);
+  std::vector<uint8_t> tail(kTailBytes);
+  int32_t nseg = 0, count = 0;
+  int status = 0;
+  for (int call = 0; call < 4 && status == 0; ++call)      // until the FIFO holds a frame
+    status = dabhip_host_fifo_call(f, 0, -100, kChunkBytes, stream.data(), &nseg, seg_end.data(), seg_src.data(), &count, tail.data());
+  CHECK(status > 0 && nseg >= 1 && nseg <= kMaxSeg);
+  CHECK(dabhip_host_fifo_call(f, 0, 0, kChunkBytes + 2, nullptr, &nseg, seg_end.data(), seg_src.data(), nullptr, nullptr) == -1);
+  CHECK(std::strstr(dabhip_last_error(), "chunk_bytes") != nullptr);      // error.cpp's text, as the library keeps it
+  dabhip_host_fifo_free(f);
+  // the control-plane replay with room for fewer frames than it produces: the count of all of them, only cap_frames written
+  const int ntf = 20, cap = 5;
+  std::vector<uint8_t> fibs, ok;
+  make_fibs(0, 3, 40, ntf, fibs, ok);
+  std::vector<int32_t> first_cif(cap), header_len(cap);
+  std::vector<uint8_t> headers(static_cast<size_t>(cap) * kEtiHeaderMax);
+  CHECK(dabhip_host_control_replay(fibs.data(), ok.data(), ntf, first_cif.data(), headers.data(), header_len.data(), cap) == 4 * (ntf - 13));
+  for (int i = 0; i < cap; ++i) CHECK(header_len[i] > 0 && header_len[i] <= kEtiHeaderMax && first_cif[i] == 4 * 13 - 16 + i);
+  std::vector<char> log(8);
+  CHECK(dabhip_host_control_replay_log(log.data(), static_cast<int64_t>(log.size())) >= 0 && std::strlen(log.data()) < log.size());
+  // the placement plan with fewer CPU entries than the lists name: CPUs beyond ncpu are not recorded
+  const int32_t slice_node[3] = {0, 1, 0};
+  const char* lists[2] = {"0-3", "4-7"};
+  std::vector<int32_t> cpu_slice(6);
+  CHECK(dabhip_host_placement_plan(slice_node, 3, lists, 2, cpu_slice.data(), static_cast<int>(cpu_slice.size())) == 3);
+  CHECK(cpu_slice == (std::vector<int32_t>{0, 0, 2, 2, 1, 1}));
+}
+static void test_fifo()
+{
+  test_fifo_views();
+  host_entries();
+}
+
+// A session's windows (session_windows.hpp) on the host: three byte arrays per stream stand in for the device windows, sized exactly as the session sizes
+// them; a known byte stream is fed in random even segments with a random non-decreasing need_from; every feed applies the plan's copies with memcpy and
+// then finds byte x of the stream at window + virtual_base + x for every x the front end may still read.
+static void session_on_host(size_t reserve, unsigned seed, bool reached[6])
+{
+  std::mt19937 rng(seed);
+  std::vector<uint8_t> stream(40 * reserve + 4096);
+  for (uint8_t& v : stream) v = static_cast<uint8_t>(rng());
+  std::vector<uint8_t> win[3];           // window k % 3 holds segment k; like DeviceBuffer: grow-only, contents lost on growth
+  auto reserve_window = [](std::vector<uint8_t>& w, size_t n) { if (n > w.size()) w = std::vector<uint8_t>(n, 0xEE); };
+  WindowBook book;
+  int64_t need_from = 0;
+  bool first = true, grown_last = false;
+  for (uint64_t k = 0; static_cast<size_t>(book.avail) < stream.size(); ++k) {
+    std::vector<uint8_t>& to = win[k % 3];
+    const std::vector<uint8_t>& from = win[(k + 2) % 3];
+    const size_t left = stream.size() - static_cast<size_t>(book.avail);
+    size_t nbytes = rng() % 4 == 0 ? 0 : 2 * (rng() % (reserve / 2 + 3));      // empty segments too; up to a little more than the reserve
+    nbytes = std::min(nbytes, left);
+    // the session's upload: the segment behind the reserve
+    reserve_window(to, window_bytes(reserve, nbytes));
+    std::memcpy(to.data() + reserve, stream.data() + book.avail, nbytes);
+    // the front end's answer: never backwards, now and then beyond what was fed; every fourth feed steered to one of the edges of the grow rule
+    const int64_t held = book.avail - need_from;
+    const int64_t edge[3] = {0, static_cast<int64_t>(reserve), static_cast<int64_t>(reserve) + 2};
+    const int64_t want = edge[rng() % 3];
+    if (!first && k % 4 == 0 && held >= want) need_from = book.avail - want;
+    else if (!first && rng() % 3 == 0) need_from += static_cast<int64_t>(rng() % (reserve / 2)) & ~int64_t(1);
+    const WindowPlan p = plan_window(book, first, need_from, nbytes, reserve);
+    CHECK(!p.refused && p.need == window_need_from(first, need_from, book.avail) && p.need >= book.base && p.kept == static_cast<size_t>(book.avail - p.need));
+    CHECK(p.grow == (p.kept > reserve));
+    if (p.grow) {                         // the segment moves to a window of its own size
+      std::vector<uint8_t> big(p.grow_bytes, 0xEE);
+      std::memcpy(big.data() + p.at, to.data() + reserve, nbytes);
+      to = std::move(big);
+    }
+    if (p.kept) std::memcpy(to.data() + p.move_to, from.data() + p.move_from, p.kept);      // (the session queues no move of nothing either)
+    CHECK(p.book.base == p.need && p.book.avail == book.avail + static_cast<int64_t>(nbytes));
+    for (int64_t x = p.need; x < p.book.avail; ++x) CHECK(to[static_cast<size_t>(p.virtual_base + x)] == stream[static_cast<size_t>(x)]);
+    reached[0] |= first;
+    reached[1] |= !first && p.kept == 0;
+    reached[2] |= p.kept == reserve;
+    reached[3] |= p.kept == reserve + 2;
+    reached[4] |= grown_last;
+    reached[5] |= need_from > book.avail;
+    grown_last = p.grow;
+    book = p.book;
+    first = false;
+  }
+}
+static void test_windows()
+{
+  for (size_t reserve : {size_t(256), size_t(65536)}) {
+    bool reached[6] = {false, false, false, false, false, false};      // first feed, kept == 0, == reserve, == reserve + 2 (grows), a feed after a grow, need_from beyond avail
+    for (unsigned seed = 1; seed <= 3; ++seed) session_on_host(reserve, seed, reached);
+    for (bool r : reached) CHECK(r);
+  }
+  // the refusals: a history the gather's 32-bit sizes cannot carry; segments the gather forms leave to the copy commands
+  WindowBook far;
+  far.avail = int64_t(1) << 32;
+  CHECK(plan_window(far, false, 0, 16, 256).refused != nullptr && plan_window(far, false, 2, 16, 256).refused == nullptr);
+  CHECK(gather_fits((size_t(1) << 32) - 1) && !gather_fits(size_t(1) << 32));
+  CHECK(window_bytes(256, 0) == 272 && window_bytes(256, 16) == 272 && window_bytes(256, 18) == 274);
+}
+
+// The dealing rule (placement.hpp: Deal): contiguous slices that cover [0, B), sizes that differ by at most one with the larger ones first, and the
+// inverse that dabhip_multi_plan answers with before any decode
+static void test_deal()
+{
+  for (int n = 1; n <= 9; ++n)
+    for (int B = 1; B <= 40; ++B) {
+      const Deal d{B, n};
+      int next = 0;
+      for (int i = 0; i < n; ++i) {
+        CHECK(d.first(i) == next && d.count(i) >= 0);
+        CHECK(d.count(i) == B / n || d.count(i) == B / n + 1);
+        if (i) CHECK(d.count(i) <= d.count(i - 1));
+        for (int b = d.first(i); b < d.first(i) + d.count(i); ++b) CHECK(d.slice_of(b) == i);
+        next += d.count(i);
+      }
+      CHECK(next == B);
+    }
+  const Deal node{2048, 8}, small{10, 4};       // the examples of multi.cpp's header
+  for (int i = 0; i < 8; ++i) CHECK(node.count(i) == 256 && node.first(i) == 256 * i);
+  for (int s = 0; s < 2048; ++s) CHECK(node.slice_of(s) == s / 256);
+  const int want[4] = {3, 3, 2, 2};
+  for (int i = 0; i < 4; ++i) CHECK(small.count(i) == want[i]);
+  CHECK(small.slice_of(5) == 1 && small.slice_of(6) == 2 && small.slice_of(9) == 3);
+}
+
 static void test_synth()
 {
   for (int preset = 0; preset < 2; ++preset) {
@@ -662,8 +793,8 @@ int main(int argc, char** argv)
 {
   const char* only = argc > 1 ? argv[1] : "";
   struct { const char* name; void (*fn)(); } tests[] = {
-      {"pool", test_pool_and_lane}, {"worklist", test_control_and_worklist}, {"fifo", test_fifo_views}, {"synth", test_synth},
-      {"layout", test_layout}, {"carry", test_carry}, {"forms", test_forms}, {"scan", test_scan}};
+      {"pool", test_pool_and_lane}, {"worklist", test_control_and_worklist}, {"fifo", test_fifo}, {"synth", test_synth},
+      {"layout", test_layout}, {"carry", test_carry}, {"forms", test_forms}, {"scan", test_scan}, {"windows", test_windows}, {"deal", test_deal}};
   for (const auto& t : tests) {
     if (*only && std::strcmp(only, t.name) != 0) continue;
     t.fn();

@@ -1,5 +1,5 @@
 """The host-only units of the product (thread pool + host lane, control plane, work-list build, closed-form FIFO, modulator, the frame layout and
-session carry of a decode, the decoder-form rule, the K1 scan's schedule) compiled
+session carry of a decode, the decoder-form rule, the K1 scan's schedule, a session's windows, the dealing rule, the GPU-free C entries) compiled
 with g++ -fsanitize=thread and -fsanitize=address,undefined and run (tests/host_sanitize/host_units.cpp).  CPU build only: GPU
 sanitizers are not available on this pool, and none of these units makes a GPU call.  SURVEY.md section 5, "Race detection /
 sanitizers" (the reference has none; its own race is dab2eti.c:117-130)."""
@@ -27,4 +27,5 @@ def test_host_units_under_sanitizer(flavour, env):
     run = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=dict(os.environ, **env), timeout=600)
     assert run.returncode == 0, (run.stdout + run.stderr)[-4000:]
     assert "Sanitizer" not in run.stderr, run.stderr[-4000:]
-    assert run.stdout.split() == ["ok", "pool", "ok", "worklist", "ok", "fifo", "ok", "synth", "ok", "layout", "ok", "carry", "ok", "forms", "ok", "scan"]
+    assert run.stdout.split() == ["ok", "pool", "ok", "worklist", "ok", "fifo", "ok", "synth", "ok", "layout", "ok", "carry", "ok", "forms", "ok", "scan",
+                                  "ok", "windows", "ok", "deal"]
