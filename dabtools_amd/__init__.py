@@ -257,6 +257,17 @@ _SIGNATURES = {
     "dabhip_stream_set_demod_all": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_stream_msc_deferred": (C.c_int, [C.c_void_p]),
     "dabhip_host_lockin_deferred": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "dabhip_ingest_create": (C.c_void_p, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_uint32]),
+    "dabhip_ingest_destroy": (None, [C.c_void_p]),
+    "dabhip_ingest_push": (C.c_int64, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int]),
+    "dabhip_ingest_output": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "dabhip_ingest_read": (C.c_int64, [C.c_void_p, C.c_int, u8p, C.c_size_t]),
+    "dabhip_ingest_gain": (C.c_uint32, [C.c_void_p, C.c_int]),
+    "dabhip_ingest_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
+    "dabhip_ingest_skip": (C.c_int, [C.c_void_p, C.c_int64]),
+    "dabhip_ingest_taps": (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_int16), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dabhip_ingest_plan": (C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "dabhip_ingest_auto_gain": (C.c_uint32, [C.c_uint64]),
 }
 
 _lib = None
@@ -833,6 +844,116 @@ class DabPlus:
     def close(self):
         if getattr(self, "_h", None):
             lib().dabhip_dabplus_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- ingest stage: other sample formats and rates -> cu8 at 2.048 Msps (dabhip.h: dabhip_ingest_*) -----------------
+INGEST_FORMATS = {"cu8": 0, "cs8": 1, "cs16": 2, "cf32": 3}
+INGEST_DTYPES = {"cu8": np.uint8, "cs8": np.int8, "cs16": np.dtype("<i2"), "cf32": np.dtype("<f4")}
+INGEST_GAIN_WINDOW = 65536
+
+
+def _ingest_format(fmt):
+    if isinstance(fmt, str):
+        if fmt not in INGEST_FORMATS:
+            raise DabhipError("ingest: unknown format %r (cu8, cs8, cs16, cf32)" % fmt)
+        return INGEST_FORMATS[fmt]
+    return int(fmt)
+
+
+def ingest_taps(fmt, rate):
+    """(taps [L][T] int16 in Q14, L, M, T) of a sample rate (dabhip_ingest_taps; no GPU needed).  L/M = 1/1: an empty table, T = 0."""
+    L, M, T = C.c_int(0), C.c_int(0), C.c_int(0)
+    n = lib().dabhip_ingest_taps(_ingest_format(fmt), int(rate), None, 0, C.byref(L), C.byref(M), C.byref(T))
+    _need(n >= 0, "ingest_taps")
+    taps = np.zeros(n, dtype=np.int16)
+    if n:
+        _need(lib().dabhip_ingest_taps(_ingest_format(fmt), int(rate), taps.ctypes.data_as(C.POINTER(C.c_int16)), n, None, None, None) == n, "ingest_taps")
+    return taps.reshape(L.value, T.value), L.value, M.value, T.value
+
+
+def ingest_plan(rate, pushes, auto_gain=False):
+    """The bookkeeping of one stream over pushes of `pushes` samples: (output samples completed per push, input samples carried behind each)."""
+    n = len(pushes)
+    src = (C.c_int64 * max(n, 1))(*[int(v) for v in pushes])
+    nout, keep = (C.c_int64 * max(n, 1))(), (C.c_int64 * max(n, 1))()
+    _need(lib().dabhip_ingest_plan(int(rate), 1 if auto_gain else 0, src, n, nout, keep) == 0, "ingest_plan")
+    return list(nout)[:n], list(keep)[:n]
+
+
+def ingest_auto_gain(energy):
+    """The automatic gain of an energy sum(I^2 + Q^2) over the first 65536 samples in the 16-bit domain (dabhip.h, step 4)."""
+    return lib().dabhip_ingest_auto_gain(int(energy))
+
+
+class Ingest:
+    """nstreams streams of fmt ("cu8", "cs8", "cs16", "cf32") IQ at `rate` samples/s -> cu8 at 2.048 Msps in device memory (dabhip_ingest_*).
+    gain: the requantisation gain (256 = 16-bit full scale to 8-bit full scale), 0 = automatic.  State carries from push to push."""
+
+    def __init__(self, device, nstreams, fmt, rate, gain=0):
+        self.nstreams, self.fmt = int(nstreams), _ingest_format(fmt)
+        self._h = lib().dabhip_ingest_create(int(device), self.nstreams, self.fmt, int(rate), int(gain))
+        _need(self._h, "ingest_create")
+
+    def push(self, arrays):
+        """One array per stream (any dtype: its bytes are the samples, possibly none) -> total output bytes of this push."""
+        _need(len(arrays) == self.nstreams, "ingest_push: one array per stream")
+        arrs = [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in arrays]
+        self._keep = arrs
+        return self.push_ptrs([a.ctypes.data for a in arrs], [a.size for a in arrs], on_device=False)
+
+    def push_ptrs(self, ptrs, sizes, on_device=False):
+        """push() over raw addresses: host memory, or device memory aligned to a sample."""
+        p = (C.c_void_p * len(ptrs))(*ptrs)
+        s = (C.c_size_t * len(sizes))(*sizes)
+        _need(len(ptrs) == self.nstreams and len(sizes) == self.nstreams, "ingest_push: one input per stream")
+        n = lib().dabhip_ingest_push(self._h, p, s, 1 if on_device else 0)
+        _need(n >= 0, "ingest_push")
+        return n
+
+    def output_ptrs(self):
+        """(device addresses, byte counts) of this push's cu8, per stream: what Engine.decode_device and Stream.feed_ptrs(on_device=True) take.
+        Valid until the next push."""
+        ptrs, sizes = [], []
+        for b in range(self.nstreams):
+            p, n = C.c_void_p(0), C.c_size_t(0)
+            _need(lib().dabhip_ingest_output(self._h, b, C.byref(p), C.byref(n)) == 0, "ingest_output")
+            ptrs.append(p.value or 0)
+            sizes.append(n.value)
+        return ptrs, sizes
+
+    def read(self, stream):
+        """This push's cu8 of one stream as a numpy array."""
+        p, n = C.c_void_p(0), C.c_size_t(0)
+        _need(lib().dabhip_ingest_output(self._h, stream, C.byref(p), C.byref(n)) == 0, "ingest_output")
+        out = np.zeros(n.value, dtype=np.uint8)
+        _need(lib().dabhip_ingest_read(self._h, stream, _p(out), out.size) == out.size, "ingest_read")
+        return out
+
+    def gain(self, stream):
+        """The stream's gain; 0 while its automatic-gain window is open."""
+        return lib().dabhip_ingest_gain(self._h, stream)
+
+    def skip(self, n):
+        """Test knob (explicit gain only): as if n zero samples had been pushed to every stream and their outputs discarded."""
+        _need(lib().dabhip_ingest_skip(self._h, int(n)) == 0, "ingest_skip")
+
+    def stage_ms(self):
+        """GPU time of the last push per stage: {"upload", "energy", "resample", "keep"} in ms."""
+        names = (C.c_char_p * 4)()
+        ms = (C.c_float * 4)()
+        n = lib().dabhip_ingest_stage_ms(self._h, names, ms, 4)
+        return {names[i].decode(): ms[i] for i in range(n)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().dabhip_ingest_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -1,5 +1,5 @@
 // capi_host.cpp — the entries of the C ABI (include/dabhip.h) that need no GPU: the host-side control plane, the constant tables, the parity guard's
-// constants, K1's FIFO bookkeeping, the CPU budget and the placement plan -- what the CPU test-suite compares with the reference.  No HIP runtime call
+// constants, K1's FIFO bookkeeping, the ingest stage's tap table and bookkeeping, the CPU budget and the placement plan -- what the CPU test-suite compares with the reference.  No HIP runtime call
 // in here: tests/host_sanitize links this file as it is.
 #include <cstring>
 #include <new>
@@ -11,6 +11,7 @@
 #include "dab_tables.hpp"
 #include "device_types.hpp"
 #include "fifo_view.hpp"
+#include "ingest_plan.hpp"
 #include "placement.hpp"
 
 using namespace dabhip;
@@ -195,3 +196,44 @@ extern "C" int dabhip_host_fifo_skip_unshifted(dabhip_fifo* f, int32_t ncalls, i
   if (consumed) *consumed = f->st.consumed;
   return 0;
 }
+
+// ---- the ingest stage's host rule (ingest_plan.hpp): the tap table of a rate and the bookkeeping of a sequence of pushes ----
+extern "C" int dabhip_ingest_taps(int format, int64_t rate_hz, int16_t* taps, int cap, int* L, int* M, int* T)
+{
+  if (format < 0 || format >= kIngestFormats) { set_error("ingest_taps: unknown format " + std::to_string(format) + " (0 = cu8, 1 = cs8, 2 = cs16, 3 = cf32)"); return -1; }
+  IngestRatio r;
+  const std::string why = ingest_ratio(rate_hz, &r);
+  if (!why.empty()) { set_error("ingest_taps: " + why); return -1; }
+  if (L) *L = r.L;
+  if (M) *M = r.M;
+  if (T) *T = r.T;
+  const int n = r.L * r.T;
+  if (r.bypass()) return 0;
+  const std::vector<int16_t> t = ingest_design_taps(r, rate_hz);
+  const std::string bad = ingest_check_taps(r, t.data());
+  if (!bad.empty()) { set_error("ingest_taps: " + bad); return -1; }
+  if (taps) {
+    if (cap < n) { set_error("ingest_taps: buffer too small"); return -1; }
+    std::memcpy(taps, t.data(), static_cast<size_t>(n) * sizeof(int16_t));
+  }
+  return n;
+}
+
+extern "C" int dabhip_ingest_plan(int64_t rate_hz, int auto_gain, const int64_t* push_samples, int npush, int64_t* nout, int64_t* carried)
+{
+  if (!push_samples || npush < 0 || !nout || !carried) { set_error("ingest_plan: bad argument"); return -1; }
+  IngestRatio r;
+  const std::string why = ingest_ratio(rate_hz, &r);
+  if (!why.empty()) { set_error("ingest_plan: " + why); return -1; }
+  IngestStreamState s;
+  s.window_open = auto_gain != 0;
+  for (int i = 0; i < npush; ++i) {
+    if (push_samples[i] < 0) { set_error("ingest_plan: negative push"); return -1; }
+    const IngestPush p = ingest_plan_push(r, s, push_samples[i]);
+    nout[i] = p.nout;
+    carried[i] = p.keep;
+  }
+  return 0;
+}
+
+extern "C" uint32_t dabhip_ingest_auto_gain(uint64_t energy) { return ingest_auto_gain(energy); }

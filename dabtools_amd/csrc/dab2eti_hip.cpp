@@ -8,6 +8,9 @@
 //   dab2eti-hip --stream [--segment-calls N] huge.cu8 > ensemble.eti
 //   dab2eti-hip --stream --devices 0-7 cap0000.cu8 ... cap2047.cu8 > all.eti  (sessions on several devices: dabhip_multi_stream)
 //
+//   hackrf_transfer -r - -s 8000000 ... | dab2eti-hip --format cs8 --rate 8000000 - > ensemble.eti
+//   dab2eti-hip --format cs16 --rate 2400000 [--gain G] airspy.cs16 > ensemble.eti   (other formats and rates: the ingest stage, dabhip_ingest_*, one device)
+//
 // Streaming mode (any input "-", or --stream) decodes unbounded input in segments of N 262,144-byte calls through a dabhip_stream session (on several
 // devices: a dabhip_multi_stream, the inputs dealt to the devices in contiguous slices): reader threads fill page-locked buffers while the GPU decodes an
 // earlier one and the one in between uploads (dabhip_stream_prefetch), frames leave as soon as their segment is done, memory stays bounded, output bytes are
@@ -293,6 +296,114 @@ int run_streaming(const std::vector<const char*>& names, size_t seg_bytes, bool 
   ses.destroy();
   return 0;
 }
+
+// ---- other sample formats and rates: the ingest stage in front of the decoder (dabhip_ingest_*), on one device -------------------------------
+struct IngestOpts {
+  int format = DABHIP_INGEST_CU8;
+  long long rate = 2048000;
+  long long gain = -1;                           // -1: not given (the automatic gain)
+  bool on() const { return format != DABHIP_INGEST_CU8 || rate != 2048000 || gain >= 0; }
+};
+int sample_bytes_of(int format) { return format == DABHIP_INGEST_CS16 ? 4 : format == DABHIP_INGEST_CF32 ? 8 : 2; }
+
+// Batch: every file in one push, the decoder reads the stage's output where it lies.  Streaming: segments of about seg_bytes of OUTPUT per input; a
+// read that ends inside a sample carries the remainder to the next push.  Frames leave stream by stream within a segment, as without the stage.
+int run_ingest(const std::vector<const char*>& names, bool streaming, size_t seg_bytes, const IngestOpts& opt, int device, bool afc, bool soft, const std::vector<int32_t>& subch)
+{
+  const int n = static_cast<int>(names.size());
+  const size_t sb = static_cast<size_t>(sample_bytes_of(opt.format));
+  dabhip_ingest* ing = dabhip_ingest_create(device, n, opt.format, opt.rate, opt.gain < 0 ? 0u : static_cast<uint32_t>(opt.gain));
+  if (!ing) { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); return 2; }
+  std::vector<const void*> src(static_cast<size_t>(n));
+  std::vector<size_t> nbytes(static_cast<size_t>(n));
+  std::vector<const uint8_t*> out(static_cast<size_t>(n));
+  std::vector<size_t> out_bytes(static_cast<size_t>(n));
+  std::vector<long long> total(static_cast<size_t>(n), 0);
+  std::vector<uint8_t> frames;
+  auto fail = [&]() { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); return 2; };
+  auto outputs = [&]() {
+    for (int i = 0; i < n; ++i)
+      if (dabhip_ingest_output(ing, i, &out[static_cast<size_t>(i)], &out_bytes[static_cast<size_t>(i)]) != 0) return false;
+    return true;
+  };
+  if (!streaming) {
+    std::vector<Mapped> files(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) {
+      if (!map_file(names[i], &files[static_cast<size_t>(i)])) return 1;
+      src[static_cast<size_t>(i)] = files[static_cast<size_t>(i)].p;
+      nbytes[static_cast<size_t>(i)] = files[static_cast<size_t>(i)].n / sb * sb;        // a file that ends inside a sample: the whole samples
+    }
+    dabhip_engine* e = dabhip_engine_create(device);
+    if (!e) return fail();
+    if (afc) dabhip_engine_set_afc(e, 1);
+    if (soft) dabhip_engine_set_soft(e, 1);
+    if (g_soft_lanes) dabhip_engine_set_soft_lanes(e, 1);
+    if (!subch.empty()) dabhip_engine_set_subchannels(e, subch.data(), static_cast<int>(subch.size()));
+    if (dabhip_ingest_push(ing, src.data(), nbytes.data(), 0) < 0 || !outputs()) return fail();
+    const int64_t nframes = dabhip_engine_decode(e, out.data(), out_bytes.data(), n, 1);
+    if (nframes < 0) return fail();
+    for (int i = 0; i < n; ++i) {
+      std::fprintf(stderr, "%s: %lld ETI frames\n", names[i], static_cast<long long>(dabhip_engine_eti_count(e, i)));
+      char text[8192];
+      if (!g_quiet && dabhip_engine_stream_log(e, i, text, sizeof text) > 0) print_log(text, names[i], n > 1);
+    }
+    if (dabhip_engine_eti_drain(e, to_stdout, nullptr) != nframes) return fail();
+    flush_stdout();
+    dabhip_engine_destroy(e);
+    dabhip_ingest_destroy(ing);
+    return 0;
+  }
+  std::vector<FILE*> in(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) {
+    in[static_cast<size_t>(i)] = std::strcmp(names[i], "-") == 0 ? stdin : std::fopen(names[i], "rb");
+    if (!in[static_cast<size_t>(i)]) { std::perror(names[i]); return 1; }
+  }
+  dabhip_stream* s = dabhip_stream_create(device, n);
+  if (!s) return fail();
+  if (afc) dabhip_stream_set_afc(s, 1);
+  if (soft) dabhip_stream_set_soft(s, 1);
+  if (g_soft_lanes) dabhip_stream_set_soft_lanes(s, 1);
+  if (!subch.empty()) dabhip_stream_set_subchannels(s, subch.data(), static_cast<int>(subch.size()));
+  // input bytes that give about seg_bytes of output: seg_bytes / 2 output samples are seg_bytes / 2 * rate / 2048000 input samples
+  const size_t seg_in = static_cast<size_t>((static_cast<unsigned long long>(seg_bytes / 2) * static_cast<unsigned long long>(opt.rate) + 2047999) / 2048000) * sb;
+  std::vector<std::vector<uint8_t>> buf(static_cast<size_t>(n), std::vector<uint8_t>(seg_in + sb));
+  std::vector<size_t> rem(static_cast<size_t>(n), 0);                                    // bytes of a sample cut by the read before
+  std::vector<bool> eof(static_cast<size_t>(n), false);
+  for (bool more = true; more;) {
+    more = false;
+    for (int i = 0; i < n; ++i) {
+      std::vector<uint8_t>& b = buf[static_cast<size_t>(i)];
+      size_t have = rem[static_cast<size_t>(i)];
+      while (!eof[static_cast<size_t>(i)] && have < seg_in) {
+        const size_t got = std::fread(b.data() + have, 1, seg_in - have, in[static_cast<size_t>(i)]);
+        if (got == 0) eof[static_cast<size_t>(i)] = true;
+        have += got;
+      }
+      src[static_cast<size_t>(i)] = b.data();
+      nbytes[static_cast<size_t>(i)] = have / sb * sb;
+      rem[static_cast<size_t>(i)] = have - nbytes[static_cast<size_t>(i)];
+      more = more || !eof[static_cast<size_t>(i)];
+    }
+    if (dabhip_ingest_push(ing, src.data(), nbytes.data(), 0) < 0 || !outputs()) return fail();
+    const int64_t nframes = dabhip_stream_feed(s, out.data(), out_bytes.data(), 1);
+    if (nframes < 0) return fail();
+    for (int i = 0; i < n; ++i) {
+      const int64_t c = dabhip_stream_eti_count(s, i);
+      frames.resize(static_cast<size_t>(c) * DABHIP_ETI_BYTES);
+      if (c > 0 && dabhip_stream_eti_read(s, i, frames.data(), c) != c) return fail();
+      write_all(frames.data(), frames.size());
+      total[static_cast<size_t>(i)] += c;
+      char text[8192];
+      if (!g_quiet && dabhip_stream_log(s, i, text, sizeof text) > 0) print_log(text, names[i], n > 1);
+      std::vector<uint8_t>& b = buf[static_cast<size_t>(i)];                             // the cut sample's first bytes to the front
+      std::memmove(b.data(), b.data() + nbytes[static_cast<size_t>(i)], rem[static_cast<size_t>(i)]);
+    }
+  }
+  for (int i = 0; i < n; ++i) std::fprintf(stderr, "%s: %lld ETI frames\n", names[i], total[static_cast<size_t>(i)]);
+  dabhip_stream_destroy(s);
+  dabhip_ingest_destroy(ing);
+  return 0;
+}
 }  // namespace
 
 int main(int argc, char** argv)
@@ -302,8 +413,27 @@ int main(int argc, char** argv)
   std::vector<int32_t> subch;                  // --subch 3,7: decode and carry only these SubChIds (TODO.md:28-31)
   std::vector<int> devices;                    // --devices 0-7 | 0,2,3 | 0,0 (an entry per slice; repeats allowed): dabhip_multi
   std::vector<const char*> names;
+  IngestOpts ingest;                           // --format / --rate / --gain: the ingest stage (off without them)
   for (int i = 1; i < argc; ++i) {
     if (std::strcmp(argv[i], "--stream") == 0) streaming = true;
+    else if (std::strcmp(argv[i], "--format") == 0 && i + 1 < argc) {
+      static const char* const kFormats[4] = {"cu8", "cs8", "cs16", "cf32"};
+      ingest.format = -1;
+      ++i;
+      for (int f = 0; f < 4; ++f)
+        if (std::strcmp(argv[i], kFormats[f]) == 0) ingest.format = f;
+      if (ingest.format < 0) { std::fprintf(stderr, "dab2eti-hip: unknown --format %s (cu8, cs8, cs16, cf32)\n", argv[i]); return 1; }
+    }
+    else if (std::strcmp(argv[i], "--rate") == 0 && i + 1 < argc) {
+      char* end = nullptr;
+      ingest.rate = std::strtoll(argv[++i], &end, 10);
+      if (end == argv[i] || *end || ingest.rate <= 0) { std::fprintf(stderr, "dab2eti-hip: --rate takes a whole number of samples per second\n"); return 1; }
+    }
+    else if (std::strcmp(argv[i], "--gain") == 0 && i + 1 < argc) {
+      char* end = nullptr;
+      ingest.gain = std::strtoll(argv[++i], &end, 10);
+      if (end == argv[i] || *end || ingest.gain < 0 || ingest.gain >= (1 << 24)) { std::fprintf(stderr, "dab2eti-hip: --gain takes 1 .. 16777215 (0 = automatic)\n"); return 1; }
+    }
     else if (std::strcmp(argv[i], "--stats") == 0) g_stats = true;
     else if (std::strcmp(argv[i], "--quiet") == 0) g_quiet = true;
     else if (std::strcmp(argv[i], "--afc") == 0) afc = true;          // software AFC: captures with a carrier offset (no tuner to steer)
@@ -333,7 +463,11 @@ int main(int argc, char** argv)
     else { names.push_back(argv[i]); streaming = streaming || std::strcmp(argv[i], "-") == 0; }
   }
   if (names.empty()) {
-    std::fprintf(stderr, "Usage: dab2eti-hip [--stream] [--segment-calls N] [--afc] [--soft] [--soft-lanes] [--quiet] [--subch ID[,ID...]] [--devices A-B|A,B,...] capture.cu8|- [more.cu8 ...] > out.eti\n");
+    std::fprintf(stderr, "Usage: dab2eti-hip [--stream] [--segment-calls N] [--afc] [--soft] [--soft-lanes] [--quiet] [--subch ID[,ID...]] [--devices A-B|A,B,...] [--format cu8|cs8|cs16|cf32] [--rate HZ] [--gain G] capture.cu8|- [more.cu8 ...] > out.eti\n");
+    return 1;
+  }
+  if (ingest.on() && devices.size() > 1) {
+    std::fprintf(stderr, "dab2eti-hip: --format / --rate / --gain run on one device: the ingest stage does not span --devices\n");
     return 1;
   }
   if (streaming) {
@@ -345,8 +479,10 @@ int main(int argc, char** argv)
       }
       seg_calls = live ? 2 : 64;
     }
+    if (ingest.on()) return run_ingest(names, true, seg_calls * 262144, ingest, devices.empty() ? 0 : devices[0], afc, soft, subch);
     return run_streaming(names, seg_calls * 262144, afc, soft, subch, devices);
   }
+  if (ingest.on()) return run_ingest(names, false, 0, ingest, devices.empty() ? 0 : devices[0], afc, soft, subch);
   argc = static_cast<int>(names.size()) + 1;
   for (int i = 1; i < argc; ++i) argv[i] = const_cast<char*>(names[i - 1]);
   const double t_start = now_s();

@@ -1,0 +1,242 @@
+// ingest.cpp — the ingest stage's host object (include/dabhip.h: dabhip_ingest): per stream the positions and the carried samples, per push the
+// plan (ingest_plan.hpp), the uploads, the energy reduction of the streams whose gain window closes, and one launch of k_ingest.hip's kernel
+// for all streams.  Every push ends in a stream synchronise (engine.hpp: what the runtime keeps of a stream that nobody synchronises).
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "capi_detail.hpp"
+#include "engine.hpp"
+#include "ingest.hpp"
+#include "ingest_plan.hpp"
+
+using namespace dabhip;
+
+struct dabhip_ingest {
+  int device = 0, nstreams = 0, format = 0, sample_bytes = 0;
+  IngestRatio ratio;
+  bool auto_gain = false;
+  std::vector<IngestStreamState> st;
+  std::vector<uint32_t> gain;                    // 0 while a stream's window is open
+  DeviceBuffer<uint32_t> table;
+  DeviceBuffer<uint8_t> carry[2], stage, out;
+  DeviceBuffer<IngestDesc> descs;
+  DeviceBuffer<unsigned long long> energy;
+  size_t carry_stride = 0;
+  int cur = 0;                                   // carry[cur] holds what the last push kept
+  std::vector<size_t> out_off, out_bytes;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[5] = {};
+  float ms[4] = {0, 0, 0, 0};
+  ~dabhip_ingest()
+  {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+namespace {
+bool ok(hipError_t e, const char* what)
+{
+  if (e == hipSuccess) return true;
+  set_error(std::string("ingest: ") + what + ": " + hipGetErrorString(e));
+  return false;
+}
+size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// the push proper: nsamples[b] samples of stream b at src[b] (device memory, aligned to a sample).  Returns the output bytes, < 0 on error.
+int64_t push_device(dabhip_ingest* d, const std::vector<const void*>& src, const std::vector<int64_t>& nsamples, bool uploaded)
+{
+  const int ns = d->nstreams;
+  std::vector<IngestStreamState> next = d->st;
+  std::vector<IngestPush> plan(static_cast<size_t>(ns));
+  std::vector<IngestDesc> h(static_cast<size_t>(ns));
+  size_t out_total = 0;
+  int64_t max_nout = 0, max_keep = 0;
+  bool closing = false;
+  for (int b = 0; b < ns; ++b) {
+    const IngestPush p = plan[static_cast<size_t>(b)] = ingest_plan_push(d->ratio, next[static_cast<size_t>(b)], nsamples[static_cast<size_t>(b)]);
+    if (p.nout > (int64_t(1) << 30)) { set_error("ingest_push: more than 2^30 output samples of one stream in one push"); return -1; }
+    if (static_cast<size_t>(p.keep) * d->sample_bytes > d->carry_stride) { set_error("ingest_push: internal: the carry outgrew its buffer"); return -1; }
+    d->out_off[static_cast<size_t>(b)] = out_total;
+    out_total += round_up(static_cast<size_t>(p.nout) * 2, 256);
+    max_nout = std::max(max_nout, p.nout);
+    max_keep = std::max(max_keep, p.keep);
+    closing = closing || p.closes;
+  }
+  if (!d->out.reserve(out_total ? out_total : 1) || !d->descs.reserve(static_cast<size_t>(ns)) || !d->energy.reserve(static_cast<size_t>(ns))) return -1;
+  for (int b = 0; b < ns; ++b) {
+    const IngestPush& p = plan[static_cast<size_t>(b)];
+    IngestDesc& x = h[static_cast<size_t>(b)];
+    x.carry = d->carry[d->cur].get() + static_cast<size_t>(b) * d->carry_stride;
+    x.keep = d->carry[d->cur ^ 1].get() + static_cast<size_t>(b) * d->carry_stride;
+    x.src = src[static_cast<size_t>(b)];
+    x.out = d->out.get() + d->out_off[static_cast<size_t>(b)];
+    x.carry_from = p.carry_from;
+    x.new_from = p.new_from;
+    x.end = p.end;
+    x.first_out = p.first_out;
+    x.keep_from = p.keep_from;
+    x.nout = static_cast<int32_t>(p.nout);
+    x.gain = d->gain[static_cast<size_t>(b)];
+    x.energy_slot = p.closes ? b : -1;
+    x.pad = 0;
+  }
+  hipStream_t st = d->stream;
+  std::vector<uint32_t> gain = d->gain;
+  if (!uploaded && !ok(hipEventRecord(d->ev[0], st), "event")) return -1;
+  if (!ok(hipEventRecord(d->ev[1], st), "event")) return -1;
+  if (closing) {
+    std::vector<unsigned long long> e(static_cast<size_t>(ns), 0);
+    if (!ok(hipMemcpyAsync(d->descs.get(), h.data(), h.size() * sizeof(IngestDesc), hipMemcpyHostToDevice, st), "descriptors") ||
+        !ok(launch_ingest_energy(d->format, d->descs.get(), ns, d->energy.get(), st), "energy launch") ||
+        !ok(hipMemcpyAsync(e.data(), d->energy.get(), e.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "energy") ||
+        !ok(hipStreamSynchronize(st), "energy"))
+      return -1;
+    for (int b = 0; b < ns; ++b)
+      if (plan[static_cast<size_t>(b)].closes) h[static_cast<size_t>(b)].gain = gain[static_cast<size_t>(b)] = ingest_auto_gain(e[static_cast<size_t>(b)]);
+  }
+  if (!ok(hipEventRecord(d->ev[2], st), "event") ||
+      !ok(hipMemcpyAsync(d->descs.get(), h.data(), h.size() * sizeof(IngestDesc), hipMemcpyHostToDevice, st), "descriptors") ||
+      !ok(launch_ingest_resample(d->format, d->descs.get(), ns, static_cast<int>(max_nout), d->table.get(), d->ratio.L, d->ratio.M, d->ratio.T, st), "resample launch") ||
+      !ok(hipEventRecord(d->ev[3], st), "event") || !ok(launch_ingest_keep(d->format, d->descs.get(), ns, max_keep, st), "keep launch") ||
+      !ok(hipEventRecord(d->ev[4], st), "event") || !ok(hipStreamSynchronize(st), "push"))
+    return -1;
+  for (int k = 0; k < 4; ++k)
+    if (!ok(hipEventElapsedTime(&d->ms[k], d->ev[k], d->ev[k + 1]), "hipEventElapsedTime")) return -1;
+  d->st = next;
+  d->gain = gain;
+  d->cur ^= 1;
+  int64_t total = 0;
+  for (int b = 0; b < ns; ++b) total += static_cast<int64_t>(d->out_bytes[static_cast<size_t>(b)] = static_cast<size_t>(plan[static_cast<size_t>(b)].nout) * 2);
+  return total;
+}
+}  // namespace
+
+extern "C" dabhip_ingest* dabhip_ingest_create(int device, int nstreams, int format, int64_t rate_hz, uint32_t gain)
+{
+  if (nstreams <= 0 || nstreams > 65535) { set_error("ingest_create: nstreams must be 1 .. 65535"); return nullptr; }
+  if (format < 0 || format >= kIngestFormats) { set_error("ingest_create: unknown format " + std::to_string(format) + " (0 = cu8, 1 = cs8, 2 = cs16, 3 = cf32)"); return nullptr; }
+  if (gain > kIngestMaxGain) { set_error("ingest_create: gain must be below 2^24 (0 = automatic)"); return nullptr; }
+  IngestRatio r;
+  const std::string why = ingest_ratio(rate_hz, &r);
+  if (!why.empty()) { set_error("ingest_create: " + why); return nullptr; }
+  std::vector<uint32_t> words(r.lds_table_bytes() / 4 + 2, 0);
+  if (!r.bypass()) {
+    const std::vector<int16_t> taps = ingest_design_taps(r, rate_hz);
+    const std::string bad = ingest_check_taps(r, taps.data());
+    if (!bad.empty()) { set_error("ingest_create: " + bad); return nullptr; }
+    for (int p = 0; p < r.L; ++p)                  // reversed, in pairs, rows padded by a word (ingest.hpp)
+      for (int j = 0; j < r.T / 2; ++j) {
+        const uint16_t lo = static_cast<uint16_t>(taps[static_cast<size_t>(p) * r.T + (r.T - 1 - 2 * j)]), hi = static_cast<uint16_t>(taps[static_cast<size_t>(p) * r.T + (r.T - 2 - 2 * j)]);
+        words[static_cast<size_t>(p) * r.lds_row_words() + j] = lo | static_cast<uint32_t>(hi) << 16;
+      }
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); set_error("ingest_create: no HIP device"); return nullptr; }
+  if (!ok(hipSetDevice(device), "hipSetDevice")) return nullptr;
+  dabhip_ingest* d = new (std::nothrow) dabhip_ingest;
+  if (!d) return nullptr;
+  d->device = device;
+  d->nstreams = nstreams;
+  d->format = format;
+  d->sample_bytes = ingest_sample_bytes(format);
+  d->ratio = r;
+  d->auto_gain = gain == 0;
+  d->st.assign(static_cast<size_t>(nstreams), IngestStreamState{});
+  for (auto& s : d->st) s.window_open = d->auto_gain;
+  d->gain.assign(static_cast<size_t>(nstreams), gain);
+  d->out_off.assign(static_cast<size_t>(nstreams), 0);
+  d->out_bytes.assign(static_cast<size_t>(nstreams), 0);
+  d->carry_stride = round_up(static_cast<size_t>(d->auto_gain ? kIngestGainWindow : std::max(r.T, 1)) * d->sample_bytes, 16);
+  bool good = ok(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking), "hipStreamCreate");
+  for (hipEvent_t& e : d->ev) good = good && ok(hipEventCreate(&e), "hipEventCreate");
+  good = good && d->table.reserve(words.size()) && d->carry[0].reserve(d->carry_stride * nstreams) && d->carry[1].reserve(d->carry_stride * nstreams) &&
+         ok(hipMemcpyAsync(d->table.get(), words.data(), words.size() * 4, hipMemcpyHostToDevice, d->stream), "table upload") &&
+         ok(hipStreamSynchronize(d->stream), "table upload");
+  if (!good) { delete d; return nullptr; }
+  return d;
+}
+
+extern "C" void dabhip_ingest_destroy(dabhip_ingest* d) { delete d; }
+
+extern "C" int64_t dabhip_ingest_push(dabhip_ingest* d, const void* const* src, const size_t* nbytes, int on_device)
+{
+  if (!d || !src || !nbytes) { set_error("ingest_push: null argument"); return -1; }
+  const int ns = d->nstreams;
+  const size_t sb = static_cast<size_t>(d->sample_bytes);
+  std::vector<const void*> dev(static_cast<size_t>(ns), nullptr);
+  std::vector<int64_t> nsamples(static_cast<size_t>(ns), 0);
+  size_t stage_total = 0;
+  for (int b = 0; b < ns; ++b) {
+    if (nbytes[b] % sb) { set_error("ingest_push: stream " + std::to_string(b) + ": " + std::to_string(nbytes[b]) + " bytes are no whole number of " + std::to_string(sb) + "-byte samples"); return -1; }
+    if (nbytes[b] && !src[b]) { set_error("ingest_push: null input"); return -1; }
+    if (on_device && nbytes[b] && reinterpret_cast<uintptr_t>(src[b]) % sb) { set_error("ingest_push: a device input must be aligned to its sample size"); return -1; }
+    nsamples[static_cast<size_t>(b)] = static_cast<int64_t>(nbytes[b] / sb);
+    stage_total += round_up(nbytes[b], 16);
+  }
+  if (!ok(hipSetDevice(d->device), "hipSetDevice")) return -1;
+  if (on_device) {
+    for (int b = 0; b < ns; ++b) dev[static_cast<size_t>(b)] = src[b];
+    return push_device(d, dev, nsamples, false);
+  }
+  if (!d->stage.reserve(stage_total ? stage_total : 1) || !ok(hipEventRecord(d->ev[0], d->stream), "event")) return -1;
+  size_t at = 0;
+  for (int b = 0; b < ns; ++b) {
+    dev[static_cast<size_t>(b)] = d->stage.get() + at;
+    if (nbytes[b] && !ok(hipMemcpyAsync(d->stage.get() + at, src[b], nbytes[b], hipMemcpyHostToDevice, d->stream), "upload")) return -1;
+    at += round_up(nbytes[b], 16);
+  }
+  return push_device(d, dev, nsamples, true);
+}
+
+extern "C" int dabhip_ingest_skip(dabhip_ingest* d, int64_t n)
+{
+  if (!d || n < 0) { set_error("ingest_skip: bad argument"); return -1; }
+  if (d->auto_gain) { set_error("ingest_skip: only with an explicit gain"); return -1; }
+  const int64_t through = ingest_skip_through(d->ratio, n);
+  if (through) {                                   // samples of value 0 in the 16-bit domain: cu8's byte 127, zero bytes otherwise
+    const std::vector<uint8_t> zeros(static_cast<size_t>(through) * d->sample_bytes, d->format == 0 ? 127 : 0);
+    std::vector<const void*> src(static_cast<size_t>(d->nstreams), zeros.data());
+    const std::vector<size_t> nbytes(static_cast<size_t>(d->nstreams), zeros.size());
+    if (dabhip_ingest_push(d, src.data(), nbytes.data(), 0) < 0) return -1;
+  }
+  for (auto& s : d->st) ingest_skip_rest(d->ratio, s, n - through);
+  std::fill(d->out_bytes.begin(), d->out_bytes.end(), size_t(0));
+  return 0;
+}
+
+extern "C" int dabhip_ingest_output(const dabhip_ingest* d, int stream, const uint8_t** dev, size_t* nbytes)
+{
+  if (!d || stream < 0 || stream >= d->nstreams || !dev || !nbytes) { set_error("ingest_output: bad argument"); return -1; }
+  *dev = d->out.get() + d->out_off[static_cast<size_t>(stream)];
+  *nbytes = d->out_bytes[static_cast<size_t>(stream)];
+  return 0;
+}
+
+extern "C" int64_t dabhip_ingest_read(const dabhip_ingest* d, int stream, uint8_t* dst, size_t cap)
+{
+  if (!d || stream < 0 || stream >= d->nstreams || (!dst && cap)) { set_error("ingest_read: bad argument"); return -1; }
+  const size_t n = d->out_bytes[static_cast<size_t>(stream)];
+  if (n > cap) { set_error("ingest_read: buffer too small"); return -1; }
+  if (!ok(hipSetDevice(d->device), "hipSetDevice")) return -1;
+  if (n && !ok(blocking_copy(dst, d->out.get() + d->out_off[static_cast<size_t>(stream)], n, hipMemcpyDeviceToHost), "read")) return -1;
+  return static_cast<int64_t>(n);
+}
+
+extern "C" uint32_t dabhip_ingest_gain(const dabhip_ingest* d, int stream)
+{
+  return d && stream >= 0 && stream < d->nstreams ? d->gain[static_cast<size_t>(stream)] : 0;
+}
+
+extern "C" int dabhip_ingest_stage_ms(const dabhip_ingest* d, const char** names, float* ms, int cap)
+{
+  static const char* const kNames[4] = {"upload", "energy", "resample", "keep"};
+  if (!d || !names || !ms) { set_error("ingest_stage_ms: null argument"); return -1; }
+  for (int k = 0; k < 4 && k < cap; ++k) { names[k] = kNames[k]; ms[k] = d->ms[k]; }
+  return std::min(cap, 4);
+}

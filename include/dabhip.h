@@ -607,6 +607,55 @@ int dabhip_dabplus_stats(const dabhip_dabplus *d, int stream, int sub, int64_t *
 /* GPU time of the last push in ms, stage by stage (names: "locate", "sync", "rs", "au", "carry"; as dabhip_engine_stage_ms); returns the count. */
 int dabhip_dabplus_stage_ms(const dabhip_dabplus *d, const char **names, float *ms, int cap);
 
+/* ---- ingest stage: other sample formats and rates -> the canonical cu8 at 2.048 Msps ------------------------------
+ * Off unless asked for: a stateful object in front of the decoder that turns nstreams streams of cu8 / cs8 / cs16 / cf32 IQ (I first, little-endian)
+ * at an integer sample rate Fin into cu8 at 2,048,000 samples/s in device memory, ready for dabhip_engine_decode(..., on_device = 1) and
+ * dabhip_stream_feed(..., on_device = 1).  The arithmetic is integer and stated here in full, so the bytes are those of a plain model
+ * (tests/ingest_model.py) and do not depend on how the input is cut into pushes:
+ *  1. To the 16-bit domain (int32 x, I and Q alike): cu8 (b - 127) 256 (127: the reference's DC offset, input_sdr.c:61-62); cs8 s 256; cs16 the
+ *     value; cf32 rint(clamp(f 32768, -32768, 32767)) in fp32, ties to even, NaN -> 0.
+ *  2. Rational resampling: L/M = 2048000/Fin reduced.  Output sample m (64-bit): n0 = floor(m M / L), p = m M mod L,
+ *     acc = sum over k < T of taps[p][k] x[n0 + T/2 - k] with x[n] = 0 for n < 0, taps int16 in Q14, T even; v = (acc + 8192) >> 14 (arithmetic
+ *     shift).  Output m exists once input sample n0 + T/2 has been pushed.  L/M = 1/1 has no filter (T = 0): v = x.
+ *  3. Gain and requantisation: o = clamp(127 + ((v g + 32768) >> 16), 0, 255) in 64-bit, 1 <= g < 2^24.  g = 256 maps 16-bit full scale to 8-bit
+ *     full scale: cu8 at 2,048,000 with g = 256 is the identity.
+ *  4. Automatic gain (gain = 0 at creation; per stream, fixed for its life): E = sum(I^2 + Q^2) over the stream's first W = 65536 input samples in
+ *     the 16-bit domain (an exact uint64), g = clamp(floor(32 65536 / sqrt(E / 2W) + 0.5), 1, 2^24 - 1) in IEEE double on the host, 256 when E = 0:
+ *     32 LSB rms per rail, the level the modulator's captures decode at.  A stream's input is held back until W samples are there (32 ms of signal,
+ *     at most 512 KB per stream), so the bytes do not depend on the pushes with automatic gain either.
+ * The tap table (dabhip_ingest_taps: taps[p][k], L rows of T): a Kaiser (beta 7) windowed sinc, cut-off 1.024 MHz, T = 4 ceil(8 M / L), every phase
+ * scaled to sum 16384 with the rounding remainder on its largest tap.  Held to: every phase sums to 16384; sum |taps[p][k]| <= 65535 per phase (then
+ * |acc| < 2^31: int32 accumulators); the interleaved prototype (rate L Fin) within +-0.05 dB of DC up to 768 kHz and at or below -60 dB from 1.28 MHz.
+ * Rates: 2,048,000 <= Fin <= 10,240,000 whose reduced L is at most 1024 and whose table fits the kernel (65536 bytes as it holds it). */
+#define DABHIP_INGEST_CU8 0
+#define DABHIP_INGEST_CS8 1
+#define DABHIP_INGEST_CS16 2
+#define DABHIP_INGEST_CF32 3
+typedef struct dabhip_ingest dabhip_ingest;
+/* gain: g of step 3, or 0 for the automatic gain.  NULL on a refusal (dabhip_last_error says which) or when there is no GPU. */
+dabhip_ingest *dabhip_ingest_create(int device, int nstreams, int format, int64_t rate_hz, uint32_t gain);
+void dabhip_ingest_destroy(dabhip_ingest *d);
+/* Append nbytes[b] bytes (whole samples: refused otherwise) to stream b: host pointers, or device pointers aligned to a sample when on_device != 0.
+ * Synchronous.  Returns the output bytes of all streams, <0 on error; the outputs stay where they are until the next push. */
+int64_t dabhip_ingest_push(dabhip_ingest *d, const void *const *src, const size_t *nbytes, int on_device);
+/* This push's cu8 of one stream: one contiguous device buffer. */
+int dabhip_ingest_output(const dabhip_ingest *d, int stream, const uint8_t **dev, size_t *nbytes);
+/* The same bytes copied to the host (cap bytes at most: refused when too small); returns the byte count. */
+int64_t dabhip_ingest_read(const dabhip_ingest *d, int stream, uint8_t *dst, size_t cap);
+/* g of a stream; 0 while its gain window is open. */
+uint32_t dabhip_ingest_gain(const dabhip_ingest *d, int stream);
+/* GPU time of the last push in ms (names: "upload", "energy", "resample", "keep"; as dabhip_engine_stage_ms); returns the count. */
+int dabhip_ingest_stage_ms(const dabhip_ingest *d, const char **names, float *ms, int cap);
+/* Test knob, explicit gain only: exactly as if n samples of value 0 in the 16-bit domain (cu8: bytes of 127) had been pushed to every stream and
+ * their outputs discarded -- positions beyond 2^32 within reach of small inputs.  The last push's outputs are gone afterwards. */
+int dabhip_ingest_skip(dabhip_ingest *d, int64_t n);
+/* Without a GPU: the table of a rate (taps may be NULL: only L, M, T; cap in taps) -- returns L T, <0 on a refusal -- */
+int dabhip_ingest_taps(int format, int64_t rate_hz, int16_t *taps, int cap, int *L, int *M, int *T);
+/* -- the bookkeeping of one stream over a sequence of npush pushes of push_samples[i] samples: nout[i] = output samples push i completes,
+ * carried[i] = input samples kept behind it (T - 1, or all of them while the gain window is open) -- and the gain rule of step 4. */
+int dabhip_ingest_plan(int64_t rate_hz, int auto_gain, const int64_t *push_samples, int npush, int64_t *nout, int64_t *carried);
+uint32_t dabhip_ingest_auto_gain(uint64_t energy);
+
 /* ---- synthetic Mode-I modulator (host only) --------------------------------------------- */
 typedef struct dabhip_subch_cfg {
   int32_t id;          /* SubChId 0..63 */
