@@ -268,6 +268,11 @@ _SIGNATURES = {
     "dabhip_ingest_taps": (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_int16), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dabhip_ingest_plan": (C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "dabhip_ingest_auto_gain": (C.c_uint32, [C.c_uint64]),
+    "dabhip_ingest_create_tuned": (C.c_void_p, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_uint32, C.POINTER(C.c_int64), C.c_int]),
+    "dabhip_ingest_tune_taps": (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_int16), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dabhip_ingest_tune_nco": (C.c_int, [C.POINTER(C.c_int16), C.c_int]),
+    "dabhip_ingest_tune_step": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_uint32)]),
+    "dabhip_ingest_tune_plan": (C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
 _lib = None
@@ -867,24 +872,57 @@ def _ingest_format(fmt):
     return int(fmt)
 
 
-def ingest_taps(fmt, rate):
-    """(taps [L][T] int16 in Q14, L, M, T) of a sample rate (dabhip_ingest_taps; no GPU needed).  L/M = 1/1: an empty table, T = 0."""
+def _ingest_taps(name, fmt, rate):
+    fn = getattr(lib(), "dabhip_" + name)
     L, M, T = C.c_int(0), C.c_int(0), C.c_int(0)
-    n = lib().dabhip_ingest_taps(_ingest_format(fmt), int(rate), None, 0, C.byref(L), C.byref(M), C.byref(T))
-    _need(n >= 0, "ingest_taps")
+    n = fn(_ingest_format(fmt), int(rate), None, 0, C.byref(L), C.byref(M), C.byref(T))
+    _need(n >= 0, name)
     taps = np.zeros(n, dtype=np.int16)
     if n:
-        _need(lib().dabhip_ingest_taps(_ingest_format(fmt), int(rate), taps.ctypes.data_as(C.POINTER(C.c_int16)), n, None, None, None) == n, "ingest_taps")
+        _need(fn(_ingest_format(fmt), int(rate), taps.ctypes.data_as(C.POINTER(C.c_int16)), n, None, None, None) == n, name)
     return taps.reshape(L.value, T.value), L.value, M.value, T.value
+
+
+def _ingest_plan(name, rate, pushes, auto_gain):
+    n = len(pushes)
+    src = (C.c_int64 * max(n, 1))(*[int(v) for v in pushes])
+    nout, keep = (C.c_int64 * max(n, 1))(), (C.c_int64 * max(n, 1))()
+    _need(getattr(lib(), "dabhip_" + name)(int(rate), 1 if auto_gain else 0, src, n, nout, keep) == 0, name)
+    return list(nout)[:n], list(keep)[:n]
+
+
+def ingest_taps(fmt, rate):
+    """(taps [L][T] int16 in Q14, L, M, T) of a sample rate (dabhip_ingest_taps; no GPU needed).  L/M = 1/1: an empty table, T = 0."""
+    return _ingest_taps("ingest_taps", fmt, rate)
 
 
 def ingest_plan(rate, pushes, auto_gain=False):
     """The bookkeeping of one stream over pushes of `pushes` samples: (output samples completed per push, input samples carried behind each)."""
-    n = len(pushes)
-    src = (C.c_int64 * max(n, 1))(*[int(v) for v in pushes])
-    nout, keep = (C.c_int64 * max(n, 1))(), (C.c_int64 * max(n, 1))()
-    _need(lib().dabhip_ingest_plan(int(rate), 1 if auto_gain else 0, src, n, nout, keep) == 0, "ingest_plan")
-    return list(nout)[:n], list(keep)[:n]
+    return _ingest_plan("ingest_plan", rate, pushes, auto_gain)
+
+
+def ingest_tune_taps(fmt, rate):
+    """ingest_taps of the tuned mode: twice the taps, cut-off 856 kHz (dabhip_ingest_tune_taps)."""
+    return _ingest_taps("ingest_tune_taps", fmt, rate)
+
+
+def ingest_tune_plan(rate, pushes, auto_gain=False):
+    """ingest_plan of the tuned mode: the gain window closes on outputs (dabhip_ingest_tune_plan)."""
+    return _ingest_plan("ingest_tune_plan", rate, pushes, auto_gain)
+
+
+def ingest_tune_nco():
+    """The tuned mode's mixer table: int16 [4096][2], (cos, sin) in Q14 (dabhip_ingest_tune_nco)."""
+    cs = np.zeros((4096, 2), dtype=np.int16)
+    _need(lib().dabhip_ingest_tune_nco(cs.ctypes.data_as(C.POINTER(C.c_int16)), 4096) == 4096, "ingest_tune_nco")
+    return cs
+
+
+def ingest_tune_step(rate, offset_hz):
+    """The mixer's phase step per input sample, in 2^-32 turns, of a channel offset_hz from the capture's centre (dabhip_ingest_tune_step)."""
+    step = C.c_uint32(0)
+    _need(lib().dabhip_ingest_tune_step(int(rate), int(offset_hz), C.byref(step)) == 0, "ingest_tune_step")
+    return step.value
 
 
 def ingest_auto_gain(energy):
@@ -894,12 +932,22 @@ def ingest_auto_gain(energy):
 
 class Ingest:
     """nstreams streams of fmt ("cu8", "cs8", "cs16", "cf32") IQ at `rate` samples/s -> cu8 at 2.048 Msps in device memory (dabhip_ingest_*).
-    gain: the requantisation gain (256 = 16-bit full scale to 8-bit full scale), 0 = automatic.  State carries from push to push."""
+    gain: the requantisation gain (256 = 16-bit full scale to 8-bit full scale), 0 = automatic.  State carries from push to push.
+    offsets: the tuned mode (dabhip_ingest_create_tuned) -- every input stream gives len(offsets) output streams, channel c the DAB block centred
+    offsets[c] Hz from the capture's centre; output stream `stream * nchannels + channel` is what output_ptrs, read and gain index."""
 
-    def __init__(self, device, nstreams, fmt, rate, gain=0):
+    def __init__(self, device, nstreams, fmt, rate, gain=0, offsets=None):
         self.nstreams, self.fmt = int(nstreams), _ingest_format(fmt)
-        self._h = lib().dabhip_ingest_create(int(device), self.nstreams, self.fmt, int(rate), int(gain))
-        _need(self._h, "ingest_create")
+        if offsets is None:
+            self.nchannels = 1
+            self._h = lib().dabhip_ingest_create(int(device), self.nstreams, self.fmt, int(rate), int(gain))
+            _need(self._h, "ingest_create")
+        else:
+            self.nchannels = len(offsets)
+            off = (C.c_int64 * max(self.nchannels, 1))(*[int(f) for f in offsets])
+            self._h = lib().dabhip_ingest_create_tuned(int(device), self.nstreams, self.fmt, int(rate), int(gain), off, self.nchannels)
+            _need(self._h, "ingest_create_tuned")
+        self.nouts = self.nstreams * self.nchannels
 
     def push(self, arrays):
         """One array per stream (any dtype: its bytes are the samples, possibly none) -> total output bytes of this push."""
@@ -918,10 +966,10 @@ class Ingest:
         return n
 
     def output_ptrs(self):
-        """(device addresses, byte counts) of this push's cu8, per stream: what Engine.decode_device and Stream.feed_ptrs(on_device=True) take.
+        """(device addresses, byte counts) of this push's cu8, per output stream: what Engine.decode_device and Stream.feed_ptrs(on_device=True) take.
         Valid until the next push."""
         ptrs, sizes = [], []
-        for b in range(self.nstreams):
+        for b in range(self.nouts):
             p, n = C.c_void_p(0), C.c_size_t(0)
             _need(lib().dabhip_ingest_output(self._h, b, C.byref(p), C.byref(n)) == 0, "ingest_output")
             ptrs.append(p.value or 0)

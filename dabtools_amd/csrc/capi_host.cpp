@@ -237,3 +237,61 @@ extern "C" int dabhip_ingest_plan(int64_t rate_hz, int auto_gain, const int64_t*
 }
 
 extern "C" uint32_t dabhip_ingest_auto_gain(uint64_t energy) { return ingest_auto_gain(energy); }
+
+// ---- the tuned mode's host rule: its table, the NCO table, the step of an offset and the bookkeeping ----
+extern "C" int dabhip_ingest_tune_taps(int format, int64_t rate_hz, int16_t* taps, int cap, int* L, int* M, int* T)
+{
+  if (format < 0 || format >= kIngestFormats) { set_error("ingest_tune_taps: unknown format " + std::to_string(format) + " (0 = cu8, 1 = cs8, 2 = cs16, 3 = cf32)"); return -1; }
+  IngestRatio r;
+  const std::string why = ingest_tune_ratio(rate_hz, &r);
+  if (!why.empty()) { set_error("ingest_tune_taps: " + why); return -1; }
+  if (L) *L = r.L;
+  if (M) *M = r.M;
+  if (T) *T = r.T;
+  const int n = r.L * r.T;
+  if (n == 0) return 0;
+  const std::vector<int16_t> t = ingest_tune_design_taps(r, rate_hz);
+  const std::string bad = ingest_check_taps(r, t.data());
+  if (!bad.empty()) { set_error("ingest_tune_taps: " + bad); return -1; }
+  if (taps) {
+    if (cap < n) { set_error("ingest_tune_taps: buffer too small"); return -1; }
+    std::memcpy(taps, t.data(), static_cast<size_t>(n) * sizeof(int16_t));
+  }
+  return n;
+}
+
+extern "C" int dabhip_ingest_tune_nco(int16_t* cs, int cap)
+{
+  if (!cs || cap < kTuneNcoSize) { set_error("ingest_tune_nco: room for 4096 pairs is wanted"); return -1; }
+  const std::vector<int16_t> t = ingest_tune_nco();
+  std::memcpy(cs, t.data(), t.size() * sizeof(int16_t));
+  return kTuneNcoSize;
+}
+
+extern "C" int dabhip_ingest_tune_step(int64_t rate_hz, int64_t offset_hz, uint32_t* step)
+{
+  if (!step) { set_error("ingest_tune_step: null argument"); return -1; }
+  IngestRatio r;
+  std::string why = ingest_tune_ratio(rate_hz, &r);
+  if (why.empty()) why = ingest_tune_offset(rate_hz, offset_hz);
+  if (!why.empty()) { set_error("ingest_tune_step: " + why); return -1; }
+  *step = ingest_tune_step(rate_hz, offset_hz);
+  return 0;
+}
+
+extern "C" int dabhip_ingest_tune_plan(int64_t rate_hz, int auto_gain, const int64_t* push_samples, int npush, int64_t* nout, int64_t* carried)
+{
+  if (!push_samples || npush < 0 || !nout || !carried) { set_error("ingest_tune_plan: bad argument"); return -1; }
+  IngestRatio r;
+  const std::string why = ingest_tune_ratio(rate_hz, &r);
+  if (!why.empty()) { set_error("ingest_tune_plan: " + why); return -1; }
+  IngestStreamState s;
+  s.window_open = auto_gain != 0;
+  for (int i = 0; i < npush; ++i) {
+    if (push_samples[i] < 0) { set_error("ingest_tune_plan: negative push"); return -1; }
+    const IngestPush p = ingest_tune_plan_push(r, s, push_samples[i]);
+    nout[i] = p.nout;
+    carried[i] = p.keep;
+  }
+  return 0;
+}

@@ -10,6 +10,8 @@
 //
 //   hackrf_transfer -r - -s 8000000 ... | dab2eti-hip --format cs8 --rate 8000000 - > ensemble.eti
 //   dab2eti-hip --format cs16 --rate 2400000 [--gain G] airspy.cs16 > ensemble.eti   (other formats and rates: the ingest stage, dabhip_ingest_*, one device)
+//   dab2eti-hip --format cs16 --rate 10000000 --tune -1712000,0,1712000 airspy.cs16 > three.eti   (the blocks that many Hz from the capture's centre,
+//                                                                 dabhip_ingest_create_tuned: their frames one block after the other, as those of several files)
 //
 // Streaming mode (any input "-", or --stream) decodes unbounded input in segments of N 262,144-byte calls through a dabhip_stream session (on several
 // devices: a dabhip_multi_stream, the inputs dealt to the devices in contiguous slices): reader threads fill page-locked buffers while the GPU decodes an
@@ -35,6 +37,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -302,27 +305,35 @@ struct IngestOpts {
   int format = DABHIP_INGEST_CU8;
   long long rate = 2048000;
   long long gain = -1;                           // -1: not given (the automatic gain)
-  bool on() const { return format != DABHIP_INGEST_CU8 || rate != 2048000 || gain >= 0; }
+  bool rate_given = false;
+  std::vector<int64_t> tune;                     // --tune: the tuned mode, one output stream per input and offset
+  bool on() const { return format != DABHIP_INGEST_CU8 || rate != 2048000 || gain >= 0 || !tune.empty(); }
 };
 int sample_bytes_of(int format) { return format == DABHIP_INGEST_CS16 ? 4 : format == DABHIP_INGEST_CF32 ? 8 : 2; }
 
+// With --tune every input gives one output stream per offset, in (input, offset) order: the decoder's streams are the stage's output streams.
 // Batch: every file in one push, the decoder reads the stage's output where it lies.  Streaming: segments of about seg_bytes of OUTPUT per input; a
 // read that ends inside a sample carries the remainder to the next push.  Frames leave stream by stream within a segment, as without the stage.
 int run_ingest(const std::vector<const char*>& names, bool streaming, size_t seg_bytes, const IngestOpts& opt, int device, bool afc, bool soft, const std::vector<int32_t>& subch)
 {
   const int n = static_cast<int>(names.size());
+  const int nch = opt.tune.empty() ? 1 : static_cast<int>(opt.tune.size()), nout = n * nch;
   const size_t sb = static_cast<size_t>(sample_bytes_of(opt.format));
-  dabhip_ingest* ing = dabhip_ingest_create(device, n, opt.format, opt.rate, opt.gain < 0 ? 0u : static_cast<uint32_t>(opt.gain));
+  const uint32_t gain = opt.gain < 0 ? 0u : static_cast<uint32_t>(opt.gain);
+  dabhip_ingest* ing = opt.tune.empty() ? dabhip_ingest_create(device, n, opt.format, opt.rate, gain)
+                                        : dabhip_ingest_create_tuned(device, n, opt.format, opt.rate, gain, opt.tune.data(), nch);
   if (!ing) { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); return 2; }
+  std::vector<std::string> label;                                                        // an output stream on stderr: the input's name, with --tune "name@offset"
+  for (int i = 0; i < nout; ++i) label.push_back(opt.tune.empty() ? std::string(names[i]) : std::string(names[i / nch]) + "@" + std::to_string(opt.tune[static_cast<size_t>(i % nch)]));
   std::vector<const void*> src(static_cast<size_t>(n));
   std::vector<size_t> nbytes(static_cast<size_t>(n));
-  std::vector<const uint8_t*> out(static_cast<size_t>(n));
-  std::vector<size_t> out_bytes(static_cast<size_t>(n));
-  std::vector<long long> total(static_cast<size_t>(n), 0);
+  std::vector<const uint8_t*> out(static_cast<size_t>(nout));
+  std::vector<size_t> out_bytes(static_cast<size_t>(nout));
+  std::vector<long long> total(static_cast<size_t>(nout), 0);
   std::vector<uint8_t> frames;
   auto fail = [&]() { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); return 2; };
   auto outputs = [&]() {
-    for (int i = 0; i < n; ++i)
+    for (int i = 0; i < nout; ++i)
       if (dabhip_ingest_output(ing, i, &out[static_cast<size_t>(i)], &out_bytes[static_cast<size_t>(i)]) != 0) return false;
     return true;
   };
@@ -340,12 +351,12 @@ int run_ingest(const std::vector<const char*>& names, bool streaming, size_t seg
     if (g_soft_lanes) dabhip_engine_set_soft_lanes(e, 1);
     if (!subch.empty()) dabhip_engine_set_subchannels(e, subch.data(), static_cast<int>(subch.size()));
     if (dabhip_ingest_push(ing, src.data(), nbytes.data(), 0) < 0 || !outputs()) return fail();
-    const int64_t nframes = dabhip_engine_decode(e, out.data(), out_bytes.data(), n, 1);
+    const int64_t nframes = dabhip_engine_decode(e, out.data(), out_bytes.data(), nout, 1);
     if (nframes < 0) return fail();
-    for (int i = 0; i < n; ++i) {
-      std::fprintf(stderr, "%s: %lld ETI frames\n", names[i], static_cast<long long>(dabhip_engine_eti_count(e, i)));
+    for (int i = 0; i < nout; ++i) {
+      std::fprintf(stderr, "%s: %lld ETI frames\n", label[static_cast<size_t>(i)].c_str(), static_cast<long long>(dabhip_engine_eti_count(e, i)));
       char text[8192];
-      if (!g_quiet && dabhip_engine_stream_log(e, i, text, sizeof text) > 0) print_log(text, names[i], n > 1);
+      if (!g_quiet && dabhip_engine_stream_log(e, i, text, sizeof text) > 0) print_log(text, label[static_cast<size_t>(i)].c_str(), nout > 1);
     }
     if (dabhip_engine_eti_drain(e, to_stdout, nullptr) != nframes) return fail();
     flush_stdout();
@@ -358,7 +369,7 @@ int run_ingest(const std::vector<const char*>& names, bool streaming, size_t seg
     in[static_cast<size_t>(i)] = std::strcmp(names[i], "-") == 0 ? stdin : std::fopen(names[i], "rb");
     if (!in[static_cast<size_t>(i)]) { std::perror(names[i]); return 1; }
   }
-  dabhip_stream* s = dabhip_stream_create(device, n);
+  dabhip_stream* s = dabhip_stream_create(device, nout);
   if (!s) return fail();
   if (afc) dabhip_stream_set_afc(s, 1);
   if (soft) dabhip_stream_set_soft(s, 1);
@@ -387,19 +398,21 @@ int run_ingest(const std::vector<const char*>& names, bool streaming, size_t seg
     if (dabhip_ingest_push(ing, src.data(), nbytes.data(), 0) < 0 || !outputs()) return fail();
     const int64_t nframes = dabhip_stream_feed(s, out.data(), out_bytes.data(), 1);
     if (nframes < 0) return fail();
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < nout; ++i) {
       const int64_t c = dabhip_stream_eti_count(s, i);
       frames.resize(static_cast<size_t>(c) * DABHIP_ETI_BYTES);
       if (c > 0 && dabhip_stream_eti_read(s, i, frames.data(), c) != c) return fail();
       write_all(frames.data(), frames.size());
       total[static_cast<size_t>(i)] += c;
       char text[8192];
-      if (!g_quiet && dabhip_stream_log(s, i, text, sizeof text) > 0) print_log(text, names[i], n > 1);
+      if (!g_quiet && dabhip_stream_log(s, i, text, sizeof text) > 0) print_log(text, label[static_cast<size_t>(i)].c_str(), nout > 1);
+    }
+    for (int i = 0; i < n; ++i) {
       std::vector<uint8_t>& b = buf[static_cast<size_t>(i)];                             // the cut sample's first bytes to the front
       std::memmove(b.data(), b.data() + nbytes[static_cast<size_t>(i)], rem[static_cast<size_t>(i)]);
     }
   }
-  for (int i = 0; i < n; ++i) std::fprintf(stderr, "%s: %lld ETI frames\n", names[i], total[static_cast<size_t>(i)]);
+  for (int i = 0; i < nout; ++i) std::fprintf(stderr, "%s: %lld ETI frames\n", label[static_cast<size_t>(i)].c_str(), total[static_cast<size_t>(i)]);
   dabhip_stream_destroy(s);
   dabhip_ingest_destroy(ing);
   return 0;
@@ -428,6 +441,16 @@ int main(int argc, char** argv)
       char* end = nullptr;
       ingest.rate = std::strtoll(argv[++i], &end, 10);
       if (end == argv[i] || *end || ingest.rate <= 0) { std::fprintf(stderr, "dab2eti-hip: --rate takes a whole number of samples per second\n"); return 1; }
+      ingest.rate_given = true;
+    }
+    else if (std::strcmp(argv[i], "--tune") == 0 && i + 1 < argc) {
+      for (const char* p = argv[++i]; *p || ingest.tune.empty();) {
+        char* end = nullptr;
+        const long long f = std::strtoll(p, &end, 10);
+        if (end == p || (*end && *end != ',') || (*end == ',' && !end[1])) { std::fprintf(stderr, "dab2eti-hip: --tune takes offsets in Hz from the capture's centre: HZ[,HZ...]\n"); return 1; }
+        ingest.tune.push_back(f);
+        p = *end ? end + 1 : end;
+      }
     }
     else if (std::strcmp(argv[i], "--gain") == 0 && i + 1 < argc) {
       char* end = nullptr;
@@ -463,11 +486,15 @@ int main(int argc, char** argv)
     else { names.push_back(argv[i]); streaming = streaming || std::strcmp(argv[i], "-") == 0; }
   }
   if (names.empty()) {
-    std::fprintf(stderr, "Usage: dab2eti-hip [--stream] [--segment-calls N] [--afc] [--soft] [--soft-lanes] [--quiet] [--subch ID[,ID...]] [--devices A-B|A,B,...] [--format cu8|cs8|cs16|cf32] [--rate HZ] [--gain G] capture.cu8|- [more.cu8 ...] > out.eti\n");
+    std::fprintf(stderr, "Usage: dab2eti-hip [--stream] [--segment-calls N] [--afc] [--soft] [--soft-lanes] [--quiet] [--subch ID[,ID...]] [--devices A-B|A,B,...] [--format cu8|cs8|cs16|cf32] [--rate HZ] [--gain G] [--tune HZ[,HZ...]] capture.cu8|- [more.cu8 ...] > out.eti\n");
     return 1;
   }
   if (ingest.on() && devices.size() > 1) {
-    std::fprintf(stderr, "dab2eti-hip: --format / --rate / --gain run on one device: the ingest stage does not span --devices\n");
+    std::fprintf(stderr, "dab2eti-hip: --format / --rate / --gain / --tune run on one device: the ingest stage does not span --devices\n");
+    return 1;
+  }
+  if (!ingest.tune.empty() && !ingest.rate_given) {
+    std::fprintf(stderr, "dab2eti-hip: --tune needs --rate: an offset in Hz means nothing without the capture's sample rate\n");
     return 1;
   }
   if (streaming) {

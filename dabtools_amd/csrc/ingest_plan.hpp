@@ -62,12 +62,13 @@ inline double ingest_bessel_i0(double x)
   }
   return sum;
 }
-inline std::vector<int16_t> ingest_design_taps(const IngestRatio& r, int64_t rate_hz)
+// (The tuned mode's table, further down, is the same construction with its own T, cut-off and beta.)
+inline std::vector<int16_t> ingest_design_taps(const IngestRatio& r, int64_t rate_hz, double cutoff_hz = 1024000.0, double beta = 7.0)
 {
   const int L = r.L, T = r.T;
   std::vector<int16_t> taps(static_cast<size_t>(L) * T);
-  const double pi = 3.14159265358979323846, beta = 7.0, half = 0.5 * T * L;
-  const double fc = 2.0 * 1024000.0 / (static_cast<double>(L) * static_cast<double>(rate_hz));      // cycles per prototype sample, doubled: sinc(fc i)
+  const double pi = 3.14159265358979323846, half = 0.5 * T * L;
+  const double fc = 2.0 * cutoff_hz / (static_cast<double>(L) * static_cast<double>(rate_hz));      // cycles per prototype sample, doubled: sinc(fc i)
   const double i0b = ingest_bessel_i0(beta);
   std::vector<double> h(static_cast<size_t>(T));
   for (int p = 0; p < L; ++p) {
@@ -162,6 +163,102 @@ inline void ingest_skip_rest(const IngestRatio& r, IngestStreamState& s, int64_t
   s.pushed += rest;
   s.produced = ingest_outputs_complete(r, s.pushed);
   s.kept_from = std::max<int64_t>(0, s.pushed - std::max(0, r.T - 1));
+}
+
+// ---- the tuned mode (dabhip_ingest_create_tuned): K channels out of one wideband stream ------------------------------------------------------
+// A mixer in front of the resampler (include/dabhip.h, "tuned mode").  The table is steeper, because the neighbouring block begins 944 kHz from the
+// wanted one's centre: twice the taps, cut-off 856 kHz.  The kernel holds that table, the input tile and the NCO table in one workgroup's LDS.
+constexpr int kTuneMaxChannels = 16;
+constexpr int64_t kTuneHalfBand = 768000;          // a DAB block's occupied half width: |f| + this must lie within Fin / 2
+constexpr double kTuneCutoffHz = 856000.0, kTuneBeta = 7.0;
+constexpr int kTuneNcoSize = 4096;                 // entries of (cos, sin) in Q14
+constexpr size_t kTuneMaxLdsBytes = 160 * 1024;    // gfx950: LDS of one CU, all of which one workgroup may have
+
+// what the tuned kernel asks of LDS: the table (rounded up to a double word), the tile's pairs of both rails, the NCO table
+inline size_t ingest_tune_lds_bytes(const IngestRatio& r)
+{
+  if (r.bypass()) return 0;
+  return ((r.lds_table_bytes() / 4 + 1) & ~size_t(1)) * 4 + static_cast<size_t>(r.tile_span() / 2 + 2) * 8 + static_cast<size_t>(kTuneNcoSize) * 4;
+}
+inline std::string ingest_tune_fits(const IngestRatio& r, int64_t rate_hz)
+{
+  if (ingest_tune_lds_bytes(r) > kTuneMaxLdsBytes)
+    return "sample rate " + std::to_string(rate_hz) + " Hz needs " + std::to_string(ingest_tune_lds_bytes(r)) + " bytes of LDS for the tuned table, the input tile and the NCO table: a workgroup has 163840";
+  return "";
+}
+// the tuned ratio of a rate: ingest_ratio's with twice the taps, or the reason it is refused
+inline std::string ingest_tune_ratio(int64_t rate_hz, IngestRatio* r)
+{
+  const std::string why = ingest_ratio(rate_hz, r);
+  if (!why.empty()) return why;
+  r->T *= 2;
+  return ingest_tune_fits(*r, rate_hz);
+}
+inline std::vector<int16_t> ingest_tune_design_taps(const IngestRatio& r, int64_t rate_hz) { return ingest_design_taps(r, rate_hz, kTuneCutoffHz, kTuneBeta); }
+
+// the NCO table: cs[2 i] = rint(16384 cos(2 pi i / 4096)), cs[2 i + 1] = the same of sin.  One quarter wave is computed and the rest mirrored, so that
+// the quarter points and the symmetries are exact.
+inline std::vector<int16_t> ingest_tune_nco()
+{
+  const int N = kTuneNcoSize, Q = N / 4;
+  std::vector<int> s(static_cast<size_t>(N));
+  for (int i = 0; i <= Q; ++i) s[static_cast<size_t>(i)] = i == Q ? 16384 : static_cast<int>(std::lrint(16384.0 * std::sin(2.0 * 3.14159265358979323846 * i / N)));
+  for (int i = Q + 1; i <= 2 * Q; ++i) s[static_cast<size_t>(i)] = s[static_cast<size_t>(2 * Q - i)];
+  for (int i = 2 * Q + 1; i < N; ++i) s[static_cast<size_t>(i)] = -s[static_cast<size_t>(i - 2 * Q)];
+  std::vector<int16_t> cs(static_cast<size_t>(2 * N));
+  for (int i = 0; i < N; ++i) {
+    cs[static_cast<size_t>(2 * i)] = static_cast<int16_t>(s[static_cast<size_t>((i + Q) % N)]);
+    cs[static_cast<size_t>(2 * i + 1)] = static_cast<int16_t>(s[static_cast<size_t>(i)]);
+  }
+  return cs;
+}
+// may a block centred f Hz from the capture's centre be tuned to?  ("" = yes)
+inline std::string ingest_tune_offset(int64_t rate_hz, int64_t f)
+{
+  const int64_t mag = f < -kIngestMaxRate || f > kIngestMaxRate ? kIngestMaxRate : f < 0 ? -f : f;      // beyond every rate's reach anyway
+  if (2 * (mag + kTuneHalfBand) > rate_hz)
+    return "offset " + std::to_string(f) + " Hz: the block's +-768000 Hz do not lie within the capture's +-" + std::to_string(rate_hz / 2) + " Hz";
+  return "";
+}
+// step = floor((2 f 2^32 + Fin) / (2 Fin)) mod 2^32: f / Fin of a turn in 2^-32 turns, rounded to nearest
+inline uint32_t ingest_tune_step(int64_t rate_hz, int64_t f)
+{
+  const __int128 num = static_cast<__int128>(2 * f) * (static_cast<__int128>(1) << 32) + rate_hz, den = 2 * static_cast<__int128>(rate_hz);
+  __int128 q = num / den;
+  if (num % den < 0) --q;                          // floor towards minus infinity
+  return static_cast<uint32_t>(static_cast<unsigned __int128>(q) & 0xffffffffu);
+}
+// everything dabhip_ingest_create_tuned refuses before it looks for a device ("" = taken)
+inline std::string ingest_tune_check(int nstreams, int64_t rate_hz, const int64_t* offsets_hz, int nchannels, IngestRatio* r)
+{
+  if (nchannels < 1 || nchannels > kTuneMaxChannels) return "nchannels must be 1 .. 16";
+  if (!offsets_hz) return "null offsets";
+  if (nstreams <= 0 || static_cast<int64_t>(nstreams) * nchannels > 65535) return "nstreams times nchannels must be 1 .. 65535";
+  const std::string why = ingest_tune_ratio(rate_hz, r);
+  if (!why.empty()) return why;
+  for (int c = 0; c < nchannels; ++c) {
+    const std::string bad = ingest_tune_offset(rate_hz, offsets_hz[c]);
+    if (!bad.empty()) return bad;
+  }
+  return "";
+}
+// input samples of a stream that complete its first k outputs (k >= 1)
+inline int64_t ingest_samples_for_outputs(const IngestRatio& r, int64_t k) { return (k - 1) * r.M / r.L + r.T / 2 + 1; }
+// The bookkeeping of one push in the tuned mode: ingest_plan_push's, except that the automatic gain is measured on OUTPUTS -- the window stays open,
+// and everything is carried, until the pushed input completes output W - 1.
+inline IngestPush ingest_tune_plan_push(const IngestRatio& r, IngestStreamState& s, int64_t nsamples)
+{
+  if (!s.window_open || ingest_outputs_complete(r, s.pushed + nsamples) >= kIngestGainWindow) return ingest_plan_push(r, s, nsamples);
+  IngestPush p;
+  p.carry_from = s.kept_from;
+  p.carry = s.pushed - s.kept_from;
+  p.new_from = s.pushed;
+  s.pushed += nsamples;
+  p.end = s.pushed;
+  p.first_out = s.produced;
+  p.keep = s.pushed;                               // keep_from = 0
+  s.kept_from = 0;
+  return p;
 }
 
 }  // namespace dabhip

@@ -656,6 +656,46 @@ int dabhip_ingest_taps(int format, int64_t rate_hz, int16_t *taps, int cap, int 
 int dabhip_ingest_plan(int64_t rate_hz, int auto_gain, const int64_t *push_samples, int npush, int64_t *nout, int64_t *carried);
 uint32_t dabhip_ingest_auto_gain(uint64_t energy);
 
+/* ---- ingest stage, tuned mode: several DAB blocks out of one wideband capture -------------------------------------
+ * dabhip_ingest_create_tuned makes an ingest object with a mixer in front of the resampler: each of nstreams input streams gives nchannels output
+ * streams, channel c being the block whose centre lies offsets_hz[c] Hz from the capture's centre (signed; Band III blocks are 1,712,000 Hz apart),
+ * brought to 0 Hz and resampled to the canonical cu8.  Objects of dabhip_ingest_create are not touched by any of this.  The arithmetic is integer,
+ * stated here in full (the plain model of it: tests/tune_model.py), and its bytes do not depend on how the input is cut into pushes:
+ *  1. To the 16-bit domain: step 1 above, for all four formats (cu8's 255 gives 32768: x is an int32).
+ *  2. Mixer.  For the channel's offset f and the input rate Fin, step = floor((2 f 2^32 + Fin) / (2 Fin)) mod 2^32 in exact integers, floor towards
+ *     minus infinity (f / Fin of a turn in units of 2^-32 turn, rounded to nearest; dabhip_ingest_tune_step).  For the input sample at absolute 64-bit
+ *     position n of its stream (the first sample ever pushed is n = 0; dabhip_ingest_skip advances n): theta = (n step) mod 2^32,
+ *     i = ((theta + 2^19) mod 2^32) >> 20, a 12-bit index (a theta within 2^19 of a full turn gives i = 0).  The table (dabhip_ingest_tune_nco) has
+ *     4096 pairs of int16: c[i] = rint(16384 cos(2 pi i / 4096)), s[i] = rint(16384 sin(2 pi i / 4096)), the quarter points exact (+-16384 and 0).
+ *       yI = clamp((xI c[i] + xQ s[i] + 8192) >> 14, -32768, 32767),  yQ = clamp((xQ c[i] - xI s[i] + 8192) >> 14, -32768, 32767)
+ *     with arithmetic shifts: y = x e^(-j theta), so a block centred at +f lands at 0.  The phase is a function of n alone, nothing accumulates.  The
+ *     clamp is real: a full-scale sample at 45 degrees reaches 46341.
+ *  3. Resampling: step 2 above on y (y[n] = 0 for n < 0), with the TUNED table (dabhip_ingest_tune_taps): the same construction with
+ *     T = 8 ceil(8 M / L) taps per phase (twice the plain table's), the -6 dB point at 856 kHz, Kaiser beta 7, every phase scaled to sum 16384 with
+ *     the rounding remainder on its largest tap.  Held to: every phase sums to 16384; sum |taps[p][k]| <= 65535 per phase; the interleaved
+ *     prototype within +-0.05 dB of DC up to 768 kHz and at or below -60 dB from 944 kHz (1,712,000 - 768,000: where the neighbouring block begins).
+ *     Fin = 2,048,000 has no filter (T = 0): v = y.
+ *  4. Gain and requantisation: step 3 above.
+ *  5. Automatic gain (gain = 0 at creation), per OUTPUT stream and fixed for its life: E = sum(vI^2 + vQ^2) over the channel's first W = 65536
+ *     outputs v of step 3 (an exact uint64), g = dabhip_ingest_auto_gain(E).  All channels of an input stream are held back, and all of its input is
+ *     carried, until its pushed input completes output 65535 (input sample floor(65535 M / L) + T/2); that push delivers outputs from 0 on.  The
+ *     energy of the wideband input would be the wrong measure: a weak block beside a strong one must still fill its 8 bits.
+ * Refused: fewer than 1 or more than 16 channels; an offset with |f| + 768,000 > Fin / 2 (the block does not lie within the capture);
+ * nstreams nchannels > 65535; a rate dabhip_ingest_create refuses; a rate whose tuned table, input tile and NCO table (16 KiB) do not fit the 160 KiB
+ * of LDS one workgroup has on gfx950 (10,000,000 Hz: 82,432 + 21,288 + 16,384 bytes, taken; 10,229,760 Hz is the kind that is not).
+ * Output stream `stream nchannels + channel` is what dabhip_ingest_output, _read and _gain call `stream`; dabhip_ingest_push still takes one input
+ * per INPUT stream and returns the output bytes of all output streams; _skip and _stage_ms are as above. */
+dabhip_ingest *dabhip_ingest_create_tuned(int device, int nstreams, int format, int64_t rate_hz, uint32_t gain, const int64_t *offsets_hz, int nchannels);
+/* Without a GPU: the tuned table of a rate (as dabhip_ingest_taps) -- */
+int dabhip_ingest_tune_taps(int format, int64_t rate_hz, int16_t *taps, int cap, int *L, int *M, int *T);
+/* -- the mixer's table, cs[2 i] = c[i], cs[2 i + 1] = s[i] (cap in pairs, 4096 at least); returns 4096 -- */
+int dabhip_ingest_tune_nco(int16_t *cs, int cap);
+/* -- the step of an offset at a rate; returns 0, <0 when the rate or the offset is refused -- */
+int dabhip_ingest_tune_step(int64_t rate_hz, int64_t offset_hz, uint32_t *step);
+/* -- and the bookkeeping of one input stream as dabhip_ingest_plan gives it: nout[i] = output samples push i completes in EVERY channel,
+ * carried[i] = input samples kept behind it (T - 1 or all there are; everything while the gain window is open, which closes on outputs). */
+int dabhip_ingest_tune_plan(int64_t rate_hz, int auto_gain, const int64_t *push_samples, int npush, int64_t *nout, int64_t *carried);
+
 /* ---- synthetic Mode-I modulator (host only) --------------------------------------------- */
 typedef struct dabhip_subch_cfg {
   int32_t id;          /* SubChId 0..63 */
