@@ -273,6 +273,14 @@ _SIGNATURES = {
     "dabhip_ingest_tune_nco": (C.c_int, [C.POINTER(C.c_int16), C.c_int]),
     "dabhip_ingest_tune_step": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_uint32)]),
     "dabhip_ingest_tune_plan": (C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "dabhip_scan_create": (C.c_void_p, [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int]),
+    "dabhip_scan_destroy": (None, [C.c_void_p]),
+    "dabhip_scan_push": (C.c_int64, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int]),
+    "dabhip_scan_spectrum": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "dabhip_scan_blocks": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int]),
+    "dabhip_scan_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
+    "dabhip_scan_detect": (C.c_int, [C.POINTER(C.c_uint64), C.c_int64, C.c_int64, C.c_void_p, C.c_int]),
+    "dabhip_scan_plan": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
 _lib = None
@@ -1002,6 +1010,100 @@ class Ingest:
     def close(self):
         if getattr(self, "_h", None):
             lib().dabhip_ingest_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- block scan: which DAB blocks lie in a wideband capture (dabhip.h: dabhip_scan_*) ------------------------------
+SCAN_BINS = 4096
+SCAN_DEFAULT_SEGMENTS = 64
+
+
+class ScanBlockRecord(C.Structure):
+    """dabhip_scan_block."""
+    _fields_ = [("offset_hz", C.c_int64), ("raw_center_hz", C.c_int64), ("width_hz", C.c_int64), ("in_", C.c_uint64), ("lo", C.c_uint64), ("hi", C.c_uint64),
+                ("nin", C.c_int32), ("ng", C.c_int32), ("name", C.c_char * 8)]
+
+
+def _scan_records(recs, n):
+    """The first n records as dicts: offset_hz, raw_center_hz, width_hz, name ("" = off the raster), in, lo, hi (sums), nin, ng (their bin counts)."""
+    return [{"offset_hz": r.offset_hz, "raw_center_hz": r.raw_center_hz, "width_hz": r.width_hz, "name": r.name.decode(), "in": r.in_, "lo": r.lo, "hi": r.hi,
+             "nin": r.nin, "ng": r.ng} for r in recs[:n]]
+
+
+def scan_detect(P, rate, center=0):
+    """The blocks in a power spectrum of 4096 bins in transform order (dabhip_scan_detect; no GPU needed): a list of records in ascending offset.
+    center: the capture's centre frequency in Hz, 0 = not known (no snapping to the Band III raster)."""
+    P = np.ascontiguousarray(P, dtype=np.uint64).reshape(-1)
+    _need(P.size == SCAN_BINS, "scan_detect: a spectrum of 4096 bins is wanted")
+    recs = (ScanBlockRecord * 16)()
+    n = lib().dabhip_scan_detect(P.ctypes.data_as(C.POINTER(C.c_uint64)), int(rate), int(center), C.cast(recs, C.c_void_p), 16)
+    _need(n >= 0, "scan_detect")
+    return _scan_records(recs, n)
+
+
+def scan_plan(nsegments, pushes):
+    """The bookkeeping of one stream of a Scan over pushes of `pushes` samples: (segments completed per push, samples carried behind each)."""
+    n = len(pushes)
+    src = (C.c_int64 * max(n, 1))(*[int(v) for v in pushes])
+    nseg, keep = (C.c_int64 * max(n, 1))(), (C.c_int64 * max(n, 1))()
+    _need(lib().dabhip_scan_plan(int(nsegments), src, n, nseg, keep) == 0, "scan_plan")
+    return list(nseg)[:n], list(keep)[:n]
+
+
+class Scan:
+    """The power spectrum of the first nsegments segments of 4096 samples of nstreams streams of fmt IQ at `rate` samples/s, and the DAB blocks in
+    it (dabhip_scan_*).  State carries from push to push; samples past the window are ignored."""
+
+    def __init__(self, device, nstreams, fmt, rate, nsegments=SCAN_DEFAULT_SEGMENTS):
+        self.nstreams, self.fmt, self.rate = int(nstreams), _ingest_format(fmt), int(rate)
+        self._h = lib().dabhip_scan_create(int(device), self.nstreams, self.fmt, self.rate, int(nsegments))
+        _need(self._h, "scan_create")
+
+    def push(self, arrays):
+        """One array per stream (any dtype: its bytes are the samples, possibly none) -> segments accumulated by this push over all streams."""
+        _need(len(arrays) == self.nstreams, "scan_push: one array per stream")
+        arrs = [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in arrays]
+        return self.push_ptrs([a.ctypes.data for a in arrs], [a.size for a in arrs], on_device=False)
+
+    def push_ptrs(self, ptrs, sizes, on_device=False):
+        """push() over raw addresses: host memory, or device memory aligned to a sample."""
+        _need(len(ptrs) == self.nstreams and len(sizes) == self.nstreams, "scan_push: one input per stream")
+        p = (C.c_void_p * len(ptrs))(*ptrs)
+        s = (C.c_size_t * len(sizes))(*sizes)
+        n = lib().dabhip_scan_push(self._h, p, s, 1 if on_device else 0)
+        _need(n >= 0, "scan_push")
+        return n
+
+    def spectrum(self, stream):
+        """(P: uint64 [4096] in transform order, segments accumulated) of one stream."""
+        P = np.zeros(SCAN_BINS, dtype=np.uint64)
+        done = C.c_int(0)
+        _need(lib().dabhip_scan_spectrum(self._h, int(stream), P.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(done)) == 0, "scan_spectrum")
+        return P, done.value
+
+    def blocks(self, stream, center=0):
+        """The blocks of one stream as scan_detect gives them."""
+        recs = (ScanBlockRecord * 16)()
+        n = lib().dabhip_scan_blocks(self._h, int(stream), int(center), C.cast(recs, C.c_void_p), 16)
+        _need(n >= 0, "scan_blocks")
+        return _scan_records(recs, n)
+
+    def stage_ms(self):
+        """GPU time of the last push per stage: {"upload", "transform", "keep"} in ms."""
+        names = (C.c_char_p * 3)()
+        ms = (C.c_float * 3)()
+        n = lib().dabhip_scan_stage_ms(self._h, names, ms, 3)
+        return {names[i].decode(): ms[i] for i in range(n)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().dabhip_scan_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -13,6 +13,7 @@
 #include "fifo_view.hpp"
 #include "ingest_plan.hpp"
 #include "placement.hpp"
+#include "scan_blocks.hpp"
 
 using namespace dabhip;
 
@@ -291,6 +292,30 @@ extern "C" int dabhip_ingest_tune_plan(int64_t rate_hz, int auto_gain, const int
     if (push_samples[i] < 0) { set_error("ingest_tune_plan: negative push"); return -1; }
     const IngestPush p = ingest_tune_plan_push(r, s, push_samples[i]);
     nout[i] = p.nout;
+    carried[i] = p.keep;
+  }
+  return 0;
+}
+
+// ---- the block scan's host rule (scan_blocks.hpp): from a spectrum to the blocks, and the bookkeeping of a sequence of pushes ----
+extern "C" int dabhip_scan_detect(const uint64_t* P, int64_t rate_hz, int64_t center_hz, dabhip_scan_block* out, int cap)
+{
+  if (!P || (!out && cap > 0) || cap < 0) { set_error("scan_detect: bad argument"); return -1; }
+  std::string why;
+  const int n = scan_detect(P, rate_hz, center_hz, out, cap, &why);
+  if (n < 0) set_error("scan_detect: " + why);
+  return n;
+}
+
+extern "C" int dabhip_scan_plan(int nsegments, const int64_t* push_samples, int npush, int64_t* nseg, int64_t* carried)
+{
+  if (!push_samples || npush < 0 || !nseg || !carried) { set_error("scan_plan: bad argument"); return -1; }
+  if (nsegments < 1 || nsegments > kScanMaxSegments) { set_error("scan_plan: nsegments must be 1 .. 65536"); return -1; }
+  ScanStreamState s;
+  for (int i = 0; i < npush; ++i) {
+    if (push_samples[i] < 0) { set_error("scan_plan: negative push"); return -1; }
+    const ScanPush p = scan_plan_push(nsegments, s, push_samples[i]);
+    nseg[i] = p.nseg;
     carried[i] = p.keep;
   }
   return 0;

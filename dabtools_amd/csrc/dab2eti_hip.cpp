@@ -12,6 +12,10 @@
 //   dab2eti-hip --format cs16 --rate 2400000 [--gain G] airspy.cs16 > ensemble.eti   (other formats and rates: the ingest stage, dabhip_ingest_*, one device)
 //   dab2eti-hip --format cs16 --rate 10000000 --tune -1712000,0,1712000 airspy.cs16 > three.eti   (the blocks that many Hz from the capture's centre,
 //                                                                 dabhip_ingest_create_tuned: their frames one block after the other, as those of several files)
+//   dab2eti-hip --format cs16 --rate 10000000 --scan [--center 227360000] airspy.cs16          (which blocks are in it: one line per block on stdout, no ETI;
+//                                                                 dabhip_scan_*: the spectrum of the first 64 x 4096 samples and the rule of dabhip_scan_detect)
+//   dab2eti-hip --format cs16 --rate 10000000 --tune auto [--center 227360000] airspy.cs16 > all.eti   (scan, then --tune with the offsets found; a pipe's
+//                                                                 scanned samples are kept and go through the ingest stage first)
 //
 // Streaming mode (any input "-", or --stream) decodes unbounded input in segments of N 262,144-byte calls through a dabhip_stream session (on several
 // devices: a dabhip_multi_stream, the inputs dealt to the devices in contiguous slices): reader threads fill page-locked buffers while the GPU decodes an
@@ -32,6 +36,7 @@
 #include <unistd.h>
 
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -307,9 +312,43 @@ struct IngestOpts {
   long long gain = -1;                           // -1: not given (the automatic gain)
   bool rate_given = false;
   std::vector<int64_t> tune;                     // --tune: the tuned mode, one output stream per input and offset
-  bool on() const { return format != DABHIP_INGEST_CU8 || rate != 2048000 || gain >= 0 || !tune.empty(); }
+  bool tune_auto = false;                        // --tune auto: the offsets come from a block scan of each input's beginning
+  bool scan = false;                             // --scan: the block scan alone
+  long long center = 0;                          // --center: the capture's centre frequency in Hz (0: not given), for the scan's raster
+  bool on() const { return format != DABHIP_INGEST_CU8 || rate != 2048000 || gain >= 0 || !tune.empty() || tune_auto || scan; }
 };
 int sample_bytes_of(int format) { return format == DABHIP_INGEST_CS16 ? 4 : format == DABHIP_INGEST_CF32 ? 8 : 2; }
+
+// The block scan of the inputs' beginnings (at most 64 x 4096 samples each: ptrs / sizes): one line per input and block on `to` (null: none), the
+// offsets found per input in *found.  0, or the exit code.
+int scan_inputs(const std::vector<const char*>& names, const std::vector<const void*>& ptrs, const std::vector<size_t>& sizes, const IngestOpts& opt, int device, FILE* to,
+                std::vector<std::vector<int64_t>>* found)
+{
+  const int n = static_cast<int>(names.size());
+  dabhip_scan* sc = dabhip_scan_create(device, n, opt.format, opt.rate, DABHIP_SCAN_DEFAULT_SEGMENTS);
+  if (!sc || dabhip_scan_push(sc, ptrs.data(), sizes.data(), 0) < 0) { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); return 2; }
+  std::vector<uint64_t> P(DABHIP_SCAN_BINS);
+  for (int i = 0; i < n; ++i) {
+    dabhip_scan_block blocks[16];
+    int segments = 0;
+    const int nb = dabhip_scan_spectrum(sc, i, P.data(), &segments) == 0 ? dabhip_scan_detect(P.data(), opt.rate, opt.center, blocks, 16) : -1;
+    if (nb < 0) { std::fprintf(stderr, "dab2eti-hip: %s: %s\n", names[i], dabhip_last_error()); return 2; }
+    if (nb == 0 && to) std::fprintf(to, "%s: no DAB block found\n", names[i]);
+    for (int k = 0; k < nb; ++k) {
+      const dabhip_scan_block& b = blocks[k];
+      (*found)[static_cast<size_t>(i)].push_back(b.offset_hz);
+      // display only: the block's power (its in-band mean per bin over the bins of 1,536,000 Hz; the bins of a segment sum to the mean |x|^2) against a
+      // full-scale tone's 32768^2, and the in-band mean against the stronger guard's
+      const double mean_in = static_cast<double>(b.in) / b.nin, guard = std::max(static_cast<double>(std::max(b.lo, b.hi)), 1.0) / b.ng;
+      const double level = 10.0 * std::log10(mean_in / std::max(segments, 1) * (1536000.0 * DABHIP_SCAN_BINS / static_cast<double>(opt.rate)) / (32768.0 * 32768.0));
+      if (to)
+        std::fprintf(to, "%s: offset %lld Hz, block %s, width %lld Hz, level %.1f dBFS, contrast %.1f dB\n", names[i], static_cast<long long>(b.offset_hz), b.name[0] ? b.name : "-",
+                     static_cast<long long>(b.width_hz), level, 10.0 * std::log10(mean_in / guard));
+    }
+  }
+  dabhip_scan_destroy(sc);
+  return 0;
+}
 
 // With --tune every input gives one output stream per offset, in (input, offset) order: the decoder's streams are the stage's output streams.
 // Batch: every file in one push, the decoder reads the stage's output where it lies.  Streaming: segments of about seg_bytes of OUTPUT per input; a
@@ -317,40 +356,91 @@ int sample_bytes_of(int format) { return format == DABHIP_INGEST_CS16 ? 4 : form
 int run_ingest(const std::vector<const char*>& names, bool streaming, size_t seg_bytes, const IngestOpts& opt, int device, bool afc, bool soft, const std::vector<int32_t>& subch)
 {
   const int n = static_cast<int>(names.size());
-  const int nch = opt.tune.empty() ? 1 : static_cast<int>(opt.tune.size()), nout = n * nch;
   const size_t sb = static_cast<size_t>(sample_bytes_of(opt.format));
   const uint32_t gain = opt.gain < 0 ? 0u : static_cast<uint32_t>(opt.gain);
-  dabhip_ingest* ing = opt.tune.empty() ? dabhip_ingest_create(device, n, opt.format, opt.rate, gain)
-                                        : dabhip_ingest_create_tuned(device, n, opt.format, opt.rate, gain, opt.tune.data(), nch);
-  if (!ing) { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); return 2; }
-  std::vector<std::string> label;                                                        // an output stream on stderr: the input's name, with --tune "name@offset"
-  for (int i = 0; i < nout; ++i) label.push_back(opt.tune.empty() ? std::string(names[i]) : std::string(names[i / nch]) + "@" + std::to_string(opt.tune[static_cast<size_t>(i % nch)]));
+  auto fail = [&]() { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); return 2; };
   std::vector<const void*> src(static_cast<size_t>(n));
   std::vector<size_t> nbytes(static_cast<size_t>(n));
+  std::vector<Mapped> files(static_cast<size_t>(n));
+  std::vector<FILE*> in(static_cast<size_t>(n), nullptr);
+  for (int i = 0; i < n; ++i) {
+    if (!streaming) {
+      if (!map_file(names[i], &files[static_cast<size_t>(i)])) return 1;
+      src[static_cast<size_t>(i)] = files[static_cast<size_t>(i)].p;
+      nbytes[static_cast<size_t>(i)] = files[static_cast<size_t>(i)].n / sb * sb;        // a file that ends inside a sample: the whole samples
+    } else {
+      in[static_cast<size_t>(i)] = std::strcmp(names[i], "-") == 0 ? stdin : std::fopen(names[i], "rb");
+      if (!in[static_cast<size_t>(i)]) { std::perror(names[i]); return 1; }
+    }
+  }
+  // --scan / --tune auto: the scan sees each input's first 64 x 4096 samples.  Those of a stream are kept (`ahead`) and are the first the ingest reads.
+  std::vector<std::vector<int64_t>> tune(static_cast<size_t>(n), opt.tune);              // the offsets of each input's channels
+  std::vector<std::vector<uint8_t>> ahead(static_cast<size_t>(n));
+  std::vector<size_t> ahead_at(static_cast<size_t>(n), 0);
+  if (opt.scan || opt.tune_auto) {
+    const size_t want = static_cast<size_t>(DABHIP_SCAN_DEFAULT_SEGMENTS) * DABHIP_SCAN_BINS * sb;
+    std::vector<const void*> first(static_cast<size_t>(n));
+    std::vector<size_t> first_bytes(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) {
+      if (streaming) {
+        std::vector<uint8_t>& a = ahead[static_cast<size_t>(i)];
+        a.resize(want);
+        size_t have = 0;
+        for (size_t got = 1; have < want && got; have += got) got = std::fread(a.data() + have, 1, want - have, in[static_cast<size_t>(i)]);
+        a.resize(have);
+        first[static_cast<size_t>(i)] = a.data();
+        first_bytes[static_cast<size_t>(i)] = have / sb * sb;
+      } else {
+        first[static_cast<size_t>(i)] = src[static_cast<size_t>(i)];
+        first_bytes[static_cast<size_t>(i)] = std::min(nbytes[static_cast<size_t>(i)], want);
+      }
+    }
+    const int rc = scan_inputs(names, first, first_bytes, opt, device, opt.scan ? stdout : g_quiet ? nullptr : stderr, &tune);
+    if (rc || opt.scan) return rc;
+    for (int i = 0; i < n; ++i) {
+      if (tune[static_cast<size_t>(i)].empty()) { std::fprintf(stderr, "dab2eti-hip: --tune auto: no DAB block found in %s\n", names[i]); return 1; }
+      if (tune[static_cast<size_t>(i)].size() != tune[0].size()) {
+        std::fprintf(stderr, "dab2eti-hip: --tune auto: %s holds %zu blocks and %s %zu: all inputs of one run must hold the same number\n", names[0], tune[0].size(), names[i],
+                     tune[static_cast<size_t>(i)].size());
+        return 1;
+      }
+    }
+    if (opt.center <= 0 && !afc && !g_quiet)
+      std::fprintf(stderr, "dab2eti-hip: --tune auto without --center: the offsets are measured (to about 2 kHz), not snapped to the block raster: --afc is recommended\n");
+  }
+  // the ingest objects: one for all inputs, or with --tune auto one per input (each input has its own offsets); `per` inputs each
+  const int nch = tune[0].empty() ? 1 : static_cast<int>(tune[0].size()), nout = n * nch;
+  const int per = opt.tune_auto ? 1 : n;
+  std::vector<dabhip_ingest*> ings;
+  for (int i = 0; i < n; i += per) {
+    ings.push_back(tune[0].empty() ? dabhip_ingest_create(device, per, opt.format, opt.rate, gain)
+                                   : dabhip_ingest_create_tuned(device, per, opt.format, opt.rate, gain, tune[static_cast<size_t>(i)].data(), nch));
+    if (!ings.back()) return fail();
+  }
+  std::vector<std::string> label;                                                        // an output stream on stderr: the input's name, with --tune "name@offset"
+  for (int i = 0; i < nout; ++i) label.push_back(tune[0].empty() ? std::string(names[i]) : std::string(names[i / nch]) + "@" + std::to_string(tune[static_cast<size_t>(i / nch)][static_cast<size_t>(i % nch)]));
   std::vector<const uint8_t*> out(static_cast<size_t>(nout));
   std::vector<size_t> out_bytes(static_cast<size_t>(nout));
   std::vector<long long> total(static_cast<size_t>(nout), 0);
   std::vector<uint8_t> frames;
-  auto fail = [&]() { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); return 2; };
+  auto push = [&]() {
+    for (size_t k = 0; k < ings.size(); ++k)
+      if (dabhip_ingest_push(ings[k], src.data() + k * per, nbytes.data() + k * per, 0) < 0) return false;
+    return true;
+  };
   auto outputs = [&]() {
     for (int i = 0; i < nout; ++i)
-      if (dabhip_ingest_output(ing, i, &out[static_cast<size_t>(i)], &out_bytes[static_cast<size_t>(i)]) != 0) return false;
+      if (dabhip_ingest_output(ings[static_cast<size_t>(i / (per * nch))], i % (per * nch), &out[static_cast<size_t>(i)], &out_bytes[static_cast<size_t>(i)]) != 0) return false;
     return true;
   };
   if (!streaming) {
-    std::vector<Mapped> files(static_cast<size_t>(n));
-    for (int i = 0; i < n; ++i) {
-      if (!map_file(names[i], &files[static_cast<size_t>(i)])) return 1;
-      src[static_cast<size_t>(i)] = files[static_cast<size_t>(i)].p;
-      nbytes[static_cast<size_t>(i)] = files[static_cast<size_t>(i)].n / sb * sb;        // a file that ends inside a sample: the whole samples
-    }
     dabhip_engine* e = dabhip_engine_create(device);
     if (!e) return fail();
     if (afc) dabhip_engine_set_afc(e, 1);
     if (soft) dabhip_engine_set_soft(e, 1);
     if (g_soft_lanes) dabhip_engine_set_soft_lanes(e, 1);
     if (!subch.empty()) dabhip_engine_set_subchannels(e, subch.data(), static_cast<int>(subch.size()));
-    if (dabhip_ingest_push(ing, src.data(), nbytes.data(), 0) < 0 || !outputs()) return fail();
+    if (!push() || !outputs()) return fail();
     const int64_t nframes = dabhip_engine_decode(e, out.data(), out_bytes.data(), nout, 1);
     if (nframes < 0) return fail();
     for (int i = 0; i < nout; ++i) {
@@ -358,16 +448,16 @@ int run_ingest(const std::vector<const char*>& names, bool streaming, size_t seg
       char text[8192];
       if (!g_quiet && dabhip_engine_stream_log(e, i, text, sizeof text) > 0) print_log(text, label[static_cast<size_t>(i)].c_str(), nout > 1);
     }
-    if (dabhip_engine_eti_drain(e, to_stdout, nullptr) != nframes) return fail();
-    flush_stdout();
+    // stream by stream, those with frames only: a block that gave nothing (a weak one the scan found, tuned a little off) does not stop the others
+    for (int i = 0; i < nout; ++i) {
+      const int64_t c = dabhip_engine_eti_count(e, i);
+      frames.resize(static_cast<size_t>(std::max<int64_t>(c, 0)) * DABHIP_ETI_BYTES);
+      if (c < 0 || (c > 0 && dabhip_engine_eti_read(e, i, frames.data(), c) != c)) return fail();
+      write_all(frames.data(), frames.size());
+    }
     dabhip_engine_destroy(e);
-    dabhip_ingest_destroy(ing);
+    for (dabhip_ingest* g : ings) dabhip_ingest_destroy(g);
     return 0;
-  }
-  std::vector<FILE*> in(static_cast<size_t>(n));
-  for (int i = 0; i < n; ++i) {
-    in[static_cast<size_t>(i)] = std::strcmp(names[i], "-") == 0 ? stdin : std::fopen(names[i], "rb");
-    if (!in[static_cast<size_t>(i)]) { std::perror(names[i]); return 1; }
   }
   dabhip_stream* s = dabhip_stream_create(device, nout);
   if (!s) return fail();
@@ -385,6 +475,13 @@ int run_ingest(const std::vector<const char*>& names, bool streaming, size_t seg
     for (int i = 0; i < n; ++i) {
       std::vector<uint8_t>& b = buf[static_cast<size_t>(i)];
       size_t have = rem[static_cast<size_t>(i)];
+      std::vector<uint8_t>& a = ahead[static_cast<size_t>(i)];                          // what the scan read ahead goes first
+      if (ahead_at[static_cast<size_t>(i)] < a.size() && have < seg_in) {
+        const size_t take = std::min(a.size() - ahead_at[static_cast<size_t>(i)], seg_in - have);
+        std::memcpy(b.data() + have, a.data() + ahead_at[static_cast<size_t>(i)], take);
+        ahead_at[static_cast<size_t>(i)] += take;
+        have += take;
+      }
       while (!eof[static_cast<size_t>(i)] && have < seg_in) {
         const size_t got = std::fread(b.data() + have, 1, seg_in - have, in[static_cast<size_t>(i)]);
         if (got == 0) eof[static_cast<size_t>(i)] = true;
@@ -393,9 +490,9 @@ int run_ingest(const std::vector<const char*>& names, bool streaming, size_t seg
       src[static_cast<size_t>(i)] = b.data();
       nbytes[static_cast<size_t>(i)] = have / sb * sb;
       rem[static_cast<size_t>(i)] = have - nbytes[static_cast<size_t>(i)];
-      more = more || !eof[static_cast<size_t>(i)];
+      more = more || !eof[static_cast<size_t>(i)] || ahead_at[static_cast<size_t>(i)] < a.size();
     }
-    if (dabhip_ingest_push(ing, src.data(), nbytes.data(), 0) < 0 || !outputs()) return fail();
+    if (!push() || !outputs()) return fail();
     const int64_t nframes = dabhip_stream_feed(s, out.data(), out_bytes.data(), 1);
     if (nframes < 0) return fail();
     for (int i = 0; i < nout; ++i) {
@@ -414,7 +511,7 @@ int run_ingest(const std::vector<const char*>& names, bool streaming, size_t seg
   }
   for (int i = 0; i < nout; ++i) std::fprintf(stderr, "%s: %lld ETI frames\n", label[static_cast<size_t>(i)].c_str(), total[static_cast<size_t>(i)]);
   dabhip_stream_destroy(s);
-  dabhip_ingest_destroy(ing);
+  for (dabhip_ingest* g : ings) dabhip_ingest_destroy(g);
   return 0;
 }
 }  // namespace
@@ -442,6 +539,13 @@ int main(int argc, char** argv)
       ingest.rate = std::strtoll(argv[++i], &end, 10);
       if (end == argv[i] || *end || ingest.rate <= 0) { std::fprintf(stderr, "dab2eti-hip: --rate takes a whole number of samples per second\n"); return 1; }
       ingest.rate_given = true;
+    }
+    else if (std::strcmp(argv[i], "--tune") == 0 && i + 1 < argc && std::strcmp(argv[i + 1], "auto") == 0) { ingest.tune_auto = true; ++i; }
+    else if (std::strcmp(argv[i], "--scan") == 0) ingest.scan = true;
+    else if (std::strcmp(argv[i], "--center") == 0 && i + 1 < argc) {
+      char* end = nullptr;
+      ingest.center = std::strtoll(argv[++i], &end, 10);
+      if (end == argv[i] || *end || ingest.center <= 0) { std::fprintf(stderr, "dab2eti-hip: --center takes the capture's centre frequency in Hz\n"); return 1; }
     }
     else if (std::strcmp(argv[i], "--tune") == 0 && i + 1 < argc) {
       for (const char* p = argv[++i]; *p || ingest.tune.empty();) {
@@ -486,11 +590,27 @@ int main(int argc, char** argv)
     else { names.push_back(argv[i]); streaming = streaming || std::strcmp(argv[i], "-") == 0; }
   }
   if (names.empty()) {
-    std::fprintf(stderr, "Usage: dab2eti-hip [--stream] [--segment-calls N] [--afc] [--soft] [--soft-lanes] [--quiet] [--subch ID[,ID...]] [--devices A-B|A,B,...] [--format cu8|cs8|cs16|cf32] [--rate HZ] [--gain G] [--tune HZ[,HZ...]] capture.cu8|- [more.cu8 ...] > out.eti\n");
+    std::fprintf(stderr, "Usage: dab2eti-hip [--stream] [--segment-calls N] [--afc] [--soft] [--soft-lanes] [--quiet] [--subch ID[,ID...]] [--devices A-B|A,B,...] [--format cu8|cs8|cs16|cf32] [--rate HZ] [--gain G] [--tune HZ[,HZ...]|auto] [--scan] [--center HZ] capture.cu8|- [more.cu8 ...] > out.eti\n");
     return 1;
   }
   if (ingest.on() && devices.size() > 1) {
-    std::fprintf(stderr, "dab2eti-hip: --format / --rate / --gain / --tune run on one device: the ingest stage does not span --devices\n");
+    std::fprintf(stderr, "dab2eti-hip: --format / --rate / --gain / --tune / --scan run on one device: the ingest stage does not span --devices\n");
+    return 1;
+  }
+  if (ingest.scan && (ingest.tune_auto || !ingest.tune.empty())) {
+    std::fprintf(stderr, "dab2eti-hip: --scan only lists the blocks: it does not go with --tune\n");
+    return 1;
+  }
+  if (ingest.tune_auto && !ingest.tune.empty()) {
+    std::fprintf(stderr, "dab2eti-hip: --tune auto does not go with --tune offsets\n");
+    return 1;
+  }
+  if ((ingest.scan || ingest.tune_auto) && !ingest.rate_given) {
+    std::fprintf(stderr, "dab2eti-hip: %s needs --rate: a spectrum means nothing without the capture's sample rate\n", ingest.scan ? "--scan" : "--tune auto");
+    return 1;
+  }
+  if (ingest.center > 0 && !ingest.scan && !ingest.tune_auto) {
+    std::fprintf(stderr, "dab2eti-hip: --center goes with --scan or --tune auto\n");
     return 1;
   }
   if (!ingest.tune.empty() && !ingest.rate_given) {

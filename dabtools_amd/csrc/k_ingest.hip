@@ -24,6 +24,7 @@
 
 #include "ingest.hpp"
 #include "ingest_plan.hpp"
+#include "ingest_sample.hpp"
 
 namespace dabhip {
 namespace {
@@ -31,29 +32,6 @@ namespace {
 typedef short __attribute__((ext_vector_type(2))) vshort2;
 constexpr int kThreads = 256;
 constexpr int kTilesPerGroup = 8;
-
-template <int F> struct Sample;
-template <> struct Sample<0> { typedef uchar2 type; };
-template <> struct Sample<1> { typedef char2 type; };
-template <> struct Sample<2> { typedef short2 type; };
-template <> struct Sample<3> { typedef float2 type; };
-
-__device__ __forceinline__ int cf32_to_16(float f)
-{
-  float v = f * 32768.0f;
-  v = (v == v) ? v : 0.0f;                                       // NaN -> 0
-  v = v < -32768.0f ? -32768.0f : v > 32767.0f ? 32767.0f : v;
-  return static_cast<int>(rintf(v));                             // ties to even
-}
-// what LDS holds of a sample: the 16-bit-domain value, or for the 8-bit formats that value / 256
-template <int F>
-__device__ __forceinline__ int2 convert(typename Sample<F>::type s)
-{
-  if constexpr (F == 0) return int2{static_cast<int>(s.x) - 127, static_cast<int>(s.y) - 127};
-  else if constexpr (F == 3) return int2{cf32_to_16(s.x), cf32_to_16(s.y)};
-  else return int2{static_cast<int>(s.x), static_cast<int>(s.y)};
-}
-template <int F> constexpr int post_shift() { return F <= 1 ? 8 : 0; }
 
 // sample n of the stream (absolute position), zero outside [carry_from, end)
 template <int F>

@@ -696,6 +696,77 @@ int dabhip_ingest_tune_step(int64_t rate_hz, int64_t offset_hz, uint32_t *step);
  * carried[i] = input samples kept behind it (T - 1 or all there are; everything while the gain window is open, which closes on outputs). */
 int dabhip_ingest_tune_plan(int64_t rate_hz, int auto_gain, const int64_t *push_samples, int npush, int64_t *nout, int64_t *carried);
 
+/* ---- block scan: which DAB blocks lie in a wideband capture ------------------------------------------------------
+ * Off unless asked for: a stateful object that measures the power spectrum of the beginning of nstreams streams of cu8 / cs8 / cs16 / cf32 IQ at an
+ * integer sample rate Fin, and a host rule that turns such a spectrum into the list of Mode-I blocks (1.536 MHz wide) in it, as offsets from the
+ * capture's centre that dabhip_ingest_create_tuned takes.  Nothing of the decoder or of the ingest objects is touched.  The arithmetic is integer and
+ * stated here in full, so the spectrum is that of a plain model (tests/scan_model.py), bit for bit, however the input is cut into pushes:
+ *  0. Window.  S = 4096 samples are a segment; the scan window of a stream is its first nsegments complete segments, counted from the first sample
+ *     ever pushed.  Samples past the window are ignored; a stream with fewer than S samples has 0 segments and an all-zero spectrum.
+ *  1. Samples: step 1 of the ingest stage, all four formats (cu8's 255 gives 32768: x is an int32).
+ *  2. Transform, per segment: radix-2 decimation in time on the bit-reversed segment (v[i] = x[bit-reverse12(i)]) with the tuned mode's NCO table
+ *     c[i], s[i] (dabhip_ingest_tune_nco: 4096 entries in Q14).  Stages of half size h = 1, 2, 4, ..., 2048; the butterfly of a stage takes a at index
+ *     i and b at index i + h (i mod 2h < h), with q = i mod h and table index t = q (2048 / h):
+ *       tI = (bI c[t] + bQ s[t] + 8192) >> 14,   tQ = (bQ c[t] - bI s[t] + 8192) >> 14      (the mixer's product b e^(-j theta): arithmetic shifts, no clamp)
+ *       a' = (a + t + 1) >> 1,   b' = (a - t + 1) >> 1                                      (per rail)
+ *     Every stage halves, so X[k] is about (1/4096) sum x[n] e^(-2 pi j k n / 4096), in transform order (bin k: frequency k Fin / 4096, k >= 2048
+ *     negative).  These two roundings per butterfly are the only ones; everything else is exact, so the order of work cannot matter.
+ *  3. Power: P[k] = sum over the window's segments of XI[k]^2 + XQ[k]^2, an exact uint64 (at most about 2^32 per segment and bin).
+ *  4. Range.  Every intermediate value stays within +-46,400 per rail: the magnitude of a sample is at most 32768 sqrt 2 = 46,341 (full scale on both
+ *     rails); a butterfly gives |a'|, |b'| <= (|a| + |t|) / 2 + 1 with |t| <= |b| |w| / 16384 + 1, where |w| <= 16384 (1 + 2^-14) for every entry of
+ *     the rounded table (c^2 + s^2 <= 16384^2 + 16384 sqrt 2 + 1/2): a stage takes the largest magnitude M to at most M (1 + 2^-15) + 3/2, which adds
+ *     less than 3, 12 stages less than 36.  A rail is no larger than the magnitude.  Both products of tI or tQ together are at most |b| |w| < 46,400 16,385 < 2^30, plus 8192 still below 2^31: int32 arithmetic
+ *     suffices, and both factors of every product fit 24 bits.
+ * From spectrum to blocks (dabhip_scan_detect; integers, 128-bit products).  Shifted index b = (k + 2048) mod 4096 has frequency
+ * (b - 2048) Fin / 4096; sums below are over P in shifted order.  ni = floor(700000 4096 / Fin), a0 = ceil(800000 4096 / Fin),
+ * a1 = floor(900000 4096 / Fin), w = max(1, floor(16000 4096 / Fin)), nin = 2 ni + 1, ng = a1 - a0 + 1.
+ *  - Candidates: for every centre bin c in [a1, 4096 - a1): in(c) = sum over [c - ni, c + ni], lo(c) = sum over [c - a1, c - a0], hi(c) = sum over
+ *    [c + a0, c + a1] (the middle of the 176 kHz guard either side of a block).  c is a candidate when in ng > 4 lo nin and in ng > 4 hi nin: the
+ *    in-band mean more than 6 dB above both guards' (strict: an all-zero spectrum has no candidate).
+ *  - Runs: each maximal run [a, b] of consecutive candidates is one detection; raw_center_hz = floor(((a + b - 4096) Fin + 4096) / 8192).
+ *  - Edges: c = (a + b) div 2, in = in(c).  Towards each side d = -1, +1, j walks from c + d ni in steps of d; the box of j is
+ *    [max(0, j - w), min(4096, j + w + 1)), s its sum and n its bin count.  The walk stops at the first j with 4 s nin < in n (the box mean below a
+ *    quarter of the in-band mean), or at j = 0 or j = 4095: that j is the edge e_d.  offset_hz = floor(((e- + e+ - 4096) Fin + 4096) / 8192),
+ *    width_hz = floor((e+ - e-) Fin / 4096).  (The run centre alone is pulled several kHz by a strong neighbour; the edges are not.)
+ *  - Width gate: kept only when 1,436,000 <= width_hz <= 1,636,000.
+ *  - Raster, when center_hz > 0 (the capture's centre frequency; 0 = not known): if the nearest of the 38 Band III block centres (5A 174,928 kHz, B, C,
+ *    D each + 1712; the same from 6A 181,936, 7A 188,928, 8A 195,936, 9A 202,928, 10A 209,936, 11A 216,928, 12A 223,936; 13A 230,784, 13B 232,496,
+ *    13C 234,208, 13D 235,776, 13E 237,488, 13F 239,200) is within 32,000 Hz of center_hz + offset_hz, offset_hz becomes that centre minus center_hz
+ *    exactly and the block carries its name; otherwise the measured offset stays and the name is empty.
+ *  - The blocks in ascending offset, 16 at most: more is an error that names the count.
+ * Reach, as far as a plain model of all this was run on synthetic captures: a block down to 20 dB below its neighbour, about 5 dB of in-band SNR.
+ * Levels in dB are for display (10 log10 of in / nin and of the ratio to the guards) and enter no decision. */
+typedef struct dabhip_scan dabhip_scan;
+typedef struct dabhip_scan_block {
+  int64_t offset_hz;       /* the block's centre from the capture's centre: measured from the edges, or exact when snapped to the raster */
+  int64_t raw_center_hz;   /* the run's centre */
+  int64_t width_hz;
+  uint64_t in, lo, hi;     /* the sums of the run's centre bin: in over nin bins, lo and hi over ng bins each (saturating at 2^64 - 1, which no
+                              spectrum of a scan object reaches) */
+  int32_t nin, ng;
+  char name[8];            /* "5A" .. "13F", or "" */
+} dabhip_scan_block;
+#define DABHIP_SCAN_BINS 4096
+#define DABHIP_SCAN_DEFAULT_SEGMENTS 64
+/* nsegments: 1 .. 65536.  Rates: any integer from 2,048,000 to 10,240,000 (no table depends on the rate).  NULL on a refusal or without a GPU. */
+dabhip_scan *dabhip_scan_create(int device, int nstreams, int format, int64_t rate_hz, int nsegments);
+void dabhip_scan_destroy(dabhip_scan *d);
+/* Append nbytes[b] bytes (whole samples: refused otherwise) to stream b: host pointers, or device pointers aligned to a sample when on_device != 0.
+ * The up to 4095 samples of an unfinished segment are carried.  Synchronous.  Returns the segments accumulated by this push over all streams, <0 on
+ * error. */
+int64_t dabhip_scan_push(dabhip_scan *d, const void *const *src, const size_t *nbytes, int on_device);
+/* P of one stream (4096 bins in transform order) and the segments it holds so far. */
+int dabhip_scan_spectrum(const dabhip_scan *d, int stream, uint64_t *P, int *nsegments_done);
+/* dabhip_scan_spectrum followed by dabhip_scan_detect: copies min(n, cap) records, returns n, <0 on error. */
+int dabhip_scan_blocks(const dabhip_scan *d, int stream, int64_t center_hz, dabhip_scan_block *out, int cap);
+/* GPU time of the last push in ms (names: "upload", "transform", "keep"; as dabhip_engine_stage_ms); returns the count. */
+int dabhip_scan_stage_ms(const dabhip_scan *d, const char **names, float *ms, int cap);
+/* Without a GPU: the rule above on a spectrum of 4096 bins.  Copies min(n, cap) records, returns n, <0 on error (rate outside 2,048,000 ..
+ * 10,240,000, center_hz negative or above 10^12, more than 16 blocks). */
+int dabhip_scan_detect(const uint64_t *P, int64_t rate_hz, int64_t center_hz, dabhip_scan_block *out, int cap);
+/* -- and the bookkeeping of one stream over a sequence of pushes: nseg[i] = segments push i completes, carried[i] = samples kept behind it. */
+int dabhip_scan_plan(int nsegments, const int64_t *push_samples, int npush, int64_t *nseg, int64_t *carried);
+
 /* ---- synthetic Mode-I modulator (host only) --------------------------------------------- */
 typedef struct dabhip_subch_cfg {
   int32_t id;          /* SubChId 0..63 */
