@@ -48,12 +48,28 @@ class ChannelCfg(C.Structure):
                 ("iq_gain_db", C.c_double), ("iq_phase_deg", C.c_double)]
 
 
+class TiiCfg(C.Structure):
+    """dabhip_tii_cfg: one comb of the modulator's null symbol; level_db relative to a data carrier."""
+    _fields_ = [("enabled", C.c_int32), ("main_id", C.c_int32), ("sub_id", C.c_int32), ("pad", C.c_int32), ("level_db", C.c_double)]
+
+
 class SynthCfg(C.Structure):
     _fields_ = [("eid", C.c_uint32), ("nsub", C.c_int32), ("sub", SubChCfg * 64), ("seed", C.c_uint64),
                 ("cif_count0", C.c_int32), ("skip_samples", C.c_int32), ("amplitude", C.c_double),
                 ("snr_db", C.c_double), ("cfo_hz", C.c_double),
                 ("fib_patch_len", C.c_int32), ("fib_patch_from_cif", C.c_int32), ("fib_patch", C.c_uint8 * 32),
-                ("reconf", ReconfCfg * 2), ("channel", ChannelCfg), ("dabplus_slots", C.c_uint64), ("dabplus_phase", C.c_int32)]
+                ("reconf", ReconfCfg * 2), ("channel", ChannelCfg), ("dabplus_slots", C.c_uint64), ("dabplus_phase", C.c_int32),
+                ("tii_phase", C.c_int32), ("tii", TiiCfg * 4)]
+
+    def set_tii(self, combs, phase=0):
+        """The null symbol of every TF with (tf + phase) even carries these combs: up to four (main_id, sub_id, level_db); none = off."""
+        combs = list(combs)
+        if len(combs) > 4:
+            raise DabhipError("set_tii: at most four combs")
+        self.tii_phase = phase
+        for i in range(4):
+            t = self.tii[i]
+            t.enabled, t.main_id, t.sub_id, t.level_db = (1,) + tuple(combs[i]) if i < len(combs) else (0, 0, 0, 0.0)
 
     def set_reconf(self, k, at_cif, subs, fic_lead=0):
         """Reconfiguration k (0 / 1): from logical CIF at_cif on the multiplex is `subs`, a list of (id, start_cu, slform, uep_index, eep_protlev,
@@ -281,6 +297,17 @@ _SIGNATURES = {
     "dabhip_scan_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
     "dabhip_scan_detect": (C.c_int, [C.POINTER(C.c_uint64), C.c_int64, C.c_int64, C.c_void_p, C.c_int]),
     "dabhip_scan_plan": (C.c_int, [C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "dabhip_engine_set_tii": (C.c_int, [C.c_void_p, C.c_int]),
+    "dabhip_engine_tii_sums": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "dabhip_engine_tii": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "dabhip_engine_tii_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "dabhip_stream_set_tii": (C.c_int, [C.c_void_p, C.c_int]),
+    "dabhip_stream_tii_sums": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "dabhip_stream_tii": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "dabhip_stream_tii_reset": (C.c_int, [C.c_void_p]),
+    "dabhip_tii_detect": (C.c_int, [C.POINTER(C.c_uint64), C.c_void_p, C.c_int]),
+    "dabhip_tii_carriers": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int16), C.c_int]),
+    "dabhip_stage_tii": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None
@@ -1113,6 +1140,52 @@ class Scan:
             pass
 
 
+# ---- TII: which transmitters an ensemble comes from (dabhip.h: "TII") ---------------------------------------------
+TII_SUMS = 192
+TII_SHADOW = 1
+
+
+class TiiRecord(C.Structure):
+    """dabhip_tii_id."""
+    _fields_ = [("main_id", C.c_int32), ("sub_id", C.c_int32), ("flags", C.c_uint32), ("pad", C.c_int32), ("strong", C.c_uint64), ("weak", C.c_uint64)]
+
+
+def _tii_records(recs, n):
+    """The first n records as dicts: main, sub, shadow (the DABHIP_TII_SHADOW flag), strong, weak (s and n of the rule)."""
+    return [{"main": r.main_id, "sub": r.sub_id, "shadow": bool(r.flags & TII_SHADOW), "strong": r.strong, "weak": r.weak} for r in recs[:n]]
+
+
+def tii_detect(T):
+    """The transmitters in 192 folded sums T[8 c + b] (dabhip_tii_detect; no GPU needed): a list of records in ascending sub identifier."""
+    T = np.ascontiguousarray(T, dtype=np.uint64).reshape(-1)
+    _need(T.size == TII_SUMS, "tii_detect: 192 sums are wanted")
+    recs = (TiiRecord * 24)()
+    n = lib().dabhip_tii_detect(T.ctypes.data_as(C.POINTER(C.c_uint64)), C.cast(recs, C.c_void_p), 24)
+    _need(n >= 0, "tii_detect")
+    return _tii_records(recs, n)
+
+
+def tii_carriers(main_id, sub_id):
+    """The 32 carriers of transmitter (main_id, sub_id) (dabhip_tii_carriers; no GPU needed)."""
+    k = np.zeros(32, dtype=np.int16)
+    _need(lib().dabhip_tii_carriers(int(main_id), int(sub_id), k.ctypes.data_as(C.POINTER(C.c_int16)), 32) == 32, "tii_carriers")
+    return k
+
+
+def _tii_sums(fn, h, stream):
+    T = np.zeros(TII_SUMS, dtype=np.uint64)
+    frames = C.c_int(0)
+    _need(fn(h, int(stream), T.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(frames)) == 0, "tii_sums")
+    return T, frames.value
+
+
+def _tii_ids(fn, h, stream):
+    recs = (TiiRecord * 24)()
+    n = fn(h, int(stream), C.cast(recs, C.c_void_p), 24)
+    _need(n >= 0, "tii")
+    return _tii_records(recs, n)
+
+
 class Engine:
     def __init__(self, device=0, host_threads=0, _borrowed=None):
         self._owned = _borrowed is None
@@ -1310,6 +1383,42 @@ class Engine:
                                       ffs.ctypes.data_as(C.POINTER(C.c_double)), ncalls)
         _need(n >= 0, "engine_trace")
         return ints[:n], ffs[:n]
+
+    def set_tii(self, enable):
+        """Transmitter identification: every later decode also folds the null symbols of its frames onto the streams' sums; off by default."""
+        _need(lib().dabhip_engine_set_tii(self._h, 1 if enable else 0) == 0, "set_tii")
+
+    def tii_sums(self, stream):
+        """(the 192 sums T[8 c + b] of one stream of the last decode, the frames that counted)"""
+        return _tii_sums(lib().dabhip_engine_tii_sums, self._h, stream)
+
+    def tii(self, stream):
+        """The transmitters of one stream of the last decode as tii_detect gives them."""
+        return _tii_ids(lib().dabhip_engine_tii, self._h, stream)
+
+    def tii_ms(self):
+        """GPU time of the TII kernel in the last decode, ms."""
+        ms = C.c_float(0)
+        _need(lib().dabhip_engine_tii_ms(self._h, C.byref(ms)) == 0, "tii_ms")
+        return ms.value
+
+    def stage_tii(self, frames, w0, step, device_ptr=None):
+        """dabhip_stage_tii: contiguous frames (host array, or device_ptr) with a window start and a step each -> uint64 [nframes][192]."""
+        w0 = np.ascontiguousarray(w0, dtype=np.int32)
+        step = np.ascontiguousarray(step, dtype=np.uint32)
+        n = w0.size
+        _need(step.size == n, "stage_tii: one step per window")
+        if device_ptr is None:
+            frames = np.ascontiguousarray(frames, dtype=np.uint8)
+            _need(frames.size == n * TF_BYTES, "stage_tii: whole frames, one per window")
+            src, on_dev = frames.ctypes.data, 0
+        else:
+            src, on_dev = device_ptr, 1
+        T = np.zeros((n, TII_SUMS), dtype=np.uint64)
+        r = lib().dabhip_stage_tii(self._h, src, n, w0.ctypes.data_as(C.POINTER(C.c_int32)), step.ctypes.data_as(C.POINTER(C.c_uint32)), on_dev,
+                                   T.ctypes.data_as(C.POINTER(C.c_uint64)))
+        _need(r == n, "stage_tii")
+        return T
 
     def trace_nco(self, stream, ncalls):
         """per call: the re-tuning in Hz the software AFC applied to that call's samples (dabhip_engine_trace_nco)"""
@@ -1537,6 +1646,23 @@ class Stream:
     def set_soft_lanes(self, enable):
         """see Engine.set_soft_lanes (any time; single- and multi-device sessions)"""
         _need(self._f("set_soft_lanes")(self._h, 1 if enable else 0) == 0, "stream_set_soft_lanes")
+
+    def set_tii(self, enable):
+        """see Engine.set_tii: the sums accumulate over the session's segments until tii_reset (single-device sessions)"""
+        self._single_device("set_tii")
+        _need(lib().dabhip_stream_set_tii(self._h, 1 if enable else 0) == 0, "stream_set_tii")
+
+    def tii_sums(self, stream):
+        self._single_device("tii_sums")
+        return _tii_sums(lib().dabhip_stream_tii_sums, self._h, stream)
+
+    def tii(self, stream):
+        self._single_device("tii")
+        return _tii_ids(lib().dabhip_stream_tii, self._h, stream)
+
+    def tii_reset(self):
+        self._single_device("tii_reset")
+        _need(lib().dabhip_stream_tii_reset(self._h) == 0, "stream_tii_reset")
 
     def _single_device(self, what):
         """The entries that exist for dabhip_stream handles only: a multi-device session's handle is another type."""

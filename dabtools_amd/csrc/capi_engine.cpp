@@ -210,7 +210,33 @@ int dabhip_engine_fft_roofline(dabhip_engine* e, int reps, int64_t* launches, in
   return e->eng.fft_roofline(reps, launches, tfs, ms) != 0 ? -1 : 0;
 }
 
+// ---- transmitter identification (tii.cpp) ---------------------------------------------------------
+int dabhip_engine_set_tii(dabhip_engine* e, int enable) { if (!e) return -1; e->eng.set_tii(enable != 0); return 0; }
+int dabhip_engine_tii_sums(dabhip_engine* e, int stream, uint64_t* T, int* frames)
+{
+  if (!e || !e->has(stream)) { set_error("tii_sums: bad argument"); return -1; }
+  return e->eng.tii_sums(stream, T, frames) ? 0 : -1;
+}
+int dabhip_engine_tii(dabhip_engine* e, int stream, dabhip_tii_id* out, int cap)
+{
+  uint64_t T[DABHIP_TII_SUMS];
+  if (cap < 0 || (!out && cap > 0)) { set_error("tii: bad argument"); return -1; }
+  if (dabhip_engine_tii_sums(e, stream, T, nullptr) != 0) return -1;
+  return dabhip_tii_detect(T, out, cap);
+}
+int dabhip_engine_tii_ms(const dabhip_engine* e, float* ms)
+{
+  if (!e || !ms) { set_error("tii_ms: null argument"); return -1; }
+  *ms = e->eng.tii_ms();
+  return 0;
+}
+
 // ---- stage entries ----------------------------------------------------------------------------
+int dabhip_stage_tii(dabhip_engine* e, const uint8_t* frames, int nframes, const int32_t* w0, const uint32_t* step, int on_device, uint64_t* T)
+{
+  if (!e || !frames || !w0 || !step || !T) { set_error("stage_tii: null argument"); return -1; }
+  return e->eng.stage_tii(frames, nframes, w0, step, on_device != 0, T);
+}
 int dabhip_stage_ofdm_fft(dabhip_engine* e, const uint8_t* frames, int nframes, float* spectra, int on_device, int reps, float* kernel_ms)
 {
   if (!e || !frames) { set_error("stage_ofdm_fft: null argument"); return -1; }

@@ -115,6 +115,31 @@ void print_log(const char* text, const char* name, bool prefix)
   }
 }
 
+// --tii: the transmitters of one input on stderr, a line "TII: main=MM sub=SS level=X.XdB[ shadow]" per comb (level: relative to the input's
+// strongest comb; for display).  A batch prints once, a session whenever an input's list of identifiers differs from the one printed last.
+bool g_tii = false;
+struct TiiPrinter {
+  std::vector<std::string> last;                 // per input: the identifiers printed last
+  explicit TiiPrinter(int n) : last(static_cast<size_t>(n)) {}
+  void print(int i, const char* name, bool prefix, const dabhip_tii_id* ids, int n)
+  {
+    std::string key, text;
+    uint64_t top = 1;
+    for (int k = 0; k < n; ++k) top = std::max(top, ids[k].strong);
+    for (int k = 0; k < n; ++k) {
+      char line[96];
+      std::snprintf(line, sizeof line, "%d,%d,%u;", ids[k].main_id, ids[k].sub_id, ids[k].flags);
+      key += line;
+      std::snprintf(line, sizeof line, "TII: main=%02d sub=%02d level=%.1fdB%s\n", ids[k].main_id, ids[k].sub_id,
+                    10.0 * std::log10(static_cast<double>(std::max<uint64_t>(ids[k].strong, 1)) / static_cast<double>(top)), (ids[k].flags & DABHIP_TII_SHADOW) ? " shadow" : "");
+      text += line;
+    }
+    if (key == last[static_cast<size_t>(i)]) return;
+    last[static_cast<size_t>(i)] = key;
+    print_log(n ? text.c_str() : "TII: none\n", name, prefix);
+  }
+};
+
 // one session on one device, or one per device behind dabhip_multi_stream: the same calls either way
 struct Session {
   dabhip_stream* one = nullptr;
@@ -129,6 +154,8 @@ struct Session {
   void set_afc() { if (one) dabhip_stream_set_afc(one, 1); else dabhip_multi_stream_set_afc(many, 1); }
   void set_soft() { if (one) dabhip_stream_set_soft(one, 1); else dabhip_multi_stream_set_soft(many, 1); }
   void set_soft_lanes() { if (one) dabhip_stream_set_soft_lanes(one, 1); else dabhip_multi_stream_set_soft_lanes(many, 1); }
+  void set_tii() { if (one) dabhip_stream_set_tii(one, 1); }      // (main refuses --tii with several devices)
+  int tii(int i, dabhip_tii_id* out, int cap) { return one ? dabhip_stream_tii(one, i, out, cap) : 0; }
   void set_subchannels(const std::vector<int32_t>& ids)
   {
     if (one) dabhip_stream_set_subchannels(one, ids.data(), static_cast<int>(ids.size()));
@@ -163,6 +190,8 @@ int run_streaming(const std::vector<const char*>& names, size_t seg_bytes, bool 
   if (afc) ses.set_afc();
   if (soft) ses.set_soft();
   if (g_soft_lanes) ses.set_soft_lanes();
+  if (g_tii) ses.set_tii();
+  TiiPrinter tii_out(n);
   if (!subch.empty()) ses.set_subchannels(subch);
   constexpr int kBufs = 3, kOut = 2;
   uint8_t* buf[kBufs];
@@ -273,6 +302,14 @@ int run_streaming(const std::vector<const char*>& names, size_t seg_bytes, bool 
         char text[8192];
         for (int i = 0; i < n; ++i)
           if (s->log(i, text, sizeof text) > 0) print_log(text, names[i], n > 1);
+      }
+      if (g_tii) {
+        dabhip_tii_id ids[24];
+        for (int i = 0; i < n; ++i) {
+          const int found = s->tii(i, ids, 24);
+          if (found < 0) { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); rc = 2; break; }
+          tii_out.print(i, names[i], n > 1, ids, found);
+        }
       }
       ++segments;
       all_frames += frames;
@@ -439,6 +476,7 @@ int run_ingest(const std::vector<const char*>& names, bool streaming, size_t seg
     if (afc) dabhip_engine_set_afc(e, 1);
     if (soft) dabhip_engine_set_soft(e, 1);
     if (g_soft_lanes) dabhip_engine_set_soft_lanes(e, 1);
+    if (g_tii) dabhip_engine_set_tii(e, 1);
     if (!subch.empty()) dabhip_engine_set_subchannels(e, subch.data(), static_cast<int>(subch.size()));
     if (!push() || !outputs()) return fail();
     const int64_t nframes = dabhip_engine_decode(e, out.data(), out_bytes.data(), nout, 1);
@@ -447,6 +485,12 @@ int run_ingest(const std::vector<const char*>& names, bool streaming, size_t seg
       std::fprintf(stderr, "%s: %lld ETI frames\n", label[static_cast<size_t>(i)].c_str(), static_cast<long long>(dabhip_engine_eti_count(e, i)));
       char text[8192];
       if (!g_quiet && dabhip_engine_stream_log(e, i, text, sizeof text) > 0) print_log(text, label[static_cast<size_t>(i)].c_str(), nout > 1);
+      if (g_tii) {
+        dabhip_tii_id ids[24];
+        const int found = dabhip_engine_tii(e, i, ids, 24);
+        if (found < 0) return fail();
+        TiiPrinter(nout).print(i, label[static_cast<size_t>(i)].c_str(), nout > 1, ids, found);
+      }
     }
     // stream by stream, those with frames only: a block that gave nothing (a weak one the scan found, tuned a little off) does not stop the others
     for (int i = 0; i < nout; ++i) {
@@ -464,6 +508,8 @@ int run_ingest(const std::vector<const char*>& names, bool streaming, size_t seg
   if (afc) dabhip_stream_set_afc(s, 1);
   if (soft) dabhip_stream_set_soft(s, 1);
   if (g_soft_lanes) dabhip_stream_set_soft_lanes(s, 1);
+  if (g_tii) dabhip_stream_set_tii(s, 1);
+  TiiPrinter tii_out(nout);
   if (!subch.empty()) dabhip_stream_set_subchannels(s, subch.data(), static_cast<int>(subch.size()));
   // input bytes that give about seg_bytes of output: seg_bytes / 2 output samples are seg_bytes / 2 * rate / 2048000 input samples
   const size_t seg_in = static_cast<size_t>((static_cast<unsigned long long>(seg_bytes / 2) * static_cast<unsigned long long>(opt.rate) + 2047999) / 2048000) * sb;
@@ -503,6 +549,12 @@ int run_ingest(const std::vector<const char*>& names, bool streaming, size_t seg
       total[static_cast<size_t>(i)] += c;
       char text[8192];
       if (!g_quiet && dabhip_stream_log(s, i, text, sizeof text) > 0) print_log(text, label[static_cast<size_t>(i)].c_str(), nout > 1);
+      if (g_tii) {
+        dabhip_tii_id ids[24];
+        const int found = dabhip_stream_tii(s, i, ids, 24);
+        if (found < 0) return fail();
+        tii_out.print(i, label[static_cast<size_t>(i)].c_str(), nout > 1, ids, found);
+      }
     }
     for (int i = 0; i < n; ++i) {
       std::vector<uint8_t>& b = buf[static_cast<size_t>(i)];                             // the cut sample's first bytes to the front
@@ -563,6 +615,7 @@ int main(int argc, char** argv)
     }
     else if (std::strcmp(argv[i], "--stats") == 0) g_stats = true;
     else if (std::strcmp(argv[i], "--quiet") == 0) g_quiet = true;
+    else if (std::strcmp(argv[i], "--tii") == 0) g_tii = true;        // transmitter identification from the null symbols, on stderr
     else if (std::strcmp(argv[i], "--afc") == 0) afc = true;          // software AFC: captures with a carrier offset (no tuner to steer)
     else if (std::strcmp(argv[i], "--soft") == 0) soft = true;        // 4-bit soft decisions (not the reference's hard ones)
     else if (std::strcmp(argv[i], "--soft-lanes") == 0) g_soft_lanes = true;   // ... through the multi-lane decoder forms where the rule picks them (dabhip.h)
@@ -590,11 +643,15 @@ int main(int argc, char** argv)
     else { names.push_back(argv[i]); streaming = streaming || std::strcmp(argv[i], "-") == 0; }
   }
   if (names.empty()) {
-    std::fprintf(stderr, "Usage: dab2eti-hip [--stream] [--segment-calls N] [--afc] [--soft] [--soft-lanes] [--quiet] [--subch ID[,ID...]] [--devices A-B|A,B,...] [--format cu8|cs8|cs16|cf32] [--rate HZ] [--gain G] [--tune HZ[,HZ...]|auto] [--scan] [--center HZ] capture.cu8|- [more.cu8 ...] > out.eti\n");
+    std::fprintf(stderr, "Usage: dab2eti-hip [--stream] [--segment-calls N] [--afc] [--soft] [--soft-lanes] [--tii] [--quiet] [--subch ID[,ID...]] [--devices A-B|A,B,...] [--format cu8|cs8|cs16|cf32] [--rate HZ] [--gain G] [--tune HZ[,HZ...]|auto] [--scan] [--center HZ] capture.cu8|- [more.cu8 ...] > out.eti\n");
     return 1;
   }
   if (ingest.on() && devices.size() > 1) {
     std::fprintf(stderr, "dab2eti-hip: --format / --rate / --gain / --tune / --scan run on one device: the ingest stage does not span --devices\n");
+    return 1;
+  }
+  if (g_tii && devices.size() > 1) {
+    std::fprintf(stderr, "dab2eti-hip: --tii runs on one device: it does not go with several --devices\n");
     return 1;
   }
   if (ingest.scan && (ingest.tune_auto || !ingest.tune.empty())) {
@@ -639,7 +696,7 @@ int main(int argc, char** argv)
   std::vector<const uint8_t*> ptrs;
   std::vector<size_t> sizes;
   for (const auto& b : files) { ptrs.push_back(b.p); sizes.push_back(b.n); }
-  if (!devices.empty()) {
+  if (!devices.empty() && !g_tii) {
     // several devices (or an explicit one): the files are dealt to them in contiguous slices, all slices decode at once
     dabhip_multi* m = dabhip_multi_create(devices.data(), static_cast<int>(devices.size()));
     if (!m) { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); return 2; }
@@ -661,8 +718,9 @@ int main(int argc, char** argv)
     dabhip_multi_destroy(m);
     return 0;
   }
-  dabhip_engine* e = dabhip_engine_create(0);
+  dabhip_engine* e = dabhip_engine_create(devices.empty() ? 0 : devices[0]);      // (an explicit device: only with --tii, which the batch object lacks)
   if (!e) { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); return 2; }
+  if (g_tii) dabhip_engine_set_tii(e, 1);
   if (afc) dabhip_engine_set_afc(e, 1);
   if (soft) dabhip_engine_set_soft(e, 1);
   if (g_soft_lanes) dabhip_engine_set_soft_lanes(e, 1);
@@ -675,6 +733,12 @@ int main(int argc, char** argv)
     std::fprintf(stderr, "%s: %lld ETI frames\n", argv[b + 1], static_cast<long long>(dabhip_engine_eti_count(e, static_cast<int>(b))));
     char text[8192];
     if (!g_quiet && dabhip_engine_stream_log(e, static_cast<int>(b), text, sizeof text) > 0) print_log(text, argv[b + 1], files.size() > 1);
+    if (g_tii) {
+      dabhip_tii_id ids[24];
+      const int found = dabhip_engine_tii(e, static_cast<int>(b), ids, 24);
+      if (found < 0) { std::fprintf(stderr, "dab2eti-hip: %s\n", dabhip_last_error()); return 2; }
+      TiiPrinter(static_cast<int>(files.size())).print(static_cast<int>(b), argv[b + 1], files.size() > 1, ids, found);
+    }
   }
   // all frames, file by file in emission order, in ONE download into page-locked memory and one run of large writes
   if (n > 0) {

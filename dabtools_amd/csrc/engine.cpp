@@ -365,6 +365,9 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
   last_.deferred = 0;
   layout_ms_ = 0;
   if (!begin_decode(nstreams, cont)) return -1;
+  tii_ms_ = 0;
+  tii_ran_ = false;
+  if (tii_ && !tii_begin(nstreams, cont)) return -1;
   const SegmentLayout& seg = seg_;          // filled by layout_frames, from inside the scan
   struct SideStreamGuard {                   // whatever was queued on the side stream is awaited before returning
     hipStream_t s;
@@ -393,6 +396,7 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
     gpu_ok = check(chunk_ev_.back().create(), "hipEventCreate");
   }
   gpu_ok = gpu_ok && ofdm_msc_part(0, nmsc, chunk, 0);
+  if (tii_) gpu_ok = gpu_ok && tii_launch();      // behind the OFDM stage's launches: it delays none of them
   run.mark("ofdm queued");
   if (!check(hipEventSynchronize(ev_fibs_), "fic decode")) return -1;
   run.mark("fibs on host");
@@ -435,6 +439,7 @@ int64_t Engine::decode_impl(const uint8_t* const* iq, const size_t* nbytes, int 
     fft_tfs_ += std::min(chunk, nmsc - c * chunk);
   }
   msc_collect();
+  if (tii_ran_ && !elapsed(&tii_ms_, ev_tii_[0], ev_tii_[1])) return -1;
   if (!on_device && times_.h2d_bytes > 0 && !elapsed(&times_.h2d, ev_h2d_[0], ev_h2d_[1])) return -1;
   if (guard && !guard_check()) return -1;
   // what the next segment of a session starts from

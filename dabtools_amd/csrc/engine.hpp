@@ -315,6 +315,15 @@ class Engine {
   hipStream_t stream() const { return stream_; }
   int device() const { return device_; }
 
+  // -- transmitter identification (tii.cpp; include/dabhip.h: "TII") -------------------------------------
+  // on: every later decode / segment also folds the null symbols of its counted frames onto the streams' sums (k_tii.hip), one launch behind the OFDM
+  // stage's.  A decode() starts from zero sums; a session's further segments add to them until tii_reset().
+  void set_tii(bool on) { tii_ = on; }
+  bool tii_sums(int stream, uint64_t* T, int* frames);      // a stream's 192 sums and the frames counted
+  bool tii_reset();
+  float tii_ms() const { return tii_ms_; }
+  int stage_tii(const uint8_t* frames, int nframes, const int32_t* w0, const uint32_t* step, bool on_device, uint64_t* T);
+
  private:
   bool check(hipError_t e, const char* what);
   bool record(hipEvent_t e, hipStream_t s);
@@ -399,6 +408,9 @@ class Engine {
   bool fused_parts(int first, int n, int sym_a, int sym_b, int nparts);
   bool ofdm_msc_part(int first, int n, int chunk, int ev_base);
   bool complete_deferred();            // read_demapped_tf: the MSC part of the last decode's deferred frames, awaited
+  bool tii_tables();                   // the mixer's table on the device, the timing events
+  bool tii_begin(int nstreams, bool cont);   // the sums' rows reserved, and cleared unless a session goes on
+  bool tii_launch();                   // over the scan's descriptors as they stand, timed
 
   bool ok_ = false;
   bool afc_ = false, fused_ = true;
@@ -503,6 +515,18 @@ class Engine {
   HostList<CopyDesc> carry_out_descs_, carry_in_descs_;   // page-locked: they go up without the host waiting for the stream
 
   PlanTable plan_table_;
+
+  // transmitter identification: rows of kTiiRow words per stream (tii.hpp)
+  bool tii_ = false, tii_ran_ = false;
+  int tii_rows_ = 0;
+  float tii_ms_ = 0;
+  Event ev_tii_[2];
+  DeviceBuffer<uint32_t> d_tii_nco_;
+  DeviceBuffer<unsigned long long> d_tii_sums_, d_tii_stage_sums_;
+  DeviceBuffer<CallDesc> d_tii_descs_;
+  DeviceBuffer<const uint8_t*> d_tii_ptr_;
+  DeviceBuffer<int32_t> d_tii_w0_;
+  DeviceBuffer<uint32_t> d_tii_step_;
 
   PinnedBuffer<CallDesc> h_descs_;
   PinnedBuffer<int2> h_info_;

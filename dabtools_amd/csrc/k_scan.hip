@@ -7,7 +7,8 @@
 //                               the caller (or the carry) left them and converted on the way;
 //     pass 1 (h = 16 .. 128):   thread (hi, lo) = (t >> 4, t & 15) holds indices 256 hi + 16 j + lo;
 //     pass 2 (h = 256 .. 2048): thread t holds indices 256 j + t, which are the bins it then owns.
-//   A stage's butterflies pair the registers whose j differ in one bit, and a butterfly rounds exactly as the header's does.  The two rails are two
+//   A stage's butterflies pair the registers whose j differ in one bit, and a butterfly rounds exactly as the header's does (fixed_butterfly.hpp,
+//   shared with k_tii.hip).  The two rails are two
 //   LDS arrays of words, index i at i + (i >> 4): the stride of 17 spreads pass 0's writes (16 t + j) and pass 1's accesses over all banks.  The
 //   twiddles are the tuned mode's NCO table, 16 KiB in LDS; pass 0's are known when the code is compiled (those of h = 1, 2 are 1 and -j: exact, no
 //   product).  Both factors of every product fit 24 bits (the header's range proof): v_mul_i32_i24.
@@ -17,6 +18,7 @@
 
 #include <type_traits>
 
+#include "fixed_butterfly.hpp"
 #include "ingest_sample.hpp"
 #include "scan.hpp"
 
@@ -40,19 +42,6 @@ __device__ __forceinline__ int2 fetch16(const ScanDesc& d, int64_t n)
   return int2{v.x * (1 << post_shift<F>()), v.y * (1 << post_shift<F>())};
 }
 
-// a' = (a + t + 1) >> 1, b' = (a - t + 1) >> 1 per rail
-__device__ __forceinline__ void halve(int2& a, int2& b, int ti, int tq)
-{
-  const int2 a0 = a;
-  a = int2{(a0.x + ti + 1) >> 1, (a0.y + tq + 1) >> 1};
-  b = int2{(a0.x - ti + 1) >> 1, (a0.y - tq + 1) >> 1};
-}
-__device__ __forceinline__ void butterfly(int2& a, int2& b, uint32_t cs)
-{
-  const int c = static_cast<short>(cs & 0xffffu), s = static_cast<short>(cs >> 16);
-  const int ti = (__mul24(b.x, c) + __mul24(b.y, s) + 8192) >> 14, tq = (__mul24(b.y, c) - __mul24(b.x, s) + 8192) >> 14;
-  halve(a, b, ti, tq);
-}
 
 // four stages on the 16 registers of a thread: register j is index base + j 16^P, and low = base mod 16^P
 template <int P>

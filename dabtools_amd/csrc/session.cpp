@@ -174,6 +174,24 @@ int dabhip_stream_set_subchannels(dabhip_stream* s, const int32_t* ids, int n)
   s->eng.set_subchannel_filter(subchannel_mask(ids, n));
   return 0;
 }
+int dabhip_stream_set_tii(dabhip_stream* s, int on) { if (!s) return -1; s->eng.set_tii(on != 0); return 0; }
+int dabhip_stream_tii_sums(dabhip_stream* s, int stream, uint64_t* T, int* frames)
+{
+  if (!s || stream < 0 || stream >= s->n) { set_error("stream_tii_sums: bad argument"); return -1; }
+  return s->eng.tii_sums(stream, T, frames) ? 0 : -1;
+}
+int dabhip_stream_tii(dabhip_stream* s, int stream, dabhip_tii_id* out, int cap)
+{
+  uint64_t T[DABHIP_TII_SUMS];
+  if (cap < 0 || (!out && cap > 0)) { set_error("stream_tii: bad argument"); return -1; }
+  if (dabhip_stream_tii_sums(s, stream, T, nullptr) != 0) return -1;
+  return dabhip_tii_detect(T, out, cap);
+}
+int dabhip_stream_tii_reset(dabhip_stream* s)
+{
+  if (!s) { set_error("stream_tii_reset: null handle"); return -1; }
+  return s->eng.tii_reset() ? 0 : -1;
+}
 int dabhip_stream_set_afc(dabhip_stream* s, int on) { if (!s) return -1; s->eng.set_afc(on != 0); return 0; }
 int dabhip_stream_set_parity_guard(dabhip_stream* s, int on) { if (!s) return -1; s->eng.set_parity_guard(on); return 0; }
 int dabhip_stream_set_sync_speculation(dabhip_stream* s, int mode) { if (!s) return -1; s->eng.set_sync_speculation(mode); return 0; }

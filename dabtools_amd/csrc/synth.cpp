@@ -13,6 +13,7 @@
 #include "dab_tables.hpp"
 #include "dabplus.hpp"
 #include "synth.hpp"
+#include "tii_detect.hpp"
 
 namespace dabhip {
 void set_error(const std::string& msg);
@@ -110,6 +111,11 @@ bool validate(const dabhip_synth_cfg& cfg)
   for (int e = 0; e < 2; ++e)
     if (c.echo_delay[e] < 0 || c.echo_delay[e] > 2047) { set_error("synth: echo delay out of range (0 .. 2047 samples)"); return false; }
   if (c.fade_depth < 0.0 || c.fade_depth >= 1.0 || std::fabs(c.sro_ppm) > 1000.0) { set_error("synth: channel parameters out of range"); return false; }
+  for (const dabhip_tii_cfg& t : cfg.tii)
+    if (t.enabled && (t.main_id < 0 || t.main_id >= kTiiPatterns || t.sub_id < 0 || t.sub_id >= kTiiSubs || !std::isfinite(t.level_db))) {
+      set_error("synth: a TII comb needs main_id 0 .. 69, sub_id 0 .. 23 and a finite level");
+      return false;
+    }
   return true;
 }
 
@@ -488,6 +494,13 @@ class Channel {
 
 bool synth_channel_active(const dabhip_synth_cfg& cfg) { return channel_active(cfg.channel); }
 
+bool synth_tii_active(const dabhip_synth_cfg& cfg)
+{
+  for (const dabhip_tii_cfg& t : cfg.tii)
+    if (t.enabled) return true;
+  return false;
+}
+
 uint64_t synth_noise_key(uint64_t seed, uint64_t ctr, uint64_t which) { return key(seed, kDomNoise, ctr, which); }
 
 bool synth_validate(const dabhip_synth_cfg& cfg) { return validate(cfg); }
@@ -619,9 +632,31 @@ extern "C" int64_t dabhip_synth_generate(const dabhip_synth_cfg* cfg, int ntf, u
   };
   auto emit = [&](double xr, double xi) { channel.push(xr, xi, quantise); };
 
+  // one period of the TII symbol (include/dabhip.h, "TII"): the enabled combs' carriers, both of a pair with the phase reference of the lower one
+  const bool tii = synth_tii_active(*cfg);
+  std::vector<double> tii_re(2048, 0.0), tii_im(2048, 0.0);
+  if (tii) {
+    for (const dabhip_tii_cfg& t : cfg->tii) {
+      if (!t.enabled) continue;
+      int16_t k[kTiiCarriers];
+      tii_carriers(t.main_id, t.sub_id, k);
+      const double level = cfg->amplitude * std::pow(10.0, t.level_db / 20.0);
+      for (int i = 0; i < kTiiCarriers; ++i) {
+        const int lower = k[i & ~1];
+        const int q = 2 * prs[lower < 0 ? lower + 768 : lower + 767];      // eighth turns
+        tii_re[(k[i] + 2048) % 2048] += level * c8[q];
+        tii_im[(k[i] + 2048) % 2048] += level * s8[q];
+      }
+    }
+    fft2048(tii_re.data(), tii_im.data(), +1);
+  }
+
   for (int tf = 0; tf < ntf; ++tf) {
     bits.next_tf(symbits.data());
-    for (int n = 0; n < kNullSamples; ++n) emit(0, 0);
+    if (tii && ((tf + cfg->tii_phase) & 1) == 0)
+      for (int n = 0; n < kNullSamples; ++n) emit(tii_re[(n + 2048 - 608) % 2048], tii_im[(n + 2048 - 608) % 2048]);
+    else
+      for (int n = 0; n < kNullSamples; ++n) emit(0, 0);
     for (int l = 0; l < kSymbolsPerTf; ++l) {
       if (l == 0) {
         for (int k = 0; k < kCarriers; ++k) phase[k] = static_cast<uint8_t>(2 * prs[k]);

@@ -767,6 +767,78 @@ int dabhip_scan_detect(const uint64_t *P, int64_t rate_hz, int64_t center_hz, da
 /* -- and the bookkeeping of one stream over a sequence of pushes: nseg[i] = segments push i completes, carried[i] = samples kept behind it. */
 int dabhip_scan_plan(int nsegments, const int64_t *push_samples, int npush, int64_t *nseg, int64_t *carried);
 
+/* ---- TII: which transmitters a received ensemble comes from ------------------------------------------------------
+ * Off unless asked for (dabhip_engine_set_tii / dabhip_stream_set_tii): the decoder otherwise uses the null symbol for coarse timing only.  In a
+ * Mode-I single-frequency network every transmitter marks the null symbol of every second transmission frame with its own comb of carriers (ETSI
+ * EN 300 401, clause 14.8): a main identifier 0 .. 69 and a sub identifier 0 .. 23.  With TII on, a decode transforms a window of the null symbol of
+ * every demodulated frame, folds the power onto 24 x 8 sums per stream, and a host rule reads the identifiers off the sums.  ETI bytes, traces,
+ * operator text and stage names are those of a decode without it.  The arithmetic is integer and stated here in full, so the sums are those of a
+ * plain model (tests/tii_model.py), bit for bit, whatever the launch shape:
+ *  0. Patterns and carriers.  The 70 patterns are the 8-bit words with exactly four ones in ascending numeric order (pattern 0 = 0x0f, pattern 69 =
+ *     0xf0); a_b(p) is bit 7 - b of word p, b = 0 .. 7.  Transmitter (p, c) sends, for every b with a_b(p) = 1 and every quarter base in {-768, -384,
+ *     1, 385}, the carrier pair k = base + 2 c + 48 b and k + 1: 32 carriers (dabhip_tii_carriers), both of a pair with the phase-reference phase of
+ *     the lower one (the standard's A(k) e^(j phi_k) + A(k-1) e^(j phi_(k-1))).  Over c, b, the quarters and the two carriers these tile the 1536
+ *     carriers exactly once.
+ *  1. Frames counted.  A demodulated call (what dabhip_engine_trace reports as ok) counts when |fine_timeshift| <= 304 and
+ *     |fine_freq_shift| < 1,024,000 (a NaN does not count; no estimate of the front end comes near the bound, it only keeps step 3 in range).
+ *  2. Window and samples.  2048 samples of the call's frame buffer from sample w0 = 304 + fine_timeshift on (0 <= w0 <= 608: the TII symbol has
+ *     period 2048 over the 2656 samples of the null symbol, so every such window holds one period); x = (byte - 127) 128 per rail.
+ *  3. De-rotation.  f = 1000 coarse_freq_shift + fine_freq_shift + nco_hz in Hz (doubles, added left to right; nco_hz: dabhip_engine_trace_nco,
+ *     0 without the software AFC) -- the capture's carrier offset as the front end measured it, same sign as dabhip_synth_cfg.cfo_hz.
+ *     step = nearbyint(f 4294967296.0 / 2048000.0) mod 2^32 (doubles, left to right, ties to even); theta_n = (step n) mod 2^32 with n counted from
+ *     the window's first sample; table index i = ((theta_n + 2^19) mod 2^32) >> 20 into dabhip_ingest_tune_nco;
+ *       yI = (xI c[i] + xQ s[i] + 8192) >> 14,   yQ = (xQ c[i] - xI s[i] + 8192) >> 14      (the tuned mode's product, arithmetic shifts, no clamp)
+ *  4. Transform: the block scan's step 2 with 2048 points -- on the bit-reversed window (v[i] = y[bit-reverse11(i)]), stages of half size h = 1, 2,
+ *     ..., 1024, table index t = q (2048 / h) in the same 4096-entry table, the same butterfly with its two roundings.  X[k] is about
+ *     (1/2048) sum y[n] e^(-2 pi j k n / 2048).
+ *  5. Range: the block scan's step 4 with half the input range.  |x| <= 16384 per rail, a magnitude of at most 16384 sqrt 2 = 23,171; the
+ *     de-rotation gives at most 23,171 (1 + 2^-14) + 1 < 23,175, and 11 stages add less than 33: every value stays within +-23,210 per rail, both
+ *     products of a sum together below 23,210 x 16,385 < 2^29: int32 arithmetic and 24-bit factors hold a fortiori.
+ *  6. Fold.  Carrier k lies in bin k mod 2048.  T[c][b] += XI^2 + XQ^2 over the eight bins of (c, b) -- four quarters times two carriers -- of every
+ *     counted frame: exact uint64 sums (at most about 2^32 per frame and sum), so neither launch shape nor order can matter.  T is stored as
+ *     T[8 c + b], 192 values.
+ * From sums to identifiers (dabhip_tii_detect; integers, 128-bit products).  For each c: order the eight T[c][b] descending, ties to the lower b:
+ * v0 .. v7; s = v0 + v1 + v2 + v3, n = v4 + .. + v7.  The comb is present when s > 2 n and v3 > 2 v4 (both strict: an all-zero T yields nothing); its
+ * main identifier is the index of the word made of the four strongest b.  DABHIP_TII_SHADOW flags a comb when another present comb has the same main
+ * identifier and an s more than 64 times larger: the leakage of a strong comb under a residual frequency error looks like that -- flagged, not
+ * dropped, because a real weak transmitter of the same main identifier looks the same.  Records come out in ascending c, 24 at most.  Several
+ * transmitters that share one sub identifier are NOT separated: their combs add, and the rule sees the four strongest b of the sum or nothing.
+ * Reach, as far as a plain model of all this was run on the modulator's captures (28 LSB rms per rail, TII in every second frame): one transmitter
+ * at the level of a data carrier from 8 frames on at 5 dB, transmitters 10 and 20 dB below the strongest in 16 clean frames, nothing in noise alone
+ * at 5 dB in 2 and in 8 frames.  The rule compares a comb with the bins around it and does not subtract the noise floor, so noise bounds its reach
+ * however many frames are folded: at 9 dB a comb at the level of a data carrier beside one 10 dB stronger is found from 4 frames on and a comb 4 dB
+ * below a data carrier from 6 frames on, a comb 7 dB or more below a data carrier never.  Levels in dB are for display and enter no decision. */
+#define DABHIP_TII_SUMS 192
+#define DABHIP_TII_SHADOW 1u
+typedef struct dabhip_tii_id {
+  int32_t main_id;         /* 0 .. 69 */
+  int32_t sub_id;          /* 0 .. 23 */
+  uint32_t flags;          /* DABHIP_TII_SHADOW */
+  int32_t pad;
+  uint64_t strong, weak;   /* s and n of the rule (saturating at 2^64 - 1, which no sum of a decode reaches) */
+} dabhip_tii_id;
+/* enable != 0: every later decode also runs the TII stage: one kernel over the decode's calls, on the engine's stream behind the OFDM stage's launches. */
+int dabhip_engine_set_tii(dabhip_engine *e, int enable);
+/* The sums of one stream of the last decode (zero when it began) and the frames that counted; either pointer may be NULL. */
+int dabhip_engine_tii_sums(dabhip_engine *e, int stream, uint64_t *T, int *frames);
+/* dabhip_engine_tii_sums followed by dabhip_tii_detect: copies min(n, cap) records, returns n, <0 on error. */
+int dabhip_engine_tii(dabhip_engine *e, int stream, dabhip_tii_id *out, int cap);
+/* GPU time of the TII kernel in the last decode in ms (HIP events); 0 when it did not run.  Not among dabhip_engine_stage_ms's names. */
+int dabhip_engine_tii_ms(const dabhip_engine *e, float *ms);
+/* The same for a session: the sums accumulate over the session's segments until dabhip_stream_tii_reset. */
+int dabhip_stream_set_tii(dabhip_stream *s, int enable);
+int dabhip_stream_tii_sums(dabhip_stream *s, int stream, uint64_t *T, int *frames);
+int dabhip_stream_tii(dabhip_stream *s, int stream, dabhip_tii_id *out, int cap);
+int dabhip_stream_tii_reset(dabhip_stream *s);
+/* Without a GPU: the rule above on 192 sums.  Copies min(n, cap) records, returns n (0 .. 24), <0 on error (T NULL, cap < 0, out NULL with cap > 0). */
+int dabhip_tii_detect(const uint64_t *T, dabhip_tii_id *out, int cap);
+/* -- and the 32 carriers (-768 .. 768 without 0) of transmitter (main_id, sub_id), quarter after quarter, ascending within each.  Returns 32,
+ * <0 on error (no such transmitter, k NULL, cap < 32). */
+int dabhip_tii_carriers(int main_id, int sub_id, int16_t *k, int cap);
+/* Stage entry (parity tests): steps 2 - 6 on nframes contiguous frames of 393216 bytes (device pointer when on_device) with explicit window starts
+ * w0[j] (0 .. 608, refused otherwise) and steps step[j] (host arrays) -> T[nframes][192] (host), one T per frame. */
+int dabhip_stage_tii(dabhip_engine *e, const uint8_t *frames, int nframes, const int32_t *w0, const uint32_t *step, int on_device, uint64_t *T);
+
 /* ---- synthetic Mode-I modulator (host only) --------------------------------------------- */
 typedef struct dabhip_subch_cfg {
   int32_t id;          /* SubChId 0..63 */
@@ -800,6 +872,14 @@ typedef struct dabhip_channel_cfg {
   double iq_phase_deg;     /* quadrature error: Q' = g (Q cos phi + I sin phi) */
 } dabhip_channel_cfg;
 
+typedef struct dabhip_tii_cfg {
+  int32_t enabled;
+  int32_t main_id;         /* 0 .. 69 */
+  int32_t sub_id;          /* 0 .. 23 */
+  int32_t pad;
+  double level_db;
+} dabhip_tii_cfg;
+
 typedef struct dabhip_synth_cfg {
   uint32_t eid;
   int32_t nsub;
@@ -832,6 +912,13 @@ typedef struct dabhip_synth_cfg {
    * slots' bit rates must be multiples of 8 kbit/s; refused together with reconfigurations. */
   uint64_t dabplus_slots;
   int32_t dabplus_phase;
+  /* TII (see "TII" above; all zero = off, byte-identical captures): transmission frames tf (counted from the capture's first) with tf + tii_phase
+   * even carry, in the 2656 samples of their null symbol, the sum of the enabled combs: amplitude sum over the comb's carriers k of
+   * 10^(level_db / 20) e^(j phi) e^(2 pi j k (n - 608) / 2048), phi the phase-reference phase of the pair's lower carrier.  level_db is relative to a
+   * data carrier.  The other frames' null symbols stay silent; the noise draws do not move.  Host generator only: dabhip_synth_generate_device
+   * refuses a configuration with TII set. */
+  int32_t tii_phase;
+  dabhip_tii_cfg tii[4];
 } dabhip_synth_cfg;
 
 /* preset 0: 12 sub-channels, 1136 kbit/s, 862 CU (the benchmark mix); 1: 4 light sub-channels. */
