@@ -486,6 +486,42 @@ def stream_ceiling(device=0, nbytes=4 << 30, reps=3):
     return {"fill": g[0], "copy": g[1], "k2_mix": g[2]}
 
 
+class _Handle:
+    """A C handle in self._h, destroyed once by the entry named _destroy: at close() or when the object goes."""
+    _h = _destroy = None
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:                       # at interpreter shutdown the module globals may already be gone
+            self.close()
+        except Exception:
+            pass
+
+
+def _stage_ms(fn, h, n):
+    """The *_stage_ms entries of the side stages: {stage: GPU time of the last push in ms}, at most n stages."""
+    names, ms = (C.c_char_p * n)(), (C.c_float * n)()
+    return {names[i].decode(): ms[i] for i in range(fn(h, names, ms, n))}
+
+
+def _push_samples(fn, what, h, nstreams, ptrs, sizes, on_device):
+    """dabhip_ingest_push and dabhip_scan_push over raw addresses, one per stream."""
+    _need(len(ptrs) == nstreams and len(sizes) == nstreams, what + ": one input per stream")
+    n = fn(h, (C.c_void_p * nstreams)(*ptrs), (C.c_size_t * nstreams)(*sizes), 1 if on_device else 0)
+    _need(n >= 0, what)
+    return n
+
+
+def _sample_bytes(what, nstreams, arrays):
+    """One array per stream as bytes (the caller keeps them alive over the push)."""
+    _need(len(arrays) == nstreams, what + ": one array per stream")
+    return [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in arrays]
+
+
 class HostBuffer:
     """nbytes of page-locked host memory (dabhip_host_alloc): .array is a numpy view, .ptr its address.  Uploads from it are
     plain asynchronous DMA at the PCIe rate; pageable memory goes through the engine's staging ring instead."""
@@ -616,8 +652,9 @@ def host_table(which):
     return out[:n].reshape(shape)
 
 
-class HostFifo:
+class HostFifo(_Handle):
     """The FIFO / frame-buffer bookkeeping of the sync-scan kernel, on the host (dabhip_host_fifo_*)."""
+    _destroy = "dabhip_host_fifo_free"
 
     def __init__(self):
         self._h = lib().dabhip_host_fifo_new()
@@ -655,17 +692,6 @@ class HostFifo:
             buf[TF_BYTES - TAIL_BYTES:] = tail
         return buf
 
-    def close(self):
-        if self._h:
-            lib().dabhip_host_fifo_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---- S1 -----------------------------------------------------------------------------------------
 def viterbi(symbols, framebits, n=1):
@@ -679,8 +705,9 @@ def viterbi(symbols, framebits, n=1):
 
 
 # ---- S2 -----------------------------------------------------------------------------------------
-class Sdr:
+class Sdr(_Handle):
     """sdr_init + sdr_demod (input_sdr.h:43-44) for one stream."""
+    _destroy = "dabhip_sdr_free"
 
     def __init__(self, device=0):
         self._h = lib().dabhip_sdr_init(device)
@@ -700,21 +727,11 @@ class Sdr:
         return (L.dabhip_sdr_coarse_timeshift(self._h), L.dabhip_sdr_fine_timeshift(self._h),
                 L.dabhip_sdr_coarse_freq_shift(self._h), L.dabhip_sdr_fine_freq_shift(self._h))
 
-    def close(self):
-        if self._h:
-            lib().dabhip_sdr_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---- S3 -----------------------------------------------------------------------------------------
-class Dab:
+class Dab(_Handle):
     """init_dab_state + dab_process_frame (dab.h:91-92) for one stream."""
+    _destroy = "dabhip_dab_free"
 
     def __init__(self, device=0, soft=False, forms=None, soft_lanes=False):
         self.frames = []
@@ -777,17 +794,6 @@ class Dab:
         lib().dabhip_dab_last_fibs(self._h, _p(fibs), _p(ok))
         return fibs, ok
 
-    def close(self):
-        if self._h:
-            lib().dabhip_dab_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---- batch engine -------------------------------------------------------------------------------
 # one record of dabhip_dabplus_superframes (dabhip.h: dabhip_dabplus_sf)
@@ -799,9 +805,10 @@ assert DABPLUS_SF.itemsize == 64
 DABPLUS_STATS = ("superframes", "fire_fails", "rs_corrected_bytes", "rs_failed_codewords", "aus", "au_crc_fails", "sync_losses")
 
 
-class DabPlus:
+class DabPlus(_Handle):
     """DAB+ audio out of ETI frames on the GPU (dabhip_dabplus_*): superframe sync, RS(120,110) correction, AU CRCs, for nstreams streams and the
     DAB+ sub-channels subch_ids of each.  State (sync, the last 4 frames of every stream) carries from push to push."""
+    _destroy = "dabhip_dabplus_destroy"
 
     def __init__(self, nstreams, subch_ids, device=0):
         self.nstreams, self.subch_ids = int(nstreams), [int(i) for i in subch_ids]
@@ -876,21 +883,7 @@ class DabPlus:
 
     def stage_ms(self):
         """GPU time of the last push per stage: {"locate", "sync", "rs", "au", "carry"} in ms."""
-        names = (C.c_char_p * 5)()
-        ms = (C.c_float * 5)()
-        n = lib().dabhip_dabplus_stage_ms(self._h, names, ms, 5)
-        return {names[i].decode(): ms[i] for i in range(n)}
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dabhip_dabplus_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _stage_ms(lib().dabhip_dabplus_stage_ms, self._h, 5)
 
 
 # ---- ingest stage: other sample formats and rates -> cu8 at 2.048 Msps (dabhip.h: dabhip_ingest_*) -----------------
@@ -965,11 +958,12 @@ def ingest_auto_gain(energy):
     return lib().dabhip_ingest_auto_gain(int(energy))
 
 
-class Ingest:
+class Ingest(_Handle):
     """nstreams streams of fmt ("cu8", "cs8", "cs16", "cf32") IQ at `rate` samples/s -> cu8 at 2.048 Msps in device memory (dabhip_ingest_*).
     gain: the requantisation gain (256 = 16-bit full scale to 8-bit full scale), 0 = automatic.  State carries from push to push.
     offsets: the tuned mode (dabhip_ingest_create_tuned) -- every input stream gives len(offsets) output streams, channel c the DAB block centred
     offsets[c] Hz from the capture's centre; output stream `stream * nchannels + channel` is what output_ptrs, read and gain index."""
+    _destroy = "dabhip_ingest_destroy"
 
     def __init__(self, device, nstreams, fmt, rate, gain=0, offsets=None):
         self.nstreams, self.fmt = int(nstreams), _ingest_format(fmt)
@@ -986,19 +980,12 @@ class Ingest:
 
     def push(self, arrays):
         """One array per stream (any dtype: its bytes are the samples, possibly none) -> total output bytes of this push."""
-        _need(len(arrays) == self.nstreams, "ingest_push: one array per stream")
-        arrs = [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in arrays]
-        self._keep = arrs
+        self._keep = arrs = _sample_bytes("ingest_push", self.nstreams, arrays)
         return self.push_ptrs([a.ctypes.data for a in arrs], [a.size for a in arrs], on_device=False)
 
     def push_ptrs(self, ptrs, sizes, on_device=False):
         """push() over raw addresses: host memory, or device memory aligned to a sample."""
-        p = (C.c_void_p * len(ptrs))(*ptrs)
-        s = (C.c_size_t * len(sizes))(*sizes)
-        _need(len(ptrs) == self.nstreams and len(sizes) == self.nstreams, "ingest_push: one input per stream")
-        n = lib().dabhip_ingest_push(self._h, p, s, 1 if on_device else 0)
-        _need(n >= 0, "ingest_push")
-        return n
+        return _push_samples(lib().dabhip_ingest_push, "ingest_push", self._h, self.nstreams, ptrs, sizes, on_device)
 
     def output_ptrs(self):
         """(device addresses, byte counts) of this push's cu8, per output stream: what Engine.decode_device and Stream.feed_ptrs(on_device=True) take.
@@ -1029,21 +1016,7 @@ class Ingest:
 
     def stage_ms(self):
         """GPU time of the last push per stage: {"upload", "energy", "resample", "keep"} in ms."""
-        names = (C.c_char_p * 4)()
-        ms = (C.c_float * 4)()
-        n = lib().dabhip_ingest_stage_ms(self._h, names, ms, 4)
-        return {names[i].decode(): ms[i] for i in range(n)}
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dabhip_ingest_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _stage_ms(lib().dabhip_ingest_stage_ms, self._h, 4)
 
 
 # ---- block scan: which DAB blocks lie in a wideband capture (dabhip.h: dabhip_scan_*) ------------------------------
@@ -1083,9 +1056,10 @@ def scan_plan(nsegments, pushes):
     return list(nseg)[:n], list(keep)[:n]
 
 
-class Scan:
+class Scan(_Handle):
     """The power spectrum of the first nsegments segments of 4096 samples of nstreams streams of fmt IQ at `rate` samples/s, and the DAB blocks in
     it (dabhip_scan_*).  State carries from push to push; samples past the window are ignored."""
+    _destroy = "dabhip_scan_destroy"
 
     def __init__(self, device, nstreams, fmt, rate, nsegments=SCAN_DEFAULT_SEGMENTS):
         self.nstreams, self.fmt, self.rate = int(nstreams), _ingest_format(fmt), int(rate)
@@ -1094,18 +1068,12 @@ class Scan:
 
     def push(self, arrays):
         """One array per stream (any dtype: its bytes are the samples, possibly none) -> segments accumulated by this push over all streams."""
-        _need(len(arrays) == self.nstreams, "scan_push: one array per stream")
-        arrs = [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in arrays]
+        self._keep = arrs = _sample_bytes("scan_push", self.nstreams, arrays)
         return self.push_ptrs([a.ctypes.data for a in arrs], [a.size for a in arrs], on_device=False)
 
     def push_ptrs(self, ptrs, sizes, on_device=False):
         """push() over raw addresses: host memory, or device memory aligned to a sample."""
-        _need(len(ptrs) == self.nstreams and len(sizes) == self.nstreams, "scan_push: one input per stream")
-        p = (C.c_void_p * len(ptrs))(*ptrs)
-        s = (C.c_size_t * len(sizes))(*sizes)
-        n = lib().dabhip_scan_push(self._h, p, s, 1 if on_device else 0)
-        _need(n >= 0, "scan_push")
-        return n
+        return _push_samples(lib().dabhip_scan_push, "scan_push", self._h, self.nstreams, ptrs, sizes, on_device)
 
     def spectrum(self, stream):
         """(P: uint64 [4096] in transform order, segments accumulated) of one stream."""
@@ -1123,21 +1091,7 @@ class Scan:
 
     def stage_ms(self):
         """GPU time of the last push per stage: {"upload", "transform", "keep"} in ms."""
-        names = (C.c_char_p * 3)()
-        ms = (C.c_float * 3)()
-        n = lib().dabhip_scan_stage_ms(self._h, names, ms, 3)
-        return {names[i].decode(): ms[i] for i in range(n)}
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().dabhip_scan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _stage_ms(lib().dabhip_scan_stage_ms, self._h, 3)
 
 
 # ---- TII: which transmitters an ensemble comes from (dabhip.h: "TII") ---------------------------------------------
@@ -1186,7 +1140,7 @@ def _tii_ids(fn, h, stream):
     return _tii_records(recs, n)
 
 
-class Engine:
+class Engine(_Handle):
     def __init__(self, device=0, host_threads=0, _borrowed=None):
         self._owned = _borrowed is None
         self._h = _borrowed or lib().dabhip_engine_create_ex(device, host_threads)
@@ -1479,17 +1433,12 @@ class Engine:
             lib().dabhip_engine_destroy(self._h)
         self._h = None
 
-    def __del__(self):
-        try:                       # at interpreter shutdown the module globals may already be gone
-            self.close()
-        except Exception:
-            pass
 
-
-class Multi:
+class Multi(_Handle):
     """The batch engine over several devices of one node (dabhip_multi_*): streams dealt to the devices in contiguous slices
     (2048 on 8 = stream s on device s // 256), all slices decoding at once, no exchange between them.  A device may be listed
     several times (every entry is its own slice)."""
+    _destroy = "dabhip_multi_destroy"
 
     def __init__(self, devices):
         devs = list(devices)
@@ -1600,23 +1549,12 @@ class Multi:
     def wall_ms(self, slice_index=-1):
         return lib().dabhip_multi_wall_ms(self._h, slice_index)
 
-    def close(self):
-        if self._h:
-            lib().dabhip_multi_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Stream:
+class Stream(_Handle):
     """Streaming session (dabhip_stream_*): B unbounded captures decoded segment by segment; the concatenated ETI
     frames equal one Engine.decode of the whole captures."""
 
-    _PREFIX = "dabhip_stream_"
+    _PREFIX, _destroy = "dabhip_stream_", "dabhip_stream_destroy"
     _RENAMED = {}
 
     def _f(self, name):
@@ -1767,23 +1705,12 @@ class Stream:
             _need(self._f("eti_read")(self._h, stream, _p(out), n) == n, "stream_eti_read")
         return out
 
-    def close(self):
-        if self._h:
-            self._f("destroy")(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class MultiStream(Stream):
     """Sessions over several devices (dabhip_multi_stream_*): nstreams unbounded captures dealt ONCE to the listed devices in contiguous slices (the rule
     of Multi.plan), every slice a complete Stream session on its device; every call is made on all slices at once.  Frames per segment and in total are
     those of one Stream over all captures.  A device may be listed several times (every entry is its own slice)."""
-    _PREFIX = "dabhip_multi_stream_"
+    _PREFIX, _destroy = "dabhip_multi_stream_", "dabhip_multi_stream_destroy"
     _RENAMED = {"status": "status_of", "log": "log_of"}
 
     def __init__(self, nstreams, devices, afc=False, soft=False, subchannels=None, guard=None):

@@ -2,10 +2,9 @@
 // HIP stream over the frames where they lie (device) or after one upload (host); between pushes it keeps the last 4 frames of every stream in
 // one of two carry buffers and the sync state of every (stream, sub-channel) on the device.  The records, corrected bytes and counters stay on
 // the device until asked for.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -13,91 +12,50 @@
 #include "dab_bits.hpp"
 #include "dabplus.hpp"
 #include "kernels.hpp"
-
-namespace dabhip {
-void set_error(const std::string& msg);
-namespace {
-
-bool ok(hipError_t e, const char* what)
-{
-  if (e == hipSuccess) return true;
-  set_error(std::string("dabplus: ") + what + ": " + hipGetErrorString(e));
-  return false;
-}
-
-// device array that only grows
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t cap = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  bool fit(size_t n)
-  {
-    if (n <= cap && p) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (!ok(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)), "hipMalloc")) return false;
-    cap = std::max<size_t>(n, 1);
-    return true;
-  }
-};
-
-}  // namespace
-}  // namespace dabhip
+#include "stage_frame.hpp"
 
 using namespace dabhip;
 
+namespace {
+const char* const kStages[5] = {"locate", "sync", "rs", "au", "carry"};
+}
+
 struct dabhip_dabplus {
-  int device = 0, nstreams = 0, nsub = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[6] = {};
-  DevBuf<int32_t> subch;
-  DevBuf<DabPlusSync> sync;
-  DevBuf<int64_t> counters;
-  DevBuf<uint8_t> carry[2];
+  int nstreams = 0, nsub = 0;
+  DeviceBuffer<int32_t> subch;
+  DeviceBuffer<DabPlusSync> sync;
+  DeviceBuffer<int64_t> counters;
+  DeviceBuffer<uint8_t> carry[2];
   int cur = 0;
   std::vector<int> ncarry;
-  DevBuf<uint8_t> staging;
-  DevBuf<uint8_t> meta;                       // base (int64) | nnew (int) | ncarry (int), per stream
-  DevBuf<DabPlusLoc> loc;
-  DevBuf<DabPlusCand> cand;
-  DevBuf<int> ncand, lane_cw, lane_sf_base, lane_cw_base, totals;
-  DevBuf<DabPlusJob> jobs;
-  DevBuf<uint8_t> data, cw_status, gf;
-  DevBuf<uint32_t> syn;
-  DevBuf<uint16_t> crc_tab;
-  DevBuf<dabhip_dabplus_sf> recs;
+  DeviceBuffer<uint8_t> staging;
+  DeviceBuffer<uint8_t> meta;                       // base (int64) | nnew (int) | ncarry (int), per stream
+  DeviceBuffer<DabPlusLoc> loc;
+  DeviceBuffer<DabPlusCand> cand;
+  DeviceBuffer<int> ncand, lane_cw, lane_sf_base, lane_cw_base, totals;
+  DeviceBuffer<DabPlusJob> jobs;
+  DeviceBuffer<uint8_t> data, cw_status, gf;
+  DeviceBuffer<uint32_t> syn;
+  DeviceBuffer<uint16_t> crc_tab;
+  DeviceBuffer<dabhip_dabplus_sf> recs;
   int64_t nsf = 0, ncw = 0;
-  float ms[5] = {};
   // host copies of the last push's records, fetched on first use
   mutable bool fetched = false;
   mutable std::vector<dabhip_dabplus_sf> h_recs;
   mutable std::vector<int> h_lane_base;
   mutable std::vector<int64_t> h_data_base;   // per superframe, and the total at the end
-
-  ~dabhip_dabplus()
-  {
-    (void)hipSetDevice(device);
-    if (stream) (void)hipStreamSynchronize(stream);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
+  StageFrame<5> f{"dabplus", kStages};
 
   bool fetch() const
   {
     if (fetched) return true;
-    if (!ok(hipSetDevice(device), "hipSetDevice")) return false;
+    if (!f.use_device()) return false;
     const int nlanes = nstreams * nsub;
     h_recs.resize(static_cast<size_t>(nsf));
     h_lane_base.assign(static_cast<size_t>(nlanes) + 1, 0);
     if (nsf > 0) {
-      if (!ok(hipMemcpy(h_recs.data(), recs.p, sizeof(dabhip_dabplus_sf) * static_cast<size_t>(nsf), hipMemcpyDeviceToHost), "records")) return false;
-      if (!ok(hipMemcpy(h_lane_base.data(), lane_sf_base.p, sizeof(int) * (static_cast<size_t>(nlanes) + 1), hipMemcpyDeviceToHost), "records")) return false;
+      if (!f.ok(blocking_copy(h_recs.data(), recs.get(), sizeof(dabhip_dabplus_sf) * static_cast<size_t>(nsf), hipMemcpyDeviceToHost), "records")) return false;
+      if (!f.ok(blocking_copy(h_lane_base.data(), lane_sf_base.get(), sizeof(int) * (static_cast<size_t>(nlanes) + 1), hipMemcpyDeviceToHost), "records")) return false;
     }
     h_data_base.assign(static_cast<size_t>(nsf) + 1, 0);
     for (int64_t i = 0; i < nsf; ++i) h_data_base[i + 1] = h_data_base[i] + static_cast<int64_t>(kRsK) * h_recs[i].s;
@@ -114,15 +72,13 @@ struct dabhip_dabplus {
 
 extern "C" dabhip_dabplus* dabhip_dabplus_create(int device, int nstreams, const int32_t* subch_ids, int nsub)
 {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device: the DAB+ stage runs on the GPU only"); return nullptr; }
-  if (device < 0 || device >= ndev) { set_error("dabplus_create: device index out of range"); return nullptr; }
+  std::unique_ptr<dabhip_dabplus> d(new dabhip_dabplus);
+  StageFrame<5>& f = d->f;
+  if (!f.open(device, "no HIP device: the DAB+ stage runs on the GPU only", "dabplus_create: device index out of range")) return nullptr;
+  const auto ok = [&f](hipError_t e, const char* what) { return f.ok(e, what); };
   if (nstreams <= 0 || nsub <= 0 || nsub > 64 || !subch_ids) { set_error("dabplus_create: bad arguments"); return nullptr; }
   for (int q = 0; q < nsub; ++q)
     if (subch_ids[q] < 0 || subch_ids[q] > 63) { set_error("dabplus_create: SubChId out of range"); return nullptr; }
-  if (!ok(hipSetDevice(device), "hipSetDevice")) return nullptr;
-  auto* d = new dabhip_dabplus;
-  d->device = device;
   d->nstreams = nstreams;
   d->nsub = nsub;
   d->ncarry.assign(static_cast<size_t>(nstreams), 0);
@@ -140,17 +96,14 @@ extern "C" dabhip_dabplus* dabhip_dabplus_create(int device, int nstreams, const
     crc[256 + n] = static_cast<uint16_t>(r);
     for (int b = 0; b < 8; ++b) r = (r & 0x8000u) ? ((r << 1) ^ 0x1021u) & 0xffffu : (r << 1) & 0xffffu;
   }
-  bool good = ok(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking), "hipStreamCreate");
-  for (hipEvent_t& e : d->ev) good = good && ok(hipEventCreate(&e), "hipEventCreate");
-  good = good && d->subch.fit(nsub) && d->sync.fit(nlanes) && d->counters.fit(nlanes * kCntN) && d->gf.fit(gf.size()) && d->crc_tab.fit(crc.size()) &&
-         d->carry[0].fit(static_cast<size_t>(nstreams) * 4 * DABHIP_ETI_BYTES) && d->carry[1].fit(static_cast<size_t>(nstreams) * 4 * DABHIP_ETI_BYTES) &&
-         d->totals.fit(2);
-  good = good && ok(hipMemcpy(d->subch.p, subch_ids, sizeof(int32_t) * nsub, hipMemcpyHostToDevice), "upload") &&
-         ok(hipMemset(d->sync.p, 0, sizeof(DabPlusSync) * nlanes), "clear") && ok(hipMemset(d->counters.p, 0, sizeof(int64_t) * nlanes * kCntN), "clear") &&
-         ok(hipMemcpy(d->gf.p, gf.data(), gf.size(), hipMemcpyHostToDevice), "upload") &&
-         ok(hipMemcpy(d->crc_tab.p, crc.data(), crc.size() * 2, hipMemcpyHostToDevice), "upload");
-  if (!good) { delete d; return nullptr; }
-  return d;
+  bool good = d->subch.reserve(nsub) && d->sync.reserve(nlanes) && d->counters.reserve(nlanes * kCntN) && d->gf.reserve(gf.size()) && d->crc_tab.reserve(crc.size()) &&
+         d->carry[0].reserve(static_cast<size_t>(nstreams) * 4 * DABHIP_ETI_BYTES) && d->carry[1].reserve(static_cast<size_t>(nstreams) * 4 * DABHIP_ETI_BYTES) &&
+         d->totals.reserve(2);
+  good = good && ok(hipMemcpy(d->subch.get(), subch_ids, sizeof(int32_t) * nsub, hipMemcpyHostToDevice), "upload") &&
+         ok(hipMemset(d->sync.get(), 0, sizeof(DabPlusSync) * nlanes), "clear") && ok(hipMemset(d->counters.get(), 0, sizeof(int64_t) * nlanes * kCntN), "clear") &&
+         ok(hipMemcpy(d->gf.get(), gf.data(), gf.size(), hipMemcpyHostToDevice), "upload") &&
+         ok(hipMemcpy(d->crc_tab.get(), crc.data(), crc.size() * 2, hipMemcpyHostToDevice), "upload");
+  return good ? d.release() : nullptr;
 }
 
 extern "C" void dabhip_dabplus_destroy(dabhip_dabplus* d) { delete d; }
@@ -158,7 +111,9 @@ extern "C" void dabhip_dabplus_destroy(dabhip_dabplus* d) { delete d; }
 extern "C" int64_t dabhip_dabplus_push(dabhip_dabplus* d, const uint8_t* frames, const int64_t* counts, int on_device)
 {
   if (!d || !counts) { set_error("dabplus_push: null argument"); return -1; }
-  if (!ok(hipSetDevice(d->device), "hipSetDevice")) return -1;
+  StageFrame<5>& f = d->f;
+  const auto ok = [&f](hipError_t e, const char* what) { return f.ok(e, what); };
+  if (!f.use_device()) return -1;
   const int ns = d->nstreams, nsub = d->nsub;
   std::vector<int64_t> base(static_cast<size_t>(ns));
   int64_t total = 0;
@@ -173,8 +128,8 @@ extern "C" int64_t dabhip_dabplus_push(dabhip_dabplus* d, const uint8_t* frames,
   const uint8_t* src = frames;
   if (total > 0 && !on_device) {
     const size_t bytes = static_cast<size_t>(total) * DABHIP_ETI_BYTES;
-    if (!d->staging.fit(bytes) || !ok(hipMemcpyAsync(d->staging.p, frames, bytes, hipMemcpyHostToDevice, d->stream), "upload")) return -1;
-    src = d->staging.p;
+    if (!d->staging.reserve(bytes) || !ok(hipMemcpyAsync(d->staging.get(), frames, bytes, hipMemcpyHostToDevice, f.stream), "upload")) return -1;
+    src = d->staging.get();
   }
   // per-stream metadata in one upload: base | nnew | ncarry
   std::vector<uint8_t> meta(static_cast<size_t>(ns) * 16);
@@ -186,43 +141,41 @@ extern "C" int64_t dabhip_dabplus_push(dabhip_dabplus* d, const uint8_t* frames,
   }
   const size_t nlanes = static_cast<size_t>(ns) * nsub;
   const int cap = maxv / kSfFrames + 1;
-  if (!d->meta.fit(meta.size()) || !d->loc.fit(static_cast<size_t>(ns) * std::max(maxv, 1) * nsub) || !d->cand.fit(nlanes * cap) ||
-      !d->jobs.fit(nlanes * cap) || !d->ncand.fit(nlanes) || !d->lane_cw.fit(nlanes) || !d->lane_sf_base.fit(nlanes + 1) || !d->lane_cw_base.fit(nlanes))
+  if (!d->meta.reserve(meta.size()) || !d->loc.reserve(static_cast<size_t>(ns) * std::max(maxv, 1) * nsub) || !d->cand.reserve(nlanes * cap) ||
+      !d->jobs.reserve(nlanes * cap) || !d->ncand.reserve(nlanes) || !d->lane_cw.reserve(nlanes) || !d->lane_sf_base.reserve(nlanes + 1) || !d->lane_cw_base.reserve(nlanes))
     return -1;
   // the host copy of meta must outlive the asynchronous copy: hipMemcpy from pageable memory returns once the bytes are staged
-  if (!ok(hipMemcpyAsync(d->meta.p, meta.data(), meta.size(), hipMemcpyHostToDevice, d->stream), "upload") || !ok(hipStreamSynchronize(d->stream), "upload"))
+  if (!ok(hipMemcpyAsync(d->meta.get(), meta.data(), meta.size(), hipMemcpyHostToDevice, f.stream), "upload") || !ok(hipStreamSynchronize(f.stream), "upload"))
     return -1;
   DabPlusFrames fr;
   fr.frames = src;
-  fr.carry = d->carry[d->cur].p;
-  fr.base = reinterpret_cast<const int64_t*>(d->meta.p);
-  fr.nnew = reinterpret_cast<const int*>(d->meta.p + 8 * ns);
-  fr.ncarry = reinterpret_cast<const int*>(d->meta.p + 12 * ns);
+  fr.carry = d->carry[d->cur].get();
+  fr.base = reinterpret_cast<const int64_t*>(d->meta.get());
+  fr.nnew = reinterpret_cast<const int*>(d->meta.get() + 8 * ns);
+  fr.ncarry = reinterpret_cast<const int*>(d->meta.get() + 12 * ns);
   fr.aligned = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
-  hipStream_t st = d->stream;
+  hipStream_t st = f.stream;
   int totals[2] = {0, 0};
-  bool good = ok(hipEventRecord(d->ev[0], st), "event") && ok(launch_dabplus_locate(fr, d->subch.p, nsub, ns, maxv, d->loc.p, st), "locate") &&
-              ok(hipEventRecord(d->ev[1], st), "event") &&
-              ok(launch_dabplus_sync(fr, ns, nsub, maxv, d->loc.p, d->sync.p, d->cand.p, cap, d->ncand.p, d->lane_cw.p, d->counters.p, d->jobs.p,
-                                     d->lane_sf_base.p, d->lane_cw_base.p, d->totals.p, st), "sync") &&
-              ok(hipEventRecord(d->ev[2], st), "event") && ok(hipMemcpyAsync(totals, d->totals.p, sizeof totals, hipMemcpyDeviceToHost, st), "totals") &&
+  bool good = f.mark(0) && ok(launch_dabplus_locate(fr, d->subch.get(), nsub, ns, maxv, d->loc.get(), st), "locate") &&
+              f.mark(1) &&
+              ok(launch_dabplus_sync(fr, ns, nsub, maxv, d->loc.get(), d->sync.get(), d->cand.get(), cap, d->ncand.get(), d->lane_cw.get(), d->counters.get(), d->jobs.get(),
+                                     d->lane_sf_base.get(), d->lane_cw_base.get(), d->totals.get(), st), "sync") &&
+              f.mark(2) && ok(hipMemcpyAsync(totals, d->totals.get(), sizeof totals, hipMemcpyDeviceToHost, st), "totals") &&
               ok(hipStreamSynchronize(st), "sync stage");
   if (!good) return -1;
   d->nsf = totals[0];
   d->ncw = totals[1];
   d->fetched = false;
-  good = d->data.fit(static_cast<size_t>(d->ncw) * kRsK + 16) && d->cw_status.fit(static_cast<size_t>(d->ncw)) && d->recs.fit(static_cast<size_t>(d->nsf)) &&
-         d->syn.fit(static_cast<size_t>(d->ncw) * 4) &&
-         ok(launch_dabplus_rs(d->jobs.p, d->totals.p, static_cast<int>(d->ncw), d->loc.p, maxv, nsub, d->gf.p, d->data.p, d->cw_status.p, d->syn.p, st),
+  good = d->data.reserve(static_cast<size_t>(d->ncw) * kRsK + 16) && d->cw_status.reserve(static_cast<size_t>(d->ncw ? d->ncw : 1)) && d->recs.reserve(static_cast<size_t>(d->nsf ? d->nsf : 1)) &&
+         d->syn.reserve(static_cast<size_t>(d->ncw ? d->ncw * 4 : 1)) &&
+         ok(launch_dabplus_rs(d->jobs.get(), d->totals.get(), static_cast<int>(d->ncw), d->loc.get(), maxv, nsub, d->gf.get(), d->data.get(), d->cw_status.get(), d->syn.get(), st),
             "rs") &&
-         ok(hipEventRecord(d->ev[3], st), "event") &&
-         ok(launch_dabplus_au(d->jobs.p, static_cast<int>(d->nsf), d->loc.p, maxv, nsub, d->data.p, d->cw_status.p, d->crc_tab.p, d->recs.p, d->counters.p, st),
+         f.mark(3) &&
+         ok(launch_dabplus_au(d->jobs.get(), static_cast<int>(d->nsf), d->loc.get(), maxv, nsub, d->data.get(), d->cw_status.get(), d->crc_tab.get(), d->recs.get(), d->counters.get(), st),
             "au") &&
-         ok(hipEventRecord(d->ev[4], st), "event") && ok(launch_dabplus_carry(fr, ns, d->carry[d->cur ^ 1].p, st), "carry") &&
-         ok(hipEventRecord(d->ev[5], st), "event") && ok(hipStreamSynchronize(st), "push");
+         f.mark(4) && ok(launch_dabplus_carry(fr, ns, d->carry[d->cur ^ 1].get(), st), "carry") &&
+         f.mark(5) && f.finish();
   if (!good) return -1;
-  for (int k = 0; k < 5; ++k)
-    if (!ok(hipEventElapsedTime(&d->ms[k], d->ev[k], d->ev[k + 1]), "hipEventElapsedTime")) return -1;
   d->cur ^= 1;
   for (int s = 0; s < ns; ++s) d->ncarry[s] = std::min(4, d->ncarry[s] + static_cast<int>(counts[s]));
   return d->nsf;
@@ -247,7 +200,7 @@ bool lane_data(const dabhip_dabplus* d, int stream, int sub, std::vector<uint8_t
   *nsf = d->h_lane_base[l + 1] - *first_sf;
   const int64_t a = d->h_data_base[*first_sf], b = d->h_data_base[*first_sf + *nsf];
   out.resize(static_cast<size_t>(b - a));
-  return b == a || ok(hipMemcpy(out.data(), d->data.p + a, static_cast<size_t>(b - a), hipMemcpyDeviceToHost), "data");
+  return b == a || d->f.ok(blocking_copy(out.data(), d->data.get() + a, static_cast<size_t>(b - a), hipMemcpyDeviceToHost), "data");
 }
 }  // namespace
 
@@ -284,21 +237,16 @@ extern "C" int dabhip_dabplus_stats(const dabhip_dabplus* d, int stream, int sub
 {
   if (!d || !counters7) { set_error("dabplus_stats: null argument"); return -1; }
   if (!d->lane_ok(stream, sub)) return -1;
-  if (!ok(hipSetDevice(d->device), "hipSetDevice")) return -1;
+  if (!d->f.use_device()) return -1;
   int64_t c[kCntN];
-  if (!ok(hipMemcpy(c, d->counters.p + (static_cast<size_t>(stream) * d->nsub + sub) * kCntN, sizeof c, hipMemcpyDeviceToHost), "counters")) return -1;
+  if (!d->f.ok(blocking_copy(c, d->counters.get() + (static_cast<size_t>(stream) * d->nsub + sub) * kCntN, sizeof c, hipMemcpyDeviceToHost), "counters")) return -1;
   std::memcpy(counters7, c, 7 * sizeof(int64_t));
   return 0;
 }
 
 extern "C" int dabhip_dabplus_stage_ms(const dabhip_dabplus* d, const char** names, float* ms, int cap)
 {
-  static const char* kNames[5] = {"locate", "sync", "rs", "au", "carry"};
   if (!d) return -1;
-  const int n = std::min(cap, 5);
-  for (int k = 0; k < n; ++k) {
-    if (names) names[k] = kNames[k];
-    if (ms) ms[k] = d->ms[k];
-  }
+  d->f.stage_ms(names, ms, cap);
   return 5;
 }

@@ -160,7 +160,7 @@ bool Engine::read_eti(int64_t first, int64_t n, uint8_t* dst)
 {
   if (n <= 0) return true;
   if (!check(hipSetDevice(device_), "hipSetDevice")) return false;   // callers may sit on another device's thread (dabhip_multi)
-  // on the download stream and ended by a stream synchronise (engine.hpp: blocking_copy): callers read after every decode or segment, for ever
+  // on the download stream and ended by a stream synchronise (hip_util.hpp: blocking_copy): callers read after every decode or segment, for ever
   return check(hipMemcpyAsync(dst, d_eti_.get() + first * kEtiBytes, static_cast<size_t>(n) * kEtiBytes, hipMemcpyDeviceToHost, d2h_stream_), "eti download") &&
          check(hipStreamSynchronize(d2h_stream_), "eti download");
 }

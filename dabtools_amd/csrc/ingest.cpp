@@ -2,21 +2,25 @@
 // plan (ingest_plan.hpp), the uploads, the energy reduction of the streams whose gain window closes, and one launch of k_ingest.hip's kernel
 // for all streams.  The tuned mode (dabhip_ingest_create_tuned) has nchannels output streams per input stream: one descriptor per output stream,
 // the channels of a stream sharing its plan, carry and input, and the keep kernel's descriptors (one per input stream) behind them.  Every push
-// ends in a stream synchronise (engine.hpp: what the runtime keeps of a stream that nobody synchronises).
+// ends in a stream synchronise (hip_util.hpp: what the runtime keeps of a stream that nobody synchronises).
 #include <cstring>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "capi_detail.hpp"
-#include "engine.hpp"
 #include "ingest.hpp"
 #include "ingest_plan.hpp"
+#include "stage_frame.hpp"
 
 using namespace dabhip;
 
+namespace {
+const char* const kStages[4] = {"upload", "energy", "resample", "keep"};
+}
+
 struct dabhip_ingest {
-  int device = 0, nstreams = 0, format = 0, sample_bytes = 0;
+  int nstreams = 0, format = 0, sample_bytes = 0;
   int nchannels = 1, nouts = 0;                  // output streams: nstreams * nchannels, stream-major
   bool tuned = false;
   std::vector<uint32_t> step;                    // tuned: the NCO step per channel
@@ -31,28 +35,10 @@ struct dabhip_ingest {
   size_t carry_stride = 0;
   int cur = 0;                                   // carry[cur] holds what the last push kept
   std::vector<size_t> out_off, out_bytes;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[5] = {};
-  float ms[4] = {0, 0, 0, 0};
-  ~dabhip_ingest()
-  {
-    (void)hipSetDevice(device);
-    if (stream) (void)hipStreamSynchronize(stream);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
+  StageFrame<4> f{"ingest", kStages};
 };
 
 namespace {
-bool ok(hipError_t e, const char* what)
-{
-  if (e == hipSuccess) return true;
-  set_error(std::string("ingest: ") + what + ": " + hipGetErrorString(e));
-  return false;
-}
-size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // the push proper: nsamples[b] samples of stream b at src[b] (device memory, aligned to a sample).  Returns the output bytes, < 0 on error.
 int64_t push_device(dabhip_ingest* d, const std::vector<const void*>& src, const std::vector<int64_t>& nsamples, bool uploaded)
 {
@@ -97,10 +83,12 @@ int64_t push_device(dabhip_ingest* d, const std::vector<const void*>& src, const
   }
   for (int b = 0; b < ns && d->tuned; ++b) h[static_cast<size_t>(no + b)] = h[static_cast<size_t>(b * nc)];
   const IngestDesc* keep_descs = d->descs.get() + (d->tuned ? no : 0);
-  hipStream_t st = d->stream;
+  StageFrame<4>& f = d->f;
+  const auto ok = [&f](hipError_t e, const char* what) { return f.ok(e, what); };
+  hipStream_t st = f.stream;
   std::vector<uint32_t> gain = d->gain;
-  if (!uploaded && !ok(hipEventRecord(d->ev[0], st), "event")) return -1;
-  if (!ok(hipEventRecord(d->ev[1], st), "event")) return -1;
+  if (!uploaded && !f.mark(0)) return -1;
+  if (!f.mark(1)) return -1;
   if (closing) {
     std::vector<unsigned long long> e(static_cast<size_t>(no), 0);
     if (!ok(hipMemcpyAsync(d->descs.get(), h.data(), h.size() * sizeof(IngestDesc), hipMemcpyHostToDevice, st), "descriptors")) return -1;
@@ -115,15 +103,12 @@ int64_t push_device(dabhip_ingest* d, const std::vector<const void*>& src, const
     for (int o = 0; o < no; ++o)
       if (plan[static_cast<size_t>(o / nc)].closes) h[static_cast<size_t>(o)].gain = gain[static_cast<size_t>(o)] = ingest_auto_gain(e[static_cast<size_t>(o)]);
   }
-  if (!ok(hipEventRecord(d->ev[2], st), "event") || !ok(hipMemcpyAsync(d->descs.get(), h.data(), h.size() * sizeof(IngestDesc), hipMemcpyHostToDevice, st), "descriptors") ||
+  if (!f.mark(2) || !ok(hipMemcpyAsync(d->descs.get(), h.data(), h.size() * sizeof(IngestDesc), hipMemcpyHostToDevice, st), "descriptors") ||
       !ok(d->tuned ? launch_ingest_tune(d->format, d->descs.get(), no, static_cast<int>(max_nout), d->table.get(), d->nco.get(), nullptr, d->ratio.L, d->ratio.M, d->ratio.T, st)
                    : launch_ingest_resample(d->format, d->descs.get(), ns, static_cast<int>(max_nout), d->table.get(), d->ratio.L, d->ratio.M, d->ratio.T, st),
           "resample launch") ||
-      !ok(hipEventRecord(d->ev[3], st), "event") || !ok(launch_ingest_keep(d->format, keep_descs, ns, max_keep, st), "keep launch") ||
-      !ok(hipEventRecord(d->ev[4], st), "event") || !ok(hipStreamSynchronize(st), "push"))
+      !f.mark(3) || !ok(launch_ingest_keep(d->format, keep_descs, ns, max_keep, st), "keep launch") || !f.mark(4) || !f.finish())
     return -1;
-  for (int k = 0; k < 4; ++k)
-    if (!ok(hipEventElapsedTime(&d->ms[k], d->ev[k], d->ev[k + 1]), "hipEventElapsedTime")) return -1;
   d->st = next;
   d->gain = gain;
   d->cur ^= 1;
@@ -148,12 +133,9 @@ std::vector<uint32_t> table_words(const IngestRatio& r, const std::vector<int16_
 // the object behind both creators, once everything that can be refused has been: step empty = the plain mode, one channel
 dabhip_ingest* make(const char* who, int device, int nstreams, int format, const IngestRatio& r, uint32_t gain, const std::vector<uint32_t>& words, const std::vector<uint32_t>& step)
 {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); set_error(std::string(who) + ": no HIP device"); return nullptr; }
-  if (!ok(hipSetDevice(device), "hipSetDevice")) return nullptr;
   dabhip_ingest* d = new (std::nothrow) dabhip_ingest;
   if (!d) return nullptr;
-  d->device = device;
+  StageFrame<4>& f = d->f;
   d->nstreams = nstreams;
   d->tuned = !step.empty();
   d->nchannels = d->tuned ? static_cast<int>(step.size()) : 1;
@@ -171,17 +153,12 @@ dabhip_ingest* make(const char* who, int device, int nstreams, int format, const
   // while the window is open everything is carried: fewer than W samples, tuned fewer than complete output W - 1
   const int64_t held = d->tuned ? ingest_samples_for_outputs(r, kIngestGainWindow) : kIngestGainWindow;
   d->carry_stride = round_up(static_cast<size_t>(d->auto_gain ? held : std::max(r.T, 1)) * d->sample_bytes, 16);
-  bool good = ok(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking), "hipStreamCreate");
-  for (hipEvent_t& e : d->ev) good = good && ok(hipEventCreate(&e), "hipEventCreate");
-  good = good && d->table.reserve(words.size()) && d->carry[0].reserve(d->carry_stride * nstreams) && d->carry[1].reserve(d->carry_stride * nstreams) &&
-         ok(hipMemcpyAsync(d->table.get(), words.data(), words.size() * 4, hipMemcpyHostToDevice, d->stream), "table upload");
-  std::vector<uint32_t> nco;
-  if (good && d->tuned) {
-    const std::vector<int16_t> cs = ingest_tune_nco();
-    for (int i = 0; i < kTuneNcoSize; ++i) nco.push_back(static_cast<uint16_t>(cs[static_cast<size_t>(2 * i)]) | static_cast<uint32_t>(static_cast<uint16_t>(cs[static_cast<size_t>(2 * i + 1)])) << 16);
-    good = d->nco.reserve(nco.size()) && ok(hipMemcpyAsync(d->nco.get(), nco.data(), nco.size() * 4, hipMemcpyHostToDevice, d->stream), "NCO table upload");
-  }
-  good = good && ok(hipStreamSynchronize(d->stream), "table upload");
+  bool good = f.open(device, std::string(who) + ": no HIP device") && d->table.reserve(words.size()) && d->carry[0].reserve(d->carry_stride * nstreams) &&
+              d->carry[1].reserve(d->carry_stride * nstreams) &&
+              f.ok(hipMemcpyAsync(d->table.get(), words.data(), words.size() * 4, hipMemcpyHostToDevice, f.stream), "table upload");
+  const std::vector<uint32_t> nco = d->tuned ? ingest_tune_nco_words() : std::vector<uint32_t>();
+  if (good && d->tuned) good = d->nco.reserve(nco.size()) && f.ok(hipMemcpyAsync(d->nco.get(), nco.data(), nco.size() * 4, hipMemcpyHostToDevice, f.stream), "NCO table upload");
+  good = good && f.ok(hipStreamSynchronize(f.stream), "table upload");
   if (!good) { delete d; return nullptr; }
   return d;
 }
@@ -227,31 +204,11 @@ extern "C" void dabhip_ingest_destroy(dabhip_ingest* d) { delete d; }
 extern "C" int64_t dabhip_ingest_push(dabhip_ingest* d, const void* const* src, const size_t* nbytes, int on_device)
 {
   if (!d || !src || !nbytes) { set_error("ingest_push: null argument"); return -1; }
-  const int ns = d->nstreams;
-  const size_t sb = static_cast<size_t>(d->sample_bytes);
-  std::vector<const void*> dev(static_cast<size_t>(ns), nullptr);
-  std::vector<int64_t> nsamples(static_cast<size_t>(ns), 0);
-  size_t stage_total = 0;
-  for (int b = 0; b < ns; ++b) {
-    if (nbytes[b] % sb) { set_error("ingest_push: stream " + std::to_string(b) + ": " + std::to_string(nbytes[b]) + " bytes are no whole number of " + std::to_string(sb) + "-byte samples"); return -1; }
-    if (nbytes[b] && !src[b]) { set_error("ingest_push: null input"); return -1; }
-    if (on_device && nbytes[b] && reinterpret_cast<uintptr_t>(src[b]) % sb) { set_error("ingest_push: a device input must be aligned to its sample size"); return -1; }
-    nsamples[static_cast<size_t>(b)] = static_cast<int64_t>(nbytes[b] / sb);
-    stage_total += round_up(nbytes[b], 16);
-  }
-  if (!ok(hipSetDevice(d->device), "hipSetDevice")) return -1;
-  if (on_device) {
-    for (int b = 0; b < ns; ++b) dev[static_cast<size_t>(b)] = src[b];
-    return push_device(d, dev, nsamples, false);
-  }
-  if (!d->stage.reserve(stage_total ? stage_total : 1) || !ok(hipEventRecord(d->ev[0], d->stream), "event")) return -1;
-  size_t at = 0;
-  for (int b = 0; b < ns; ++b) {
-    dev[static_cast<size_t>(b)] = d->stage.get() + at;
-    if (nbytes[b] && !ok(hipMemcpyAsync(d->stage.get() + at, src[b], nbytes[b], hipMemcpyHostToDevice, d->stream), "upload")) return -1;
-    at += round_up(nbytes[b], 16);
-  }
-  return push_device(d, dev, nsamples, true);
+  const SamplePush p = plan_sample_push("ingest_push", static_cast<size_t>(d->sample_bytes), src, nbytes, on_device != 0, d->nstreams, [](int, int64_t n) { return n; });
+  if (!p.refusal.empty()) { set_error(p.refusal); return -1; }
+  std::vector<const void*> dev(src, src + d->nstreams);
+  if (!d->f.use_device() || (!on_device && !d->f.upload(d->stage, p, src, dev))) return -1;
+  return push_device(d, dev, p.nsamples, !on_device);
 }
 
 extern "C" int dabhip_ingest_skip(dabhip_ingest* d, int64_t n)
@@ -283,8 +240,8 @@ extern "C" int64_t dabhip_ingest_read(const dabhip_ingest* d, int stream, uint8_
   if (!d || stream < 0 || stream >= d->nouts || (!dst && cap)) { set_error("ingest_read: bad argument"); return -1; }
   const size_t n = d->out_bytes[static_cast<size_t>(stream)];
   if (n > cap) { set_error("ingest_read: buffer too small"); return -1; }
-  if (!ok(hipSetDevice(d->device), "hipSetDevice")) return -1;
-  if (n && !ok(blocking_copy(dst, d->out.get() + d->out_off[static_cast<size_t>(stream)], n, hipMemcpyDeviceToHost), "read")) return -1;
+  if (!d->f.use_device()) return -1;
+  if (n && !d->f.ok(blocking_copy(dst, d->out.get() + d->out_off[static_cast<size_t>(stream)], n, hipMemcpyDeviceToHost), "read")) return -1;
   return static_cast<int64_t>(n);
 }
 
@@ -295,8 +252,6 @@ extern "C" uint32_t dabhip_ingest_gain(const dabhip_ingest* d, int stream)
 
 extern "C" int dabhip_ingest_stage_ms(const dabhip_ingest* d, const char** names, float* ms, int cap)
 {
-  static const char* const kNames[4] = {"upload", "energy", "resample", "keep"};
   if (!d || !names || !ms) { set_error("ingest_stage_ms: null argument"); return -1; }
-  for (int k = 0; k < 4 && k < cap; ++k) { names[k] = kNames[k]; ms[k] = d->ms[k]; }
-  return std::min(cap, 4);
+  return d->f.stage_ms(names, ms, cap);
 }

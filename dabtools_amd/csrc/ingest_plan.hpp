@@ -212,6 +212,14 @@ inline std::vector<int16_t> ingest_tune_nco()
   }
   return cs;
 }
+// the table as the kernels hold it (k_ingest.hip, k_scan.hip, k_tii.hip): one word per entry, cos in the low half and sin in the high half
+inline std::vector<uint32_t> ingest_tune_nco_words()
+{
+  const std::vector<int16_t> cs = ingest_tune_nco();
+  std::vector<uint32_t> words(static_cast<size_t>(kTuneNcoSize));
+  for (size_t i = 0; i < words.size(); ++i) words[i] = static_cast<uint16_t>(cs[2 * i]) | static_cast<uint32_t>(static_cast<uint16_t>(cs[2 * i + 1])) << 16;
+  return words;
+}
 // may a block centred f Hz from the capture's centre be tuned to?  ("" = yes)
 inline std::string ingest_tune_offset(int64_t rate_hz, int64_t f)
 {

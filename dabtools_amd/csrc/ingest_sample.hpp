@@ -1,8 +1,10 @@
 // ingest_sample.hpp — step 1 of the ingest stage (include/dabhip.h): a sample of one of the four formats to the 16-bit domain.  Shared by the kernels
-// that read captures where the caller left them: k_ingest.hip and k_scan.hip.  Device code.
+// that read captures where the caller left them, k_ingest.hip and k_scan.hip, with the launch wrappers' dispatch on the format.  Device code, but for that.
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 namespace dabhip {
 namespace {
@@ -29,6 +31,20 @@ __device__ __forceinline__ int2 convert(typename Sample<F>::type s)
   else return int2{static_cast<int>(s.x), static_cast<int>(s.y)};
 }
 template <int F> constexpr int post_shift() { return F <= 1 ? 8 : 0; }
+
+// fn(std::integral_constant<int, format>()) launches; returns what the launch left
+template <class Fn>
+hipError_t by_format(int format, Fn fn)
+{
+  switch (format) {
+    case 0: fn(std::integral_constant<int, 0>()); break;
+    case 1: fn(std::integral_constant<int, 1>()); break;
+    case 2: fn(std::integral_constant<int, 2>()); break;
+    case 3: fn(std::integral_constant<int, 3>()); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
 
 }  // namespace
 }  // namespace dabhip

@@ -20,8 +20,6 @@
 // ingest_tune_bypass_kernel: Fin = 2,048,000: the mixer only, the NCO entry read through the cache (one lookup per output and no tile to share it).
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
 #include "ingest.hpp"
 #include "ingest_plan.hpp"
 #include "ingest_sample.hpp"
@@ -258,19 +256,6 @@ __global__ __launch_bounds__(kThreads) void ingest_tune_bypass_kernel(const Inge
     const unsigned pair = requantise(v.x, d.gain) | requantise(v.y, d.gain) << 8;
     reinterpret_cast<unsigned short*>(d.out)[o] = static_cast<unsigned short>(pair);
   }
-}
-
-template <class Fn>
-hipError_t by_format(int format, Fn fn)
-{
-  switch (format) {
-    case 0: fn(std::integral_constant<int, 0>()); break;
-    case 1: fn(std::integral_constant<int, 1>()); break;
-    case 2: fn(std::integral_constant<int, 2>()); break;
-    case 3: fn(std::integral_constant<int, 3>()); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
 }
 
 }  // namespace

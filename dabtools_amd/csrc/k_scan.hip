@@ -16,8 +16,6 @@
 // scan_keep_kernel: the unfinished segment's samples into the other carry buffer.
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
 #include "fixed_butterfly.hpp"
 #include "ingest_sample.hpp"
 #include "scan.hpp"
@@ -119,19 +117,6 @@ __global__ __launch_bounds__(kThreads) void scan_keep_kernel(const ScanDesc* __r
   const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x, n = d.keep_from + i;
   if (n >= d.end) return;
   static_cast<S*>(d.keep)[i] = n < d.new_from ? static_cast<const S*>(d.carry)[n - d.carry_from] : static_cast<const S*>(d.src)[n - d.new_from];
-}
-
-template <class Fn>
-hipError_t by_format(int format, Fn fn)
-{
-  switch (format) {
-    case 0: fn(std::integral_constant<int, 0>()); break;
-    case 1: fn(std::integral_constant<int, 1>()); break;
-    case 2: fn(std::integral_constant<int, 2>()); break;
-    case 3: fn(std::integral_constant<int, 3>()); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
 }
 
 }  // namespace

@@ -59,6 +59,12 @@ inline ScanPush scan_plan_push(int nsegments, ScanStreamState& s, int64_t nsampl
   s.kept_from = p.keep_from;
   return p;
 }
+// of a push of nsamples, the samples the host path uploads: only what the window can still use -- the unfinished segment and the segments missing
+inline int64_t scan_upload_samples(int nsegments, const ScanStreamState& s, int64_t nsamples)
+{
+  const int64_t wanted = s.done == nsegments ? 0 : static_cast<int64_t>(nsegments) * kScanSize - s.pushed;
+  return std::min<int64_t>(nsamples, std::max<int64_t>(wanted, 0));
+}
 
 // ---- from spectrum to blocks -------------------------------------------------------------------------------------------------------------------
 // the 38 Band III block centres in Hz, ascending, and their names

@@ -296,7 +296,7 @@ int64_t dabhip_stream_feed(dabhip_stream* s, const uint8_t* const* iq, const siz
   s->gather_launches = s->gather_calls = 0;
   const int64_t frames = s->eng.feed(virt.data(), avail.data(), s->n, s->first);
   if (frames < 0) return broken(nullptr);        // (the engine's error text stands)
-  // the prefetch stream is only ever waited for through events (engine.hpp: blocking_copy): every 32nd segment, wait for the stream itself -- at
+  // the prefetch stream is only ever waited for through events (hip_util.hpp: blocking_copy): every 32nd segment, wait for the stream itself -- at
   // most the upload of the next segment, which the next feed needs anyway
   if (s->queued_ever && ++s->up_uses % kReapEvery == 0 && reap_enabled()) (void)hipStreamSynchronize(s->up_stream);
   s->first = false;

@@ -16,9 +16,7 @@ bool Engine::tii_tables()
   if (d_tii_nco_.get()) return true;
   for (Event& e : ev_tii_)
     if (!e && !check(e.create(), "hipEventCreate")) return false;
-  const std::vector<int16_t> cs = ingest_tune_nco();
-  std::vector<uint32_t> nco;
-  for (int i = 0; i < kTuneNcoSize; ++i) nco.push_back(static_cast<uint16_t>(cs[static_cast<size_t>(2 * i)]) | static_cast<uint32_t>(static_cast<uint16_t>(cs[static_cast<size_t>(2 * i + 1)])) << 16);
+  const std::vector<uint32_t> nco = ingest_tune_nco_words();
   if (!d_tii_nco_.reserve(nco.size())) return false;
   if (!check(blocking_copy(d_tii_nco_.get(), nco.data(), nco.size() * 4, hipMemcpyHostToDevice), "NCO table upload")) { d_tii_nco_.release(); return false; }
   return true;

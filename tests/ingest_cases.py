@@ -83,3 +83,21 @@ def random_raw(rng, fmt, n):
 def samples_for_outputs(L, M, T, k):
     """The fewest input samples of a stream that complete k outputs (k >= 1): output k - 1 needs sample floor((k - 1) M / L) + T/2."""
     return (k - 1) * M // L + T // 2 + 1
+
+
+def check_stage_ms(handle, entry, want):
+    """The contract of dabhip_ingest_stage_ms and dabhip_scan_stage_ms, on the C entry itself: the names in order, min(cap, count) returned and no
+    more than that written, null arrays and a null handle refused.  After a push every time is finite and >= 0."""
+    import ctypes as C
+    fn, n = getattr(dab.lib(), entry), len(want)
+    for cap in (0, 1, n - 1, n, n + 3):
+        names, ms = (C.c_char_p * (n + 3))(), (C.c_float * (n + 3))(*([-7.0] * (n + 3)))
+        got = fn(handle._h, names, ms, cap)
+        assert got == min(cap, n), (entry, cap, got)
+        assert [names[k].decode() for k in range(got)] == list(want)[:got]
+        assert all(np.isfinite(ms[k]) and ms[k] >= 0 for k in range(got)), (entry, list(ms))
+        assert all(names[k] is None and ms[k] == -7.0 for k in range(got, n + 3)), (entry, cap)
+    names, ms = (C.c_char_p * n)(), (C.c_float * n)()
+    for args in ((handle._h, None, ms, n), (handle._h, names, None, n), (None, names, ms, n)):
+        assert fn(*args) == -1 and (entry[len("dabhip_"):] + ": null argument") in dab.last_error()
+    assert list(handle.stage_ms()) == list(want)

@@ -117,6 +117,38 @@ def test_rs_stage_equals_the_model_under_random_errors():
     assert set(st) == {"locate", "sync", "rs", "au", "carry"} and all(v >= 0 for v in st.values())
 
 
+def test_empty_pushes_and_the_stage_ms_entry():
+    """A push without a frame on a fresh object and one that completes no superframe return 0 and leave every query answering (buffers of zero
+    records, code words and syndromes); the frames that follow decode as if nothing had happened.  Then dabhip_dabplus_stage_ms's contract: 5
+    whatever cap is, min(cap, 5) entries written, null arrays tolerated, a null handle refused."""
+    import ctypes as C
+    rng = np.random.default_rng(16)
+    frames = [_frames(40, [(5, _protected_superframes(rng, 4, 4))]), _frames(90, [(5, _protected_superframes(rng, 4, 4))])[1:]]
+    dp = dab.DabPlus(2, [5])
+    for parts in ([[], []], [frames[0][:3], []]):
+        assert dp.push([np.array(p, dtype=np.uint8).reshape(-1, m.ETI_BYTES) for p in parts]) == 0
+        for b in range(2):
+            assert dp.superframes(b, 0).size == 0 and dp.data(b, 0).size == 0 and dp.aus(b, 0) == [] and not dp.stats(b, 0).any()
+    assert dp.push([np.array(frames[0][3:], dtype=np.uint8), np.array(frames[1], dtype=np.uint8)]) > 0
+    for b in range(2):
+        sm = m.SyncModel(5)
+        want = m.stage(sm, frames[b])
+        assert len(want) > 0
+        _assert_lane_equal(*_gpu_lane(dp, b, 0), want, b)
+        assert list(dp.stats(b, 0)) == _model_stats(want, sm.losses)
+    fn, want = dab.lib().dabhip_dabplus_stage_ms, ["locate", "sync", "rs", "au", "carry"]
+    for cap in (0, 1, 4, 5, 8):
+        names, ms = (C.c_char_p * 8)(), (C.c_float * 8)(*([-7.0] * 8))
+        assert fn(dp._h, names, ms, cap) == 5
+        k = min(cap, 5)
+        assert [n.decode() for n in names[:k]] == want[:k] and all(np.isfinite(v) and v >= 0 for v in ms[:k])
+        assert all(n is None for n in names[k:]) and all(v == -7.0 for v in ms[k:])
+    names, ms = (C.c_char_p * 5)(), (C.c_float * 5)()
+    assert fn(dp._h, None, ms, 5) == 5 and fn(dp._h, names, None, 5) == 5 and fn(dp._h, None, None, 5) == 5 and fn(None, names, ms, 5) == -1
+    assert list(dp.stage_ms()) == want
+    dp.close()
+
+
 def test_sync_rule_and_any_chunking_of_the_pushes():
     seed = fresh_seed("test_sync_rule_and_any_chunking_of_the_pushes")
     rng = np.random.default_rng(seed)

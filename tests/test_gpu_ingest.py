@@ -113,6 +113,33 @@ def test_chunking_does_not_change_the_bytes(fmt, rate):
 
 
 @pytest.mark.gpu
+def test_mixed_host_push_equals_one_device_push():
+    """One host push of three streams of 0, 1 and 4097 samples (staging offsets 0, 0 and 16: the one sample's 4 bytes are rounded up) and a second one
+    that completes them, against the same samples pushed from device memory in one piece.  Then the stage_ms entry's contract."""
+    rng = np.random.default_rng(16)
+    first = (0, 1, 4097)
+    raws = [cases.random_raw(rng, "cs16", n + 3000 + 11 * b) for b, n in enumerate(first)]
+    dev = [dab.DeviceBuffer(r.nbytes) for r in raws]
+    for d, r in zip(dev, raws):
+        d.upload(r.view(np.uint8))
+    one = dab.Ingest(0, 3, "cs16", 2400000, 300)
+    one.push_ptrs([d.ptr for d in dev], [r.nbytes for r in raws], on_device=True)
+    want = [one.read(b) for b in range(3)]
+    assert all(w.size > 2 * 2000 for w in want)
+    one.close()
+    ing = dab.Ingest(0, 3, "cs16", 2400000, 300)
+    ing.push([r[:2 * n] for r, n in zip(raws, first)])
+    got = [ing.read(b) for b in range(3)]
+    ing.push([r[2 * n:] for r, n in zip(raws, first)])
+    for b in range(3):
+        assert np.array_equal(np.concatenate([got[b], ing.read(b)]), want[b]), b
+    cases.check_stage_ms(ing, "dabhip_ingest_stage_ms", ("upload", "energy", "resample", "keep"))
+    ing.close()
+    for d in dev:
+        d.free()
+
+
+@pytest.mark.gpu
 def test_push_refuses_part_of_a_sample():
     ing = dab.Ingest(0, 1, "cs16", 2400000, 256)
     with pytest.raises(dab.DabhipError, match="whole number"):

@@ -128,6 +128,33 @@ def test_chunking_does_not_change_the_spectrum(fmt, on_device):
 
 
 @pytest.mark.gpu
+def test_mixed_host_push_equals_one_device_push():
+    """One host push of three streams of 0, 1 and 4097 samples and a second one that runs past the window of 2 segments (the host path uploads only
+    what the window still lacks), against the same samples pushed from device memory in one piece.  Then the stage_ms entry's contract."""
+    rng = np.random.default_rng(16)
+    first = (0, 1, 4097)
+    raws = [cases.random_raw(rng, "cs16", 2 * S + 500 + 11 * b) for b in range(3)]
+    dev = [dab.DeviceBuffer(r.nbytes) for r in raws]
+    for d, r in zip(dev, raws):
+        d.upload(r.view(np.uint8))
+    one = dab.Scan(0, 3, "cs16", 4096000, 2)
+    assert one.push_ptrs([d.ptr for d in dev], [r.nbytes for r in raws], on_device=True) == 6
+    want = [one.spectrum(b) for b in range(3)]
+    one.close()
+    scan = dab.Scan(0, 3, "cs16", 4096000, 2)
+    assert scan.push([r[:2 * n] for r, n in zip(raws, first)]) == 1
+    assert scan.push([r[2 * n:] for r, n in zip(raws, first)]) == 5
+    assert scan.push(raws) == 0                                   # the window is done: nothing is uploaded
+    for b in range(3):
+        P, done = scan.spectrum(b)
+        assert done == want[b][1] == 2 and P.any() and np.array_equal(P, want[b][0]), b
+    cases.check_stage_ms(scan, "dabhip_scan_stage_ms", ("upload", "transform", "keep"))
+    scan.close()
+    for d in dev:
+        d.free()
+
+
+@pytest.mark.gpu
 def test_refusals_of_push():
     scan = dab.Scan(0, 1, "cs16", 4096000)
     with pytest.raises(dab.DabhipError, match="no whole number"):

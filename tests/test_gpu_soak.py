@@ -1,6 +1,6 @@
 """Things left running: a session, the CLI under a pipe and the reference's per-buffer seams over thousands of calls -- frames keep coming out right and
 the process does not grow.  Round 6 found 2 .. 3.6 KB of heap per segment here: the HIP runtime keeps its records of finished copies until somebody
-synchronises their STREAM (tools/hip_retained_commands.py); engine.hpp (blocking_copy, kReapEvery) is what these tests hold in place.  Short forms of
+synchronises their STREAM (tools/hip_retained_commands.py); hip_util.hpp (blocking_copy, kReapEvery) is what these tests hold in place.  Short forms of
 tools/soak.py, tools/soak_cli.py, tools/soak_seams.py (the long ones: tools/gpu/soak.sh, profiles/r06_soak_*.json)."""
 import json
 import os

@@ -235,15 +235,25 @@ def test_model_against_the_librarys_bookkeeping(nsegments):
     assert short.push(np.full(2 * (S - 1), 200, np.uint8)) == 0 and not short.P.any()
 
 
-def test_host_rule_under_sanitizers():
+def run_unit(name):
     here = os.path.join(ROOT, "tests", "host_sanitize")
     os.makedirs(os.path.join(here, "build"), exist_ok=True)
-    exe = os.path.join(here, "build", "scan_units_asan")
+    exe = os.path.join(here, "build", name + "_units_asan")
     build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                            os.path.join(here, "scan_units.cpp"), "-o", exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+                            os.path.join(here, name + "_units.cpp"), "-o", exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert build.returncode == 0, build.stdout[-3000:]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1 abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=300)
     assert run.returncode == 0, (run.stdout + run.stderr)[-4000:]
     assert "Sanitizer" not in run.stderr, run.stderr[-4000:]
-    assert run.stdout.split() == ["ok", "scan-units"]
+    assert run.stdout.split() == ["ok", name + "-units"]
+
+
+def test_host_rule_under_sanitizers():
+    run_unit("scan")
+
+
+def test_push_front_under_sanitizers():
+    """tests/host_sanitize/push_units.cpp: the front of the ingest's and the scan's push (csrc/sample_push.hpp), the scan's upload clamp and the
+    packed mixer table."""
+    run_unit("push")

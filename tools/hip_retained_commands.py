@@ -5,7 +5,7 @@ Heap in use of this process (glibc mallinfo2) before and after N repetitions of 
 ROCm 7.2 / MI355X (profiles/r06_hip_retained_commands.txt): a blocking hipMemcpy into PAGEABLE host memory keeps 970 bytes per call, an asynchronous copy
 + hipEventRecord + hipEventSynchronize on a stream of its own 2.0 KB per round -- for as long as nobody synchronises THAT STREAM (hipStreamQuery does
 not count, nor does a hipDeviceSynchronize afterwards for the null stream's copies); with a hipStreamSynchronize every 32 rounds, or one per copy, nothing
-grows.  What libdabhip does about it: engine.hpp (blocking_copy, kReapEvery).  Usage: hip_retained_commands.py [N=20000]"""
+grows.  What libdabhip does about it: hip_util.hpp (blocking_copy, kReapEvery).  Usage: hip_retained_commands.py [N=20000]"""
 import ctypes as C, json, sys
 class MI(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in ("arena", "ordblks", "smblks", "hblks", "hblkhd", "usmblks", "fsmblks", "uordblks", "fordblks", "keepcost")]

@@ -16,7 +16,7 @@ long (default 11,200 = 4.4 GB: byte offsets past 2^32).  That is ~8,400 feeds of
   * frames per stream = 4 (T - 15), stream status 0, FCT stepping by one throughout;
   * the process's heap in use (mallinfo2), resident set and the device's free memory, sampled every 256 feeds: flat once the first rounds are through
     (page-locked staging and the windows are sized by then, and this script has stopped keeping frames for the oracle).  Round 6 found 2 .. 3.6 KB
-    per feed here: the HIP runtime's records of copies on streams nobody synchronised (tools/hip_retained_commands.py; engine.hpp: blocking_copy).
+    per feed here: the HIP runtime's records of copies on streams nobody synchronised (tools/hip_retained_commands.py; hip_util.hpp: blocking_copy).
 One JSON object; exit code 1 when a check fails.  Checker use of oracle/ only (like tests/)."""
 import argparse
 import ctypes as C
