@@ -114,6 +114,21 @@ constexpr uint32_t puncture_mask(int pi)
   return m;
 }
 
+// Branch code words of the K = 7 mother code: bit j of code(i) = parity(i & poly_j), i = 7-bit register with the
+// low predecessor's oldest bit 0 (viterbi.c:373-381).  poly 0 == poly 3, so bit 3 == bit 0
+// and only 8 distinct code words exist; code(i ^ 1) = code(i) ^ 7 on the three distinct bits.
+constexpr unsigned parity_u(unsigned x)
+{
+  x ^= x >> 4;
+  x ^= x >> 2;
+  x ^= x >> 1;
+  return x & 1u;
+}
+constexpr unsigned branch_code3(unsigned i)   // bits 0..2 of the code word
+{
+  return parity_u(i & 0x6d) | (parity_u(i & 0x4f) << 1) | (parity_u(i & 0x53) << 2);
+}
+
 // Frequency de-interleaver: carrier index (0..1535, ascending frequency, DC skipped) ->
 // QPSK symbol index within the OFDM symbol.  ETSI 14.6.1.
 inline const std::array<uint16_t, kCarriers>& carrier_to_qpsk()

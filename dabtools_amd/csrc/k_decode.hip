@@ -3,9 +3,10 @@
 //
 //  regroup_kernel / fic_group_kernel  logical CIF rows (demap_kernel folded misc.c:29-39 into its scatter)
 //                  resp. FIC blocks -> natural bit order, 64 records interleaved word by word.
-//  viterbi_fused_kernel  FIC and MSC decoder with the de-puncturing (depuncture.c:45-132) fused into its load.
+//  viterbi_fused_kernel  FIC and MSC decoder with the de-puncturing (depuncture.c:45-132) fused into its load; what it shares with
+//                  the forms of several lanes per code word (vit_two_lanes.hpp, vit_four_lanes.hpp, vit_soft_lanes.hpp): vit_common.hpp.
 //  viterbi_kernel  the same decoder fed with explicit per-step symbols: the S1 seam (dabhip_viterbi_batch).
-//  viterbi_kernel  K=7 rate-1/4 maximum-likelihood decoder with the decisions of the
+//                  Both: K=7 rate-1/4 maximum-likelihood decoder with the decisions of the
 //                  reference's scalar viterbi() (viterbi.c:352-451): one LANE per code word,
 //                  all 64 path metrics of that code word live in the lane's VGPRs (32 packed
 //                  int16 pairs), so the add-compare-select is packed VALU work with no
@@ -43,21 +44,7 @@ namespace dabhip {
 namespace {
 
 // ---------------------------------------------------------------------------------------
-// branch code words: bit j of code(i) = parity(i & poly_j), i = 7-bit register with the
-// low predecessor's oldest bit 0 (viterbi.c:373-381).  poly 0 == poly 3, so bit 3 == bit 0
-// and only 8 distinct code words exist; code(i ^ 1) = code(i) ^ 7 on the three distinct bits.
-__host__ __device__ constexpr unsigned parity_u(unsigned x)
-{
-  x ^= x >> 4;
-  x ^= x >> 2;
-  x ^= x >> 1;
-  return x & 1u;
-}
-__host__ __device__ constexpr unsigned branch_code3(unsigned i)   // bits 0..2 of the code word
-{
-  return parity_u(i & 0x6d) | (parity_u(i & 0x4f) << 1) | (parity_u(i & 0x53) << 2);
-}
-
+// (branch code words: branch_code3, dab_tables.hpp)
 // Path metrics are agreement counts held as packed int16 pairs: 32 VGPRs for the 64 states.
 // In layout L(tau) (tau = 0..3, delta = 1 << tau) register r (0..15) holds states (k, k ^ delta) for the
 // r-th k < 32 whose bit tau is clear, register 16 + r the same pair + 32.  With both members of a
@@ -547,29 +534,14 @@ __device__ __forceinline__ void acs8_tail_lut(uint32_t rows0, uint32_t rows1, in
   survivor_record8(pn, rec);
 }
 
+#include "vit_common.hpp"
+
 // chain back over byte-tag records: block b of 8 steps at my_rec[256 b + 64 j], j = 0..3
 __device__ __forceinline__ void chain_back8(const uint4* my_rec, int nsteps, const uint32_t* __restrict__ prbs_words, uint32_t* dst)
 {
-  unsigned state = 0;
-  uint32_t acc = 0;
-  auto consume = [&](unsigned tags, int t0, int k_hi) {    // steps t0 + k_hi .. t0, newest first
-#pragma unroll
-    for (int k = 7; k >= 0; --k) {
-      const int t = t0 + k;
-      if (k <= k_hi && t >= 6) {                           // steps 0..5 only flush the encoder's initial zeros
-        const unsigned bit = ((tags >> k) & 1u) ^ 1u;      // tag set = low predecessor survived = decision 0
-        state = (state | (bit << 6)) >> 1;
-        const int i = t - 6;                               // data bit index
-        acc |= bit << (8 * ((i >> 3) & 3) + (7 - (i & 7)));
-        if ((i & 31) == 0) {
-          dst[i >> 5] = acc ^ prbs_words[i >> 5];
-          acc = 0;
-        }
-      }
-    }
-  };
+  ChainOut o{prbs_words, dst};
   const int nfull = nsteps >> 3, r = nsteps & 7;
-  if (r) consume(my_rec[static_cast<size_t>(nfull) * 256].x & 255u, 8 * nfull, r - 1);
+  if (r) o.consume<8>(my_rec[static_cast<size_t>(nfull) * 256].x & 255u, 8 * nfull, r - 1);
   // Only the word of a record that holds the current state's byte is fetched (its 16-byte part = state bits 5 and 3): a chain of
   // dependent loads, one memory round trip per 8 steps, but 45 % of the records' sectors instead of all of them -- the stage is
   // bound by the record traffic, and a wave that waits here leaves the SIMD to the forward passes of the others (5.42 -> 5.06 ms;
@@ -581,61 +553,28 @@ __device__ __forceinline__ void chain_back8(const uint4* my_rec, int nsteps, con
   // the chain-back of the group before by one record per eight steps of the next group's forward pass (the load issued at the end of a block, consumed a block
   // later): 5.5 ms against 4.85.  The four words of chain state live across the forward pass's blocks, the kernel has no register to spare (12 spilled), and a
   // scratch reload inside the block waits -- loads and stores retire in order on one counter -- for the record stores issued just before it.
-  // A whole block per step: its decisions d_k = !tag_k (k = 0 .. 7, step 8 b + k), bit-reversed: r8 = d_0 .. d_7 from the top.  Walking
-  // back from step 8 b + 7 to 8 b leaves state (d_0 .. d_5) = r8 >> 2; data bit i = step - 6 goes MSB-first into byte i >> 3: d_6, d_7
-  // are the top two bits of byte b, d_0 .. d_5 the low six bits of byte b - 1 -- the new state itself.
-  for (int b = nfull - 1; b >= 0; --b) {
-    const unsigned reg = ((state >> 5) << 4) | (state & 15u), half = (state >> 4) & 1u, i = reg >> 1, byte = 2u * (reg & 1u) + half;   // survivor_record8's layout
+  for (int b = nfull - 1; b >= 0; --b) {                   // a whole block per step (ChainOut::block8)
+    const unsigned reg = ((o.state >> 5) << 4) | (o.state & 15u), half = (o.state >> 4) & 1u, i = reg >> 1, byte = 2u * (reg & 1u) + half;   // survivor_record8's layout
     const uint32_t w = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(my_rec + static_cast<size_t>(b) * 256 + 64 * (i >> 2)) + (i & 3u));
-    const unsigned tags = (w >> (8u * byte)) & 255u;
-    if (b >= 1) {
-      const unsigned r8 = __brev(~tags & 0xffu) >> 24;
-      state = r8 >> 2;
-      acc |= ((r8 & 3u) << 6) << (8 * (b & 3));
-      if ((b & 3) == 0) {
-        dst[b >> 2] = acc ^ prbs_words[b >> 2];
-        acc = 0;
-      }
-      acc |= state << (8 * ((b - 1) & 3));
-    } else {
-      consume(tags, 0, 7);                                 // steps 0..5 only flush the encoder's initial zeros
-    }
+    o.block8((w >> (8u * byte)) & 255u, b);
   }
 }
 
-// chain back from state 0 (viterbi.c:438-450), descramble (misc.c:41-58), pack MSB first.  my_rec: this lane's
-// records, block b at my_rec[128 b] and my_rec[128 b + 64].
+// chain back over nibble-tag records: block b of 4 steps at my_rec[128 b] and my_rec[128 b + 64].
 __device__ __forceinline__ void chain_back(const uint4* my_rec, int nsteps, const uint32_t* __restrict__ prbs_words, uint32_t* dst)
 {
-  unsigned state = 0;
-  uint32_t acc = 0;
-  auto consume = [&](unsigned nib, int t0, int k_hi) {     // steps t0 + k_hi .. t0, newest first
-#pragma unroll
-    for (int k = 3; k >= 0; --k) {
-      const int t = t0 + k;
-      if (k <= k_hi && t >= 6) {                           // steps 0..5 only flush the encoder's initial zeros
-        const unsigned bit = ((nib >> k) & 1u) ^ 1u;       // tag set = low predecessor survived = decision 0
-        state = (state | (bit << 6)) >> 1;
-        const int i = t - 6;                               // data bit index
-        acc |= bit << (8 * ((i >> 3) & 3) + (7 - (i & 7)));
-        if ((i & 31) == 0) {
-          dst[i >> 5] = acc ^ prbs_words[i >> 5];
-          acc = 0;
-        }
-      }
-    }
-  };
+  ChainOut o{prbs_words, dst};
   const int nfull = nsteps >> 2, r = nsteps & 3;
-  if (r) consume(my_rec[static_cast<size_t>(nfull) * 128].x & 15u, 4 * nfull, r - 1);
+  if (r) o.consume<4>(my_rec[static_cast<size_t>(nfull) * 128].x & 15u, 4 * nfull, r - 1);
   // as in chain_back8: only the 16-byte half of a record that holds the state's nibble is fetched (half = word index >> 2).  (Round 3: two blocks per memory
   // round trip -- both halves of record b - 1 fetched with the selected half of record b -- measured the same, 6.55 against 6.51 .. 6.66 ms.)
   // Block 0 (steps 0..3) only flushes the encoder's initial zeros: nothing to read.
   for (int b = nfull - 1; b >= 1; --b) {
-    const unsigned reg = ((state >> 5) << 4) | (state & 15u), half = (state >> 4) & 1u;
+    const unsigned reg = ((o.state >> 5) << 4) | (o.state & 15u), half = (o.state >> 4) & 1u;
     const unsigned i = reg >> 2, nib = 4u * (reg & 1u) + 2u * half + ((reg >> 1) & 1u);     // survivor_record's layout
     const uint4 v = rec_load(my_rec + static_cast<size_t>(b) * 128 + 64 * (i >> 2));
     const uint32_t lo = (i & 1u) ? in_vgpr(v.y) : in_vgpr(v.x), hi = (i & 1u) ? in_vgpr(v.w) : in_vgpr(v.z);
-    consume((((i & 2u) ? hi : lo) >> (4u * nib)) & 15u, 4 * b, 3);
+    o.consume<4>((((i & 2u) ? hi : lo) >> (4u * nib)) & 15u, 4 * b, 3);
   }
 }
 
@@ -651,24 +590,6 @@ struct MetricScale {
   static constexpr int kRebaseSteps = kBits == 1 ? 256 : 32;
 };
 
-template <int kBits>
-__device__ __forceinline__ void init_metrics(pk16 (&pm)[32])
-{
-  // L(0): register r = states (2r, 2r+1), register 16 + r = states (32 + 2r, 33 + 2r)
-#pragma unroll
-  for (int r = 0; r < 32; ++r) pm[r] = as_pk(0u);
-  pm[0] = as_pk(MetricScale<kBits>::kBase);
-}
-
-template <int kBits>
-__device__ __forceinline__ void rebase_metrics(pk16 (&pm)[32])
-{
-  const uint32_t s0 = (as_u32(pm[0]) & 0xffffu) - MetricScale<kBits>::kBase;
-  const uint32_t base = s0 | (s0 << 16);                  // every half is >= s0: no borrow crosses
-#pragma unroll
-  for (int r = 0; r < 32; ++r) pm[r] = as_pk(as_u32(pm[r]) - base);
-}
-
 // one wave (64 lanes) per group of <= 64 equal-length code words; trellis input = one byte per step (gather_kernel)
 __global__ __launch_bounds__(64) void viterbi_kernel(const WaveGroup* __restrict__ groups, const int* __restrict__ job_ids,
                                                      const CodewordPlan* __restrict__ plans, const uint4* __restrict__ steps,
@@ -682,7 +603,7 @@ __global__ __launch_bounds__(64) void viterbi_kernel(const WaveGroup* __restrict
   uint4* my_rec = reinterpret_cast<uint4*>(decisions + grp.dec_base * 64) + lane;
 
   pk16 pm[32], pn[32], pl4[32];
-  init_metrics<1>(pm);
+  init_metrics(pm, MetricScale<1>::kBase);            // L(0): register r = states (2r, 2r+1), register 16 + r = states (32 + 2r, 33 + 2r)
   const int n16 = (nsteps + 15) >> 4;
   uint4 pack = my_steps[0];
   for (int t16 = 0; t16 < n16; ++t16) {
@@ -699,13 +620,12 @@ __global__ __launch_bounds__(64) void viterbi_kernel(const WaveGroup* __restrict
       if (t + 4 <= nsteps) acs4(ww, pm, pn, pl4, rec);
       else acs_tail(ww, nsteps - t, pm, pn, rec);
     }
-    if ((t16 & 15) == 15) rebase_metrics<1>(pm);
+    if ((t16 & 15) == 15) rebase<1>(pm, MetricScale<1>::kBase);
     pack = next;
   }
   if (lane >= grp.count) return;
   const CodewordPlan pl = plans[grp.plan];
-  const int record = job_ids ? job_ids[grp.first + lane] : grp.first + lane;
-  chain_back(my_rec, nsteps, prbs_words, reinterpret_cast<uint32_t*>(out + static_cast<size_t>(record) * record_stride + pl.out_offset));
+  chain_back(my_rec, nsteps, prbs_words, output_words(job_ids, grp.first + lane, out, record_stride, pl.out_offset));
 }
 
 // Decoder with the de-puncturing fused into the load (depuncture.c:45-132): lane = output record (ETI frame or FIC
@@ -755,78 +675,40 @@ __global__ __launch_bounds__(256, DABHIP_VIT_WAVES) void viterbi_fused_kernel(co
   uint4* my_rec = reinterpret_cast<uint4*>(decisions + grp.dec_base * 64) + lane;
 
   // received words of this lane's record: tile = grp.first / 64 (job lists are padded to tiles of 64)
-  // (a plan whose first word lies outside the row cannot arrive any more: the control plane drops such multiplexes, control_plane.hpp StreamFault;
-  // the clamp keeps even a corrupted plan inside the tile's rows)
-  const int word0 = min((pl.start_bit * kBits) >> 5, row_words - 1);
-  const uint32_t* src = grouped + (static_cast<size_t>(grp.first >> 6) * row_words + word0) * 64 + lane;
-  const int last_word = row_words - 1 - word0;
-  uint64_t fifo = 0;
-  int have = 0;                              // wave-uniform number of valid bits in fifo
-  // (one word ahead; two -- hard -- and six -- soft -- words ahead measured slower, 5.04 against 4.88 and 6.78 against 6.63 ms)
-  uint32_t nextw = src[0];
-  int widx = 1;
-  auto refill = [&]() {
-    fifo |= static_cast<uint64_t>(nextw) << have;
-    have += 32;
-    nextw = src[static_cast<size_t>(min(widx, last_word)) * 64];
-    ++widx;
-  };
+  RowInput<kBits> in(grouped, row_words, grp.first >> 6, pl.start_bit, lane);
 
   constexpr int kScale = kBits == 1 ? 8 : kBits;     // hard decisions run on byte tags here
   pk16 pm[32], pn[32], pl4[32];
-  init_metrics<kScale>(pm);
+  init_metrics(pm, MetricScale<kScale>::kBase);
   int t = 0;
   for (int seg = 0; seg < 5; ++seg) {
-    const uint32_t mask = seg < 4 ? pl.mask[seg] : (puncture_mask(8) & 0x00ffffffu);
-    const int units = seg < 4 ? 4 * pl.blocks[seg] : 1;     // units of 8 trellis steps (= 32 mother-code bits)
-    const int need = __popc(mask);
-    // values taken by each of the 8 steps of a unit, 3 bits per step
-    uint32_t counts = 0;
-    for (int g = 0; g < 8; ++g) counts |= static_cast<uint32_t>(__popc((mask >> (4 * g)) & 15u)) << (3 * g);
-    for (int u = 0; u < units; ++u) {
+    const Segment s(pl, seg);
+    for (int u = 0; u < s.units; ++u) {
       if (kBits == 1) {
-        if (have < need) refill();           // at most one refill per unit: need <= 32
-        uint32_t ww[2] = {0, 0};
-#pragma unroll
-        for (int g = 0; g < 8; ++g) {
-          const int n = (counts >> (3 * g)) & 7;
-          const uint32_t m = (1u << n) - 1u;
-          const uint32_t row = (static_cast<uint32_t>(fifo) & m) + lut_row_base(n);     // table row of (value, mask)
-          fifo >>= n;
-          ww[g >> 2] |= row << (8 * (g & 3));
-        }
-        have -= need;
+        if (in.have < s.need) in.refill();   // at most one refill per unit: need <= 32
+        uint32_t ww[2];
+        in.take_rows(s.counts, s.need, ww);               // table rows of (value, mask)
         // (measurement build DABHIP_VIT_NOSTORE: the MSC code words' records all land on the same four blocks, i.e. stay in L2 --
         // the forward pass without its HBM traffic; the decoded MSC bytes are garbage then, the FIC is untouched)
         const size_t blk = (DABHIP_VIT_NOSTORE && nsteps > 800) ? static_cast<size_t>((t >> 3) & 3) : static_cast<size_t>(t >> 3);
         if (t + 8 <= nsteps) acs8_lut(ww[0], ww[1], lut, pm, pn, pl4, my_rec + blk * 256);
         else if (t < nsteps) acs8_tail_lut(ww[0], ww[1], nsteps - t, lut, pm, pn, pl4, my_rec + blk * 256);
       } else {
-        // a step's values straight out of the fifo's low word (4 n <= 16 bits; n wave-uniform): one 32-bit and, one 64-bit shift per step -- collecting
-        // them in 64-bit words first, to be taken apart again by the steps, cost seven instructions more per step (161 -> 150 per step)
         uint32_t x[8];
-#pragma unroll
-        for (int g = 0; g < 8; ++g) {
-          const int nb = 4 * ((counts >> (3 * g)) & 7);        // bits of this step: 4 per received value
-          if (have < nb) refill();
-          x[g] = static_cast<uint32_t>(fifo) & ((1u << nb) - 1u);
-          fifo >>= nb;
-          have -= nb;
-        }
+        in.take_soft(s.counts, x);
         if (t + 4 <= nsteps) acs4_soft(x[0], x[1], x[2], x[3], soft_lut, pm, pn, pl4, my_rec + static_cast<size_t>(t >> 2) * 128);
         if (t + 8 <= nsteps) acs4_soft(x[4], x[5], x[6], x[7], soft_lut, pm, pn, pl4, my_rec + static_cast<size_t>((t >> 2) + 1) * 128);
         else if (t + 4 < nsteps) acs_tail_soft(x[4], x[5], x[6], nsteps - t - 4, soft_lut, pm, pn, my_rec + static_cast<size_t>((t >> 2) + 1) * 128);
       }
       t += 8;
-      if ((t & (MetricScale<kScale>::kRebaseSteps - 1)) == 0 && t < nsteps) rebase_metrics<kScale>(pm);
+      if ((t & (MetricScale<kScale>::kRebaseSteps - 1)) == 0 && t < nsteps) rebase<1>(pm, MetricScale<kScale>::kBase);
     }
   }
 #if DABHIP_VIT_TIMES
   if (stamp) g_vit_times[4 * g + 1] = wall_clock64();
 #endif
   if (lane < grp.count && !(kBits == 1 && DABHIP_VIT_NOSTORE == 2 && nsteps > 800)) {     // (NOSTORE == 2: ... and without the chain-back)
-    const int record = job_ids ? job_ids[grp.first + lane] : grp.first + lane;
-    uint32_t* dst = reinterpret_cast<uint32_t*>(out + static_cast<size_t>(record) * record_stride + pl.out_offset);
+    uint32_t* dst = output_words(job_ids, grp.first + lane, out, record_stride, pl.out_offset);
 #if defined(DABHIP_CB_PRIO)
     __builtin_amdgcn_s_setprio(DABHIP_CB_PRIO);          // experiment (tools/gpu/cbprio.sh, round 4): the chain-back's few instructions ahead of the others' forward passes -- priority 1 and 3 measured the same as none (4.86 .. 4.95 ms all three, three rounds on one box)
 #endif

@@ -38,18 +38,7 @@ __device__ __forceinline__ uint32_t write_lane(uint32_t old, uint32_t value, int
   return static_cast<uint32_t>(dabhip_llvm_writelane(static_cast<int>(value), lane, static_cast<int>(old)));
 }
 
-__host__ __device__ constexpr unsigned vw_parity(unsigned x)
-{
-  x ^= x >> 4;
-  x ^= x >> 2;
-  x ^= x >> 1;
-  return x & 1u;
-}
-// bits 0..2 of the code word on the branch low predecessor -> state i (bit j = parity(i & poly_j), viterbi.c:35,373-381; bit 3 = bit 0)
-__host__ __device__ constexpr unsigned vw_code3(unsigned i)
-{
-  return vw_parity(i & 0x6d) | (vw_parity(i & 0x4f) << 1) | (vw_parity(i & 0x53) << 2);
-}
+// (branch_code3, dab_tables.hpp: bits 0..2 of the code word on the branch low predecessor -> state i; bit 3 = bit 0)
 __host__ __device__ constexpr unsigned vw_rotl6(unsigned s, unsigned j) { return j == 0 ? s & 63u : ((s << j) | (s >> (6 - j))) & 63u; }
 
 constexpr int kInitOther = -(1 << 24);       // "unreachable" start metric of states 1..63 (viterbi.c:387-389): far below what six steps can collect
@@ -173,7 +162,7 @@ __global__ __launch_bounds__(256) void viterbi_wave_kernel(const WaveGroup* __re
     const unsigned i = vw_rotl6(static_cast<unsigned>(lane), (6u - j) % 6u);      // the new state this lane will hold
     const unsigned b = (static_cast<unsigned>(lane) >> j) & 1u;                  // = i & 1: own metric is the low (0) / high (1) predecessor's
     // j >= 4: the metric of the branch low predecessor -> i for every lane; j <= 3: that of the branch own predecessor -> i
-    const unsigned c = vw_code3(i) ^ ((b && j <= 3) ? 7u : 0u);
+    const unsigned c = branch_code3(i) ^ ((b && j <= 3) ? 7u : 0u);
     bit[ph] = static_cast<int>(b);
     if (kBits == 1) { sh[ph] = 4 * static_cast<int>(c); sgn[ph] = 1; }
     else { sh[ph] = 8 * static_cast<int>(c < 4 ? c : c ^ 7u); sgn[ph] = c < 4 ? 1 : -1; }

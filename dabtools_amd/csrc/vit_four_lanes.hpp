@@ -46,6 +46,22 @@ __host__ __device__ constexpr int at_five(int t)                       // which 
   return -1;
 }
 __host__ __device__ constexpr unsigned cw4(unsigned c) { return c | ((c & 1u) << 3); }
+// register_of (vit_common.hpp: softmulti::chain_back's way from a state to its register; multi::chain_back below and two::chain_back8_two write the same
+// inverse out by hand, which this assertion does not see) inverts this numbering in every layout a record is written in -- pair bit
+// parked at place 4, before a step that is a multiple of 4 (hard blocks: of 8) -- and vit_two_lanes.hpp's lane bit and registers are those of NL = 1
+template <int NL>
+constexpr bool register_of_is_compact()
+{
+  for (int t = 4; t <= 24; t += 4)
+    for (int k = 0; k < 64; ++k) {
+      const unsigned removed = taken<NL>(4, t);
+      const int P = static_cast<int>(register_of(k, removed));
+      if (P != compact(k, removed) || expand(P, removed) != (k & ~static_cast<int>(removed))) return false;
+      if (NL == 1 && (two::lane_bit(t) != place(0, t) || two::phys_of(k, 4, place(0, t)) != P)) return false;
+    }
+  return true;
+}
+static_assert(register_of_is_compact<1>() && register_of_is_compact<2>(), "register_of inverts the compaction numbering");
 
 template <int kCtrl>
 __device__ __forceinline__ uint32_t add_partner(uint32_t partner_reg, uint32_t b)

@@ -1,6 +1,6 @@
 // vit_soft_lanes.hpp — the SOFT-decision decoder with 2^NL lanes per code word (NL = 2: four lanes; NL = 1: two lanes), opt-in (decoder_form.hpp: soft_lanes).
 //
-// Included by k_decode.hip inside its anonymous namespace, after vit_four_lanes.hpp, whose lane-bit rotation, compaction numbering, exchange through
+// Included by k_decode.hip inside its anonymous namespace, after vit_common.hpp and vit_four_lanes.hpp, whose lane-bit rotation, compaction numbering, exchange through
 // quad_perm and re-pairing it reuses unchanged (namespace multi).  What soft values change, all of it run on the CPU first
 // (tools/models/multilane_soft_model.py, held against oracle/or_soft.c by the CPU suite):
 //   * the lane form's soft scale: metrics x16 with FOUR tag bits (MetricScale<4>: kBase 8192, re-base every 32 steps), so a block is 4 steps, every
@@ -18,7 +18,7 @@
 //     lane bit, 0 for the bit at place 5, and exact by construction: every lane reads the lane form's rows for the values as received.
 //   * at an exchange step over id bit i the lanes with that bit set own the HIGH predecessor: their own operand takes the untagged words and the
 //     partner's the tagged ones (the hard form's address ^ 1024; here the tag is added after the select, to A or to B).
-// Input: each lane of a code word repeats the lane form's fifo arithmetic on the code word's row (4 bits per value, refill when have < nb).
+// Input: each lane of a code word repeats the lane form's fifo arithmetic on the code word's row (RowInput<4>::take_soft).
 // Per step and lane at NL = 2: 24 add / max (butterflies) + 8 (words) + 8 (tags) + at most 16 selects.
 // Resources and occupancy: the kernel's comment below.
 
@@ -147,15 +147,16 @@ __device__ __forceinline__ void unit(const uint32_t (&x)[8], int left, const Sof
   else if (left > 4) block_tail<NL, v1>(x[4], x[5], x[6], left - 4, lut, id, pm, pn, h1);
 }
 
-// re-base (MetricScale<4>): state 0 -- lane 0 of the code word, register 0, low half -- back to kBase in all of the code word's lanes
-template <int NL>
-__device__ __forceinline__ void rebase(pk16 (&pm)[Lane<NL>::kRegs])
+// dword idx (0..15) of four fetched 16-byte parts: uint4 idx >> 2, component idx & 3 (the barriers keep the selects in registers, see in_vgpr)
+__device__ __forceinline__ uint32_t pick_word(const uint4 (&q)[4], unsigned idx)
 {
-  const uint32_t r0 = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(as_u32(pm[0])), NL == 1 ? 0xA0 /* [0,0,2,2] */ : 0x00 /* [0,0,0,0] */, 0xf, 0xf, true));
-  const uint32_t s0 = (r0 & 0xffffu) - MetricScale<4>::kBase;
-  const uint32_t base = s0 | (s0 << 16);
+  uint32_t d[4];
 #pragma unroll
-  for (int r = 0; r < Lane<NL>::kRegs; ++r) pm[r] = as_pk(as_u32(pm[r]) - base);
+  for (int u = 0; u < 4; ++u) {
+    const uint32_t lo = (idx & 1u) ? in_vgpr(q[u].y) : in_vgpr(q[u].x), hi = (idx & 1u) ? in_vgpr(q[u].w) : in_vgpr(q[u].z);
+    d[u] = (idx & 2u) ? hi : lo;
+  }
+  return (idx & 8u) ? ((idx & 4u) ? d[3] : d[2]) : ((idx & 4u) ? d[1] : d[0]);
 }
 
 // chain back over the lanes' half-records, in one lane per code word (multi::chain_back's scheme: the whole records of four units per memory round
@@ -165,28 +166,11 @@ template <int NL>
 __device__ __forceinline__ void chain_back(const uint4* cw_rec, int nsteps, const uint32_t* __restrict__ prbs_words, uint32_t* dst)
 {
   constexpr int kLanes = 1 << NL, kVec = Lane<NL>::kRegs / 8, kHalfWords = Lane<NL>::kRegs / 4;
-  unsigned state = 0;
-  uint32_t acc = 0;
-  auto consume = [&](unsigned nib, int t0, int k_hi) {     // steps t0 + k_hi .. t0, newest first
-#pragma unroll
-    for (int k = 3; k >= 0; --k) {
-      const int t = t0 + k;
-      if (k <= k_hi && t >= 6) {                           // steps 0..5 only flush the encoder's initial zeros
-        const unsigned bit = ((nib >> k) & 1u) ^ 1u;       // tag set = low predecessor survived = decision 0
-        state = (state | (bit << 6)) >> 1;
-        const int i = t - 6;
-        acc |= bit << (8 * ((i >> 3) & 3) + (7 - (i & 7)));
-        if ((i & 31) == 0) {
-          dst[i >> 5] = acc ^ prbs_words[i >> 5];
-          acc = 0;
-        }
-      }
-    }
-  };
+  ChainOut o{prbs_words, dst};
   const int nfull = nsteps >> 2, r = nsteps & 3;           // whole blocks of 4 steps; block b = half b & 1 of unit b >> 1
   if (r) {                                                 // state 0's nibble: lane 0, word 0 of the half-record, nibble 0
     const uint4 q = rec_load(cw_rec + static_cast<size_t>(nfull >> 1) * 256 + (NL == 1 ? 64 * (nfull & 1) : 0));
-    consume((NL == 2 && (nfull & 1) ? q.z : q.x) & 15u, 4 * nfull, r - 1);
+    o.consume<4>((NL == 2 && (nfull & 1) ? q.z : q.x) & 15u, 4 * nfull, r - 1);
   }
   int m3 = nfull % 3;                                      // (block + 1) mod 3 of the block in hand
   for (int top = (nfull - 1) >> 1; top >= 0; top -= 4) {
@@ -207,29 +191,16 @@ __device__ __forceinline__ void chain_back(const uint4* cw_rec, int nsteps, cons
       for (int h = 1; h >= 0; --h) {
         const int b = 2 * u + h;
         if (b >= nfull || b < 1) continue;                 // block 0 (steps 0..3) only flushes the encoder's initial zeros
-        const unsigned L0 = m3 == 0 ? 3u : m3 == 1 ? 1u : 5u, L1 = m3 == 0 ? 5u : m3 == 1 ? 3u : 1u;
-        unsigned removed = (1u << 4) | (1u << L0), lane = (state >> L0) & 1u;
+        using multi::place;
+        const unsigned L0 = m3 == 0 ? place(0, 0) : m3 == 1 ? place(0, 4) : place(0, 8), L1 = m3 == 0 ? place(1, 0) : m3 == 1 ? place(1, 4) : place(1, 8);
+        unsigned removed = (1u << 4) | (1u << L0), lane = (o.state >> L0) & 1u;
         if (NL == 2) {
           removed |= 1u << L1;
-          lane |= ((state >> L1) & 1u) << 1;
+          lane |= ((o.state >> L1) & 1u) << 1;
         }
-        unsigned P = 0, pos = 0;
-#pragma unroll
-        for (unsigned bit = 0; bit < 6; ++bit) {
-          const unsigned keep = ((removed >> bit) & 1u) ^ 1u;
-          P |= (((state >> bit) & 1u) & keep) << pos;
-          pos += keep;
-        }
-        const unsigned half = (state >> 4) & 1u, shift = 8u * (2u * (P & 1u) + half) + 4u * ((P >> 1) & 1u);
-        const unsigned idx = lane * (2 * kHalfWords) + static_cast<unsigned>(h) * kHalfWords + (P >> 2);      // word of the unit's 16: uint4 idx >> 2, part idx & 3
-        uint32_t d[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const uint32_t lo = (idx & 1u) ? in_vgpr(q[k][e].y) : in_vgpr(q[k][e].x), hi = (idx & 1u) ? in_vgpr(q[k][e].w) : in_vgpr(q[k][e].z);
-          d[e] = (idx & 2u) ? hi : lo;
-        }
-        const uint32_t w = (idx & 8u) ? ((idx & 4u) ? d[3] : d[2]) : ((idx & 4u) ? d[1] : d[0]);
-        consume((w >> shift) & 15u, 4 * b, 3);
+        const unsigned P = register_of(o.state, removed), half = (o.state >> 4) & 1u, shift = 8u * (2u * (P & 1u) + half) + 4u * ((P >> 1) & 1u);
+        const unsigned idx = lane * (2 * kHalfWords) + static_cast<unsigned>(h) * kHalfWords + (P >> 2);      // word of the unit's 16
+        o.consume<4>((pick_word(q[k], idx) >> shift) & 15u, 4 * b, 3);
         m3 = m3 == 0 ? 2 : m3 - 1;
       }
     }
@@ -238,7 +209,7 @@ __device__ __forceinline__ void chain_back(const uint4* cw_rec, int nsteps, cons
 
 }  // namespace softmulti
 
-// the fused soft decoder (viterbi_fused_kernel<4>'s load, de-puncturing and output) with 2^NL lanes per code word: 2^NL waves per group of 64 code words.
+// the fused soft decoder (vit_common.hpp's front and output) with 2^NL lanes per code word: 2^NL waves per group of 64 code words.
 // LDS: the lane form's SoftLut, 32 KB per workgroup.  As compiled for gfx950 (-Rpass-analysis=kernel-resource-usage): NL = 2: 83 VGPRs, no scratch, no
 // spills, occupancy 5 waves per SIMD -- five workgroups per CU, which is also what 5 x 32 KB = 160 KB of LDS admits (the launch bound asks for four);
 // NL = 1: 115 VGPRs, no scratch, no spills, occupancy 4 waves per SIMD (registers: 512 / 115), four workgroups = 128 KB of LDS.
@@ -262,41 +233,17 @@ __global__ __launch_bounds__(256, NL == 2 ? 4 : 2) void viterbi_soft_lanes_kerne
   const unsigned id = lane & (kLanes - 1);
   const int cw = (64 >> NL) * part + (lane >> NL);           // this lane's code word within the group
   uint4* my_rec = reinterpret_cast<uint4*>(decisions + grp.dec_base * 64) + 64 * kVec * part + lane;
-
-  const int word0 = min((plan->start_bit * 4) >> 5, row_words - 1);
-  const uint32_t* src = grouped + (static_cast<size_t>(grp.first >> 6) * row_words + word0) * 64 + cw;
-  const int last_word = row_words - 1 - word0;
-  uint64_t fifo = 0;
-  int have = 0;
-  uint32_t nextw = src[0];
-  int widx = 1;
-  auto refill = [&]() {
-    fifo |= static_cast<uint64_t>(nextw) << have;
-    have += 32;
-    nextw = src[static_cast<size_t>(min(widx, last_word)) * 64];
-    ++widx;
-  };
-
+  RowInput<4> in(grouped, row_words, grp.first >> 6, plan->start_bit, cw);
   pk16 pm[kRegs], pn[kRegs], pl4[kRegs];
 #pragma unroll
-  for (int r = 0; r < kRegs; ++r) pm[r] = as_pk(0u);
+  for (int r = 0; r < kRegs; ++r) pm[r] = as_pk(0u);         // (init_metrics, written out: through the function the NL = 1 kernel takes 116 VGPRs, not 115)
   pm[0] = as_pk(id ? 0u : MetricScale<4>::kBase);            // state 0: lane 0, register 0, low half
   int t = 0, v = 0;                                          // v = unit index mod 3: the unit's variant
   for (int seg = 0; seg < 5; ++seg) {
-    const uint32_t mask = seg < 4 ? plan->mask[seg] : (puncture_mask(8) & 0x00ffffffu);
-    const int units = seg < 4 ? 4 * plan->blocks[seg] : 1;
-    uint32_t counts = 0;
-    for (int q = 0; q < 8; ++q) counts |= static_cast<uint32_t>(__popc((mask >> (4 * q)) & 15u)) << (3 * q);
-    for (int u = 0; u < units; ++u) {
+    const Segment s(*plan, seg);
+    for (int u = 0; u < s.units; ++u) {
       uint32_t x[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int nb = 4 * ((counts >> (3 * q)) & 7);        // bits of this step: 4 per received value
-        if (have < nb) refill();
-        x[q] = static_cast<uint32_t>(fifo) & ((1u << nb) - 1u);
-        fifo >>= nb;
-        have -= nb;
-      }
+      in.take_soft(s.counts, x);
       if (t < nsteps) {
         uint32_t h0[kHalfWords] = {}, h1[kHalfWords] = {};
         const int left = nsteps - t;
@@ -313,12 +260,9 @@ __global__ __launch_bounds__(256, NL == 2 ? 4 : 2) void viterbi_soft_lanes_kerne
       }
       t += 8;
       v = v == 2 ? 0 : v + 1;
-      if ((t & (MetricScale<4>::kRebaseSteps - 1)) == 0 && t < nsteps) softmulti::rebase<NL>(pm);
+      if ((t & (MetricScale<4>::kRebaseSteps - 1)) == 0 && t < nsteps) rebase<kLanes>(pm, MetricScale<4>::kBase);
     }
   }
-  if (id == 0 && cw < grp.count) {
-    const int record = job_ids ? job_ids[grp.first + cw] : grp.first + cw;
-    uint32_t* dst = reinterpret_cast<uint32_t*>(out + static_cast<size_t>(record) * record_stride + plan->out_offset);
-    softmulti::chain_back<NL>(my_rec, nsteps, prbs_words, dst);
-  }
+  if (id == 0 && cw < grp.count)
+    softmulti::chain_back<NL>(my_rec, nsteps, prbs_words, output_words(job_ids, grp.first + cw, out, record_stride, plan->out_offset));
 }

@@ -16,7 +16,7 @@ def parity(x):
     return bin(x).count("1") & 1
 
 
-def code3(i):                      # k_decode.hip: branch_code3
+def code3(i):                      # dab_tables.hpp: branch_code3
     return parity(i & 0x6d) | (parity(i & 0x4f) << 1) | (parity(i & 0x53) << 2)
 
 
