@@ -1,5 +1,6 @@
 """ctypes loaders for the CPU oracle (oracle/liboracle.so) and, when present, the real
 reference back end (oracle/_ref/libdabref.so).  Test infrastructure only."""
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -266,3 +267,69 @@ def or_replay_afc(iq, cap_frames=4096, trace_cap=4096):
     assert n <= cap_frames
     k = min(nt.value, trace_cap)
     return eti[:n], [tr[i] for i in range(k)], nco[:k]
+
+
+# ---- the fp64 front end driven call by call, with the tuner rule steering its NCO ---------------------------------------------------------------------
+AfcFrame = collections.namedtuple("AfcFrame", "call nco_hz bits soft margins buffer")
+
+
+def _afc_signatures(L):
+    if getattr(L, "_afc_signatures_set", False):
+        return L
+    L.or_sdr_frame.restype = C.POINTER(C.c_double)
+    L.or_sdr_frame.argtypes = [C.c_void_p]
+    L.or_sdr_set_afc.restype = None
+    L.or_sdr_set_afc.argtypes = [C.c_void_p, C.c_int]
+    L.or_afc_step.restype = None
+    L.or_afc_step.argtypes = [C.c_void_p]
+    L.or_sdr_nco_hz.restype = C.c_int32
+    L.or_sdr_nco_hz.argtypes = [C.c_void_p]
+    L._afc_signatures_set = True
+    return L
+
+
+def carrier_walk():
+    """The demapper's carrier walk (input_sdr.c:132-162): for k = 0 .. 1535 in the order the loop meets them, (fftshifted bin, raw DFT bin, place of the
+    carrier's first bit among the symbol's 3072 -- the second bit sits 1536 further)."""
+    shifted = np.array([i for i in range(2048) if 255 < i < 1793 and i != 1024], dtype=np.int64)
+    rev = np.ctypeslib.as_array(oracle().or_rev_freq_deint_tab(), (1536,)).astype(np.int64)
+    return shifted, (shifted + 1024) & 2047, rev
+
+
+def or_frontend_afc_frames(iq, afc=True, margins=False):
+    """or_sdr_demod call by call (262,144 bytes each) with or_afc_step after EVERY call, as or_replay_afc does (afc=False: the plain front end).
+    -> (calls, frames): calls[k] = ((ok, read_frame, coarse_timeshift, fine_timeshift, coarse_freq_shift, fifo_count), fine_freq_shift, nco_hz of call k);
+    frames = one AfcFrame per accepted TF: the call that gave it, the frequency its samples were de-rotated by, the oracle's 230,400 bits (FIC then MSC),
+    or_soft_demap's Q4 values (int8, same places), with margins=True the fp64 quantities the decisions were made of -- Re(cur conj(prev)) at a first bit's
+    place, Im(cur conj(prev)) at a second bit's (positive: the bit is 0) -- and the 393,216-byte frame buffer the TF was demodulated from."""
+    L = _afc_signatures(oracle())
+    iq = np.ascontiguousarray(iq, dtype=np.uint8)
+    S = L.or_sdr_new()
+    L.or_sdr_set_afc(S, 1 if afc else 0)
+    fic, msc = np.zeros(9216, np.uint8), np.zeros(221184, np.uint8)
+    sfic, smsc = np.zeros(9216, np.float32), np.zeros(221184, np.float32)
+    tr = SdrTrace()
+    calls, frames = [], []
+    shifted, _, rev = carrier_walk()
+    for k, off in enumerate(range(0, iq.size - 262144 + 1, 262144)):
+        ok = L.or_sdr_demod(S, _ptr(iq[off:off + 262144]), 262144, _ptr(fic), _ptr(msc))
+        L.or_sdr_get_trace(S, tr)
+        nco = int(L.or_sdr_nco_hz(S))
+        calls.append(((tr.ok, tr.read_frame, tr.coarse_timeshift, tr.fine_timeshift, tr.coarse_freq_shift, tr.fifo_count), tr.fine_freq_shift, nco))
+        if ok:
+            L.or_soft_demap(S, SOFT_Q4, _ptr(sfic, C.c_float), _ptr(smsc, C.c_float))
+            m = None
+            if margins:
+                X = np.ctypeslib.as_array(L.or_sdr_symbols(S), (76, 2048, 2))
+                Z = X[..., 0] + 1j * X[..., 1]
+                z = Z[1:, shifted] * np.conj(Z[:-1, shifted])
+                m = np.zeros((75, 3072))
+                m[:, rev] = z.real
+                m[:, 1536 + rev] = z.imag
+                m = m.reshape(-1)
+            frames.append(AfcFrame(k, nco, np.concatenate([fic, msc]), np.concatenate([sfic, smsc]).astype(np.int8), m,
+                                   np.ctypeslib.as_array(L.or_sdr_buffer(S), (393216,)).copy()))
+        if afc:
+            L.or_afc_step(S)
+    L.or_sdr_free(S)
+    return calls, frames
