@@ -59,7 +59,8 @@ class SynthCfg(C.Structure):
                 ("snr_db", C.c_double), ("cfo_hz", C.c_double),
                 ("fib_patch_len", C.c_int32), ("fib_patch_from_cif", C.c_int32), ("fib_patch", C.c_uint8 * 32),
                 ("reconf", ReconfCfg * 2), ("channel", ChannelCfg), ("dabplus_slots", C.c_uint64), ("dabplus_phase", C.c_int32),
-                ("tii_phase", C.c_int32), ("tii", TiiCfg * 4)]
+                ("tii_phase", C.c_int32), ("tii", TiiCfg * 4),
+                ("packet_slots", C.c_uint64), ("packet_fec_slots", C.c_uint64), ("packet_phase", C.c_int32), ("packet_pad", C.c_int32)]
 
     def set_tii(self, combs, phase=0):
         """The null symbol of every TF with (tf + phase) even carries these combs: up to four (main_id, sub_id, level_db); none = off."""
@@ -194,6 +195,9 @@ _SIGNATURES = {
     "dabhip_synth_payload": (C.c_int, [C.POINTER(SynthCfg), C.c_int, C.c_int, u8p, C.c_int]),
     "dabhip_synth_fibs": (C.c_int, [C.POINTER(SynthCfg), C.c_int, u8p]),
     "dabhip_synth_dabplus_superframe": (C.c_int, [C.POINTER(SynthCfg), C.c_int, C.c_int, u8p, C.c_int]),
+    "dabhip_synth_packet_addresses": (C.c_int, [C.POINTER(SynthCfg), C.c_int, C.POINTER(C.c_int32)]),
+    "dabhip_synth_packet_cells": (C.c_int, [C.POINTER(SynthCfg), C.c_int, C.c_int64, C.c_int, u8p, C.c_int]),
+    "dabhip_synth_packet_group": (C.c_int, [C.POINTER(SynthCfg), C.c_int, C.c_int, C.c_int, u8p, C.c_int]),
     "dabhip_dabplus_create": (C.c_void_p, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "dabhip_dabplus_destroy": (None, [C.c_void_p]),
     "dabhip_dabplus_push": (C.c_int64, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
@@ -202,6 +206,18 @@ _SIGNATURES = {
     "dabhip_dabplus_au_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, u8p, C.c_int64]),
     "dabhip_dabplus_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "dabhip_dabplus_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
+    "dabhip_packet_create": (C.c_void_p, [C.c_int, C.c_int, C.POINTER(C.c_int32), u8p, C.c_int]),
+    "dabhip_packet_destroy": (None, [C.c_void_p]),
+    "dabhip_packet_push": (C.c_int64, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "dabhip_packet_records": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
+    "dabhip_packet_data": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, u8p, C.c_int64]),
+    "dabhip_packet_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "dabhip_packet_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
+    "dabhip_packet_groups_create": (C.c_void_p, []),
+    "dabhip_packet_groups_destroy": (None, [C.c_void_p]),
+    "dabhip_packet_groups_push": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, u8p, C.c_int64]),
+    "dabhip_packet_groups_get": (C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p, u8p, C.c_int64]),
+    "dabhip_packet_groups_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "dabhip_engine_set_fused": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_engine_set_sync_speculation": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_stream_set_sync_speculation": (C.c_int, [C.c_void_p, C.c_int]),
@@ -477,6 +493,29 @@ def synth_dabplus_superframe(cfg, sf_index, slot):
     n = lib().dabhip_synth_dabplus_superframe(C.byref(cfg), sf_index, slot, _p(buf), buf.size)
     _need(n >= 0, "synth_dabplus_superframe")
     return buf[:n].copy()
+
+
+def synth_packet_addresses(cfg, slot):
+    """The addresses the data groups of a packet_slots slot go out on (two or three)."""
+    a = (C.c_int32 * 3)()
+    n = lib().dabhip_synth_packet_addresses(C.byref(cfg), slot, a)
+    _need(n >= 0, "synth_packet_addresses")
+    return [int(a[i]) for i in range(n)]
+
+
+def synth_packet_cells(cfg, slot, cell_index, ncells):
+    """ncells transmitted cells of a packet_slots slot from cell_index on (cells counted from logical CIF 0's first): an (ncells, 24) array."""
+    buf = np.zeros((ncells, 24), dtype=np.uint8)
+    _need(lib().dabhip_synth_packet_cells(C.byref(cfg), slot, cell_index, ncells, _p(buf), buf.size) == buf.size, "synth_packet_cells")
+    return buf
+
+
+def synth_packet_group(cfg, slot, address, n):
+    """The n-th data group of an address of a packet_slots slot, counted from unit 0 on."""
+    buf = np.zeros(8208, dtype=np.uint8)
+    size = lib().dabhip_synth_packet_group(C.byref(cfg), slot, address, n, _p(buf), buf.size)
+    _need(size >= 0, "synth_packet_group")
+    return buf[:size].copy()
 
 
 def stream_ceiling(device=0, nbytes=4 << 30, reps=3):
@@ -884,6 +923,113 @@ class DabPlus(_Handle):
     def stage_ms(self):
         """GPU time of the last push per stage: {"locate", "sync", "rs", "au", "carry"} in ms."""
         return _stage_ms(lib().dabhip_dabplus_stage_ms, self._h, 5)
+
+
+# ---- packet-mode data (dabhip.h: dabhip_packet_*, dabhip_packet_groups_*) --------------------------------------------
+# one record of dabhip_packet_records (dabhip_packet_rec) and of dabhip_packet_groups_get (dabhip_packet_group)
+PACKET_REC = np.dtype([("cell", "<i8"), ("address", "<u2"), ("length", "u1"), ("continuity", "u1"), ("first_last", "u1"), ("command", "u1"),
+                       ("useful_length", "u1"), ("flags", "u1")])
+assert PACKET_REC.itemsize == 16
+PACKET_GROUP = np.dtype([("address", "<i4"), ("length", "<i4"), ("ext_flag", "u1"), ("crc_flag", "u1"), ("seg_flag", "u1"), ("ua_flag", "u1"),
+                         ("type", "u1"), ("continuity", "u1"), ("repetition", "u1"), ("crc_ok", "u1"), ("ext_field", "<u2"), ("last_segment", "u1"),
+                         ("header_ok", "u1"), ("segment_number", "<i4"), ("transport_id", "<i4")])
+assert PACKET_GROUP.itemsize == 28
+PACKET_FROM_FEC, PACKET_FROM_MISS = 1, 2
+PACKET_STATS = ("units", "missed_frames", "sync_losses", "cells_skipped", "bad_cells", "packets", "rs_corrected_bytes", "rs_failed_codewords")
+PACKET_GROUP_STATS = ("groups", "dropped", "orphan_packets", "crc_fails")
+
+
+class Packet(_Handle):
+    """Packet-mode data out of ETI frames on the GPU (dabhip_packet_*): cell streams, FEC frame sync and RS(204,188) correction where fec is set,
+    packet CRCs, for nstreams streams and the sub-channels subch_ids of each.  State (sync, at most 102 cells per lane) carries from push to push."""
+    _destroy = "dabhip_packet_destroy"
+
+    def __init__(self, nstreams, subch_ids, fec=None, device=0):
+        self.nstreams, self.subch_ids = int(nstreams), [int(i) for i in subch_ids]
+        self.fec = [1 if f else 0 for f in (fec if fec is not None else [0] * len(self.subch_ids))]
+        _need(len(self.fec) == len(self.subch_ids), "packet_create: one FEC flag per sub-channel")
+        ids = (C.c_int32 * len(self.subch_ids))(*self.subch_ids)
+        flags = np.array(self.fec + [0], dtype=np.uint8)
+        self._h = lib().dabhip_packet_create(device, self.nstreams, ids, _p(flags), len(self.subch_ids))
+        _need(self._h, "packet_create")
+
+    def push(self, frames, counts=None):
+        """frames as DabPlus.push takes them.  Returns the packets this push took."""
+        if isinstance(frames, tuple):
+            ptr, counts = frames
+            src, on_dev = C.c_void_p(ptr), 1
+        else:
+            if isinstance(frames, list):
+                counts = [np.asarray(f).size // ETI_BYTES for f in frames]
+                arr = np.ascontiguousarray(np.concatenate([np.asarray(f, dtype=np.uint8).reshape(-1) for f in frames]) if frames else np.zeros(0, np.uint8))
+            else:
+                arr = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+                if counts is None:
+                    _need(self.nstreams == 1, "packet_push: counts needed for several streams")
+                    counts = [arr.size // ETI_BYTES]
+            self._keep = arr
+            src, on_dev = C.c_void_p(arr.ctypes.data), 0
+        cnt = (C.c_int64 * self.nstreams)(*[int(c) for c in counts])
+        n = lib().dabhip_packet_push(self._h, src, cnt, on_dev)
+        _need(n >= 0, "packet_push")
+        return n
+
+    def records(self, stream=0, sub=0):
+        """Records of the last push's packets of (stream, sub-channel index): a PACKET_REC array."""
+        n = lib().dabhip_packet_records(self._h, stream, sub, None, 0)
+        _need(n >= 0, "packet_records")
+        out = np.zeros(n, dtype=PACKET_REC)
+        _need(lib().dabhip_packet_records(self._h, stream, sub, out.ctypes.data, n) == n, "packet_records")
+        return out
+
+    def data(self, stream=0, sub=0):
+        """The useful bytes of those packets, one after another."""
+        n = lib().dabhip_packet_data(self._h, stream, sub, None, 0)
+        _need(n >= 0, "packet_data")
+        out = np.zeros(n, dtype=np.uint8)
+        _need(lib().dabhip_packet_data(self._h, stream, sub, _p(out), n) == n, "packet_data")
+        return out
+
+    def stats(self, stream=0, sub=0):
+        """Counters since creation, in PACKET_STATS order (int64 array of 8)."""
+        c = np.zeros(8, dtype=np.int64)
+        _need(lib().dabhip_packet_stats(self._h, stream, sub, c.ctypes.data_as(C.POINTER(C.c_int64))) == 0, "packet_stats")
+        return c
+
+    def stage_ms(self):
+        """GPU time of the last push per stage: {"locate", "sync", "gather", "rs", "cand", "walk", "carry"} in ms."""
+        return _stage_ms(lib().dabhip_packet_stage_ms, self._h, 7)
+
+
+class PacketGroups(_Handle):
+    """MSC data groups out of the packets of one (stream, sub-channel) on the host (dabhip_packet_groups_*).  State carries from push to push."""
+    _destroy = "dabhip_packet_groups_destroy"
+
+    def __init__(self):
+        self._h = lib().dabhip_packet_groups_create()
+        _need(self._h, "packet_groups_create")
+
+    def push(self, records, data):
+        """The records and useful bytes of a push (Packet.records / .data) -> [(PACKET_GROUP record, bytes)] of the groups they complete."""
+        recs = np.ascontiguousarray(records, dtype=PACKET_REC)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        n = lib().dabhip_packet_groups_push(self._h, recs.ctypes.data, recs.size, _p(data), data.size)
+        _need(n >= 0, "packet_groups_push")
+        out = []
+        for i in range(n):
+            rec = np.zeros(1, dtype=PACKET_GROUP)
+            size = lib().dabhip_packet_groups_get(self._h, i, rec.ctypes.data, None, 0)
+            _need(size >= 0, "packet_groups_get")
+            buf = np.zeros(size, dtype=np.uint8)
+            _need(lib().dabhip_packet_groups_get(self._h, i, None, _p(buf), size) == size, "packet_groups_get")
+            out.append((rec[0], buf))
+        return out
+
+    def stats(self):
+        """Counters since creation, in PACKET_GROUP_STATS order (int64 array of 4)."""
+        c = np.zeros(4, dtype=np.int64)
+        _need(lib().dabhip_packet_groups_stats(self._h, c.ctypes.data_as(C.POINTER(C.c_int64))) == 0, "packet_groups_stats")
+        return c
 
 
 # ---- ingest stage: other sample formats and rates -> cu8 at 2.048 Msps (dabhip.h: dabhip_ingest_*) -----------------

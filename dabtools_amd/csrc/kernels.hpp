@@ -10,6 +10,7 @@
 #include "dabplus.hpp"
 #include "device_types.hpp"
 #include "launch_limits.hpp"
+#include "packet.hpp"
 
 namespace dabhip {
 
@@ -199,6 +200,28 @@ hipError_t launch_dabplus_au(const DabPlusJob* jobs, int nsf, const DabPlusLoc* 
 hipError_t launch_dabplus_carry(const DabPlusFrames& fr, int nstreams, uint8_t* carry_next, hipStream_t stream);
 size_t dabplus_gf_table_bytes();                 // the rs kernel's GF(256) tables: their size, and filled on the host
 void dabplus_gf_table_fill(uint8_t* out);
+
+// k_packet.hip: packet-mode data out of ETI frames (packet.hpp has the types and the sync rule, dabhip.h the rules in words).  locate: the
+// sub-channels of every (stream, new frame) into loc [nstreams][maxv][nsub]; sync + scan + jobs: every lane's virtual cell numbering, its units (at
+// most cap each) and the push's unit list, totals = {units, buffer cells}; gather: the units' cells into the cell buffer; rs: the 12 code words of
+// every RS-decoded frame, corrected in place (cw_status: symbols corrected, 0xff = failed; syn: 16 bytes of scratch per code word); cand: per
+// buffer cell, the length of the packet the walk may take there (crc_tab: the CRC-16 byte table); walk: a record per buffer cell (length 0: none)
+// and the counters; carry: every lane's unconsumed cells (at most 102).
+hipError_t launch_packet_locate(const PacketFrames& fr, const int32_t* subch, int nsub, int nstreams, int maxv, PacketLoc* loc, hipStream_t stream);
+hipError_t launch_packet_sync(const PacketFrames& fr, int nstreams, int nsub, int maxv, const uint8_t* fec, PacketLoc* loc, PacketSync* sync, const uint8_t* carry,
+                              PacketSlot* slots, int cap, int* nunits, int* lane_buf, int* ncar_in, int* ncar_out, int* lo, int64_t* counters, PacketUnit* units,
+                              int* lane_unit_base, int* lane_buf_base, int* totals, hipStream_t stream);
+hipError_t launch_packet_gather(const PacketFrames& fr, const PacketUnit* units, const int* totals, int ncells, const PacketLoc* loc, int maxv, int nsub,
+                                const uint8_t* carry, const int* ncar_in, uint8_t* cells, hipStream_t stream);
+hipError_t launch_packet_rs(const PacketUnit* units, const int* totals, int nunits, const uint8_t* gf_tables, uint8_t* cells, uint8_t* cw_status, uint32_t* syn,
+                            hipStream_t stream);
+hipError_t launch_packet_cand(const PacketUnit* units, const int* totals, int ncells, const uint16_t* crc_tab, const uint8_t* cells, uint8_t* cand, hipStream_t stream);
+hipError_t launch_packet_walk(const PacketUnit* units, const int* totals, int nunits, const uint8_t* cells, const uint8_t* cand, const uint8_t* cw_status,
+                              dabhip_packet_rec* recs, int64_t* counters, int* npackets, hipStream_t stream);
+hipError_t launch_packet_carry(const PacketFrames& fr, int nlanes, const PacketLoc* loc, int maxv, int nsub, const uint8_t* carry, const int* ncar_in,
+                               const int* ncar_out, const int* lo, uint8_t* carry_next, hipStream_t stream);
+size_t packet_gf_table_bytes();
+void packet_gf_table_fill(uint8_t* out);
 
 // k_probe.hip: streaming rates of this device (fill, copy, K2's read/write mix) in GB/s -- bench.py's yardstick beside the K2 figure
 int stream_ceiling(int device, size_t bytes, int reps, double* gbs);

@@ -1,0 +1,261 @@
+// packet.cpp — dabhip_packet: the stateful packet-mode consumer of ETI frames (dabhip.h), and dabhip_packet_groups, the host rule above it
+// (packet_groups.hpp).  Each push runs the kernels of k_packet.hip on its own HIP stream over the frames where they lie (device) or after one
+// upload (host); between pushes it keeps the unconsumed cells of every (stream, sub-channel), 102 at most, in one of two carry buffers and the
+// sync state on the device.  The per-cell records, the cell buffer and the counters stay on the device until asked for.
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/dabhip.h"
+#include "dab_bits.hpp"
+#include "kernels.hpp"
+#include "packet.hpp"
+#include "packet_groups.hpp"
+#include "stage_frame.hpp"
+
+using namespace dabhip;
+
+namespace {
+const char* const kStages[7] = {"locate", "sync", "gather", "rs", "cand", "walk", "carry"};
+}
+
+struct dabhip_packet {
+  int nstreams = 0, nsub = 0;
+  DeviceBuffer<int32_t> subch;
+  DeviceBuffer<uint8_t> fec;
+  DeviceBuffer<PacketSync> sync;
+  DeviceBuffer<int64_t> counters;
+  DeviceBuffer<uint8_t> carry[2];
+  int cur = 0;
+  DeviceBuffer<uint8_t> staging;
+  DeviceBuffer<uint8_t> meta;                       // base (int64) | nnew (int), per stream
+  DeviceBuffer<PacketLoc> loc;
+  DeviceBuffer<PacketSlot> slots;
+  DeviceBuffer<PacketUnit> units;
+  DeviceBuffer<int> nunits, lane_buf, ncar_in, ncar_out, lo, lane_unit_base, lane_buf_base, totals;
+  DeviceBuffer<uint8_t> cells, cand, cw_status, gf;
+  DeviceBuffer<uint32_t> syn;
+  DeviceBuffer<uint16_t> crc_tab;
+  DeviceBuffer<dabhip_packet_rec> recs;
+  int64_t n_units = 0, n_cells = 0;
+  // host copies of the last push's lane bases, fetched on first use
+  mutable bool fetched = false;
+  mutable std::vector<int> h_buf_base;
+  StageFrame<7> f{"packet", kStages};
+
+  bool fetch() const
+  {
+    if (fetched) return true;
+    if (!f.use_device()) return false;
+    const size_t nlanes = static_cast<size_t>(nstreams) * nsub;
+    h_buf_base.assign(nlanes + 1, 0);
+    if (n_cells > 0 && !f.ok(blocking_copy(h_buf_base.data(), lane_buf_base.get(), sizeof(int) * (nlanes + 1), hipMemcpyDeviceToHost), "records")) return false;
+    fetched = true;
+    return true;
+  }
+
+  bool lane_ok(int s, int q) const
+  {
+    if (s < 0 || s >= nstreams || q < 0 || q >= nsub) { set_error("packet: no such stream / sub-channel"); return false; }
+    return true;
+  }
+
+  // the per-cell records of one lane of the last push, and its cells when asked for
+  bool lane_cells(int stream, int sub, std::vector<dabhip_packet_rec>& r, std::vector<uint8_t>* bytes) const
+  {
+    if (!lane_ok(stream, sub) || !fetch()) return false;
+    const int l = stream * nsub + sub;
+    const int64_t a = h_buf_base[l], n = h_buf_base[l + 1] - a;
+    r.resize(static_cast<size_t>(n));
+    if (bytes) bytes->resize(static_cast<size_t>(n) * kPkCell);
+    if (n == 0) return true;
+    if (!f.ok(blocking_copy(r.data(), recs.get() + a, sizeof(dabhip_packet_rec) * static_cast<size_t>(n), hipMemcpyDeviceToHost), "records")) return false;
+    return !bytes || f.ok(blocking_copy(bytes->data(), cells.get() + a * kPkCell, bytes->size(), hipMemcpyDeviceToHost), "data");
+  }
+};
+
+extern "C" dabhip_packet* dabhip_packet_create(int device, int nstreams, const int32_t* subch_ids, const uint8_t* fec_flags, int nsub)
+{
+  std::unique_ptr<dabhip_packet> d(new dabhip_packet);
+  StageFrame<7>& f = d->f;
+  if (!f.open(device, "no HIP device: the packet-mode stage runs on the GPU only", "packet_create: device index out of range")) return nullptr;
+  const auto ok = [&f](hipError_t e, const char* what) { return f.ok(e, what); };
+  if (nstreams <= 0 || nsub <= 0 || nsub > 64 || !subch_ids || !fec_flags) { set_error("packet_create: bad arguments"); return nullptr; }
+  for (int q = 0; q < nsub; ++q)
+    if (subch_ids[q] < 0 || subch_ids[q] > 63) { set_error("packet_create: SubChId out of range"); return nullptr; }
+  if (static_cast<int64_t>(nstreams) * nsub > (1 << 24)) { set_error("packet_create: too many (stream, sub-channel) pairs"); return nullptr; }
+  d->nstreams = nstreams;
+  d->nsub = nsub;
+  const size_t nlanes = static_cast<size_t>(nstreams) * nsub;
+  std::vector<uint8_t> gf(packet_gf_table_bytes());
+  packet_gf_table_fill(gf.data());
+  std::vector<uint16_t> crc(256);
+  for (int v = 0; v < 256; ++v) {
+    const uint8_t b = static_cast<uint8_t>(v);
+    crc[v] = crc16_ccitt(&b, 1, 0);   // the CRC register after byte v from 0: the kernel's table-driven step
+  }
+  const size_t carry_bytes = nlanes * kPkCarry * kPkCell;
+  bool good = d->subch.reserve(nsub) && d->fec.reserve(nsub) && d->sync.reserve(nlanes) && d->counters.reserve(nlanes * kPkCntN) && d->gf.reserve(gf.size()) &&
+              d->crc_tab.reserve(crc.size()) && d->carry[0].reserve(carry_bytes) && d->carry[1].reserve(carry_bytes) && d->totals.reserve(4) &&
+              d->nunits.reserve(nlanes) && d->lane_buf.reserve(nlanes) && d->ncar_in.reserve(nlanes) && d->ncar_out.reserve(nlanes) && d->lo.reserve(nlanes) &&
+              d->lane_unit_base.reserve(nlanes + 1) && d->lane_buf_base.reserve(nlanes + 1);
+  good = good && ok(hipMemcpy(d->subch.get(), subch_ids, sizeof(int32_t) * nsub, hipMemcpyHostToDevice), "upload") &&
+         ok(hipMemcpy(d->fec.get(), fec_flags, static_cast<size_t>(nsub), hipMemcpyHostToDevice), "upload") &&
+         ok(hipMemset(d->sync.get(), 0, sizeof(PacketSync) * nlanes), "clear") && ok(hipMemset(d->counters.get(), 0, sizeof(int64_t) * nlanes * kPkCntN), "clear") &&
+         ok(hipMemcpy(d->gf.get(), gf.data(), gf.size(), hipMemcpyHostToDevice), "upload") &&
+         ok(hipMemcpy(d->crc_tab.get(), crc.data(), crc.size() * 2, hipMemcpyHostToDevice), "upload");
+  return good ? d.release() : nullptr;
+}
+
+extern "C" void dabhip_packet_destroy(dabhip_packet* d) { delete d; }
+
+extern "C" int64_t dabhip_packet_push(dabhip_packet* d, const uint8_t* frames, const int64_t* counts, int on_device)
+{
+  if (!d || !counts) { set_error("packet_push: null argument"); return -1; }
+  StageFrame<7>& f = d->f;
+  const auto ok = [&f](hipError_t e, const char* what) { return f.ok(e, what); };
+  if (!f.use_device()) return -1;
+  const int ns = d->nstreams, nsub = d->nsub;
+  std::vector<int64_t> base(static_cast<size_t>(ns));
+  int64_t total = 0;
+  int maxv = 0;
+  for (int s = 0; s < ns; ++s) {
+    if (counts[s] < 0 || counts[s] > (1 << 16)) { set_error("packet_push: bad frame count"); return -1; }
+    base[s] = total;
+    total += counts[s];
+    maxv = std::max<int>(maxv, static_cast<int>(counts[s]));
+  }
+  if (total > 0 && !frames) { set_error("packet_push: null frames"); return -1; }
+  const uint8_t* src = frames;
+  if (total > 0 && !on_device) {
+    const size_t bytes = static_cast<size_t>(total) * DABHIP_ETI_BYTES;
+    if (!d->staging.reserve(bytes) || !ok(hipMemcpyAsync(d->staging.get(), frames, bytes, hipMemcpyHostToDevice, f.stream), "upload")) return -1;
+    src = d->staging.get();
+  }
+  // per-stream metadata in one upload: base | nnew
+  std::vector<uint8_t> meta(static_cast<size_t>(ns) * 12);
+  std::memcpy(meta.data(), base.data(), sizeof(int64_t) * ns);
+  for (int s = 0; s < ns; ++s) {
+    const int n = static_cast<int>(counts[s]);
+    std::memcpy(meta.data() + 8 * ns + 4 * s, &n, 4);
+  }
+  const size_t nlanes = static_cast<size_t>(ns) * nsub;
+  // the units a lane can give in one push: its frames without FEC; with it, a frame per 103 of its carried and new cells (256 per ETI frame at
+  // most) and one more for the frame a first run completes
+  const int cap = std::max(maxv, (kPkCarry + maxv * 256) / kPkFrameCells + 1) + 1;
+  if (!d->meta.reserve(meta.size()) || !d->loc.reserve(static_cast<size_t>(ns) * std::max(maxv, 1) * nsub) || !d->slots.reserve(nlanes * cap) || !d->units.reserve(nlanes * cap))
+    return -1;
+  // the host copy of meta must outlive the asynchronous copy: hipMemcpy from pageable memory returns once the bytes are staged
+  if (!ok(hipMemcpyAsync(d->meta.get(), meta.data(), meta.size(), hipMemcpyHostToDevice, f.stream), "upload") || !ok(hipStreamSynchronize(f.stream), "upload"))
+    return -1;
+  PacketFrames fr;
+  fr.frames = src;
+  fr.base = reinterpret_cast<const int64_t*>(d->meta.get());
+  fr.nnew = reinterpret_cast<const int*>(d->meta.get() + 8 * ns);
+  hipStream_t st = f.stream;
+  const uint8_t* carry = d->carry[d->cur].get();
+  int totals[4] = {0, 0, 0, 0};
+  bool good = f.mark(0) && ok(launch_packet_locate(fr, d->subch.get(), nsub, ns, maxv, d->loc.get(), st), "locate") &&
+              f.mark(1) && ok(hipMemsetAsync(d->totals.get(), 0, sizeof totals, st), "clear") &&
+              ok(launch_packet_sync(fr, ns, nsub, maxv, d->fec.get(), d->loc.get(), d->sync.get(), carry, d->slots.get(), cap, d->nunits.get(), d->lane_buf.get(),
+                                    d->ncar_in.get(), d->ncar_out.get(), d->lo.get(), d->counters.get(), d->units.get(), d->lane_unit_base.get(),
+                                    d->lane_buf_base.get(), d->totals.get(), st), "sync") &&
+              f.mark(2) && ok(hipMemcpyAsync(totals, d->totals.get(), sizeof totals, hipMemcpyDeviceToHost, st), "totals") &&
+              ok(hipStreamSynchronize(st), "sync stage");
+  if (!good) return -1;
+  d->n_units = totals[0];
+  d->n_cells = totals[1];
+  d->fetched = false;
+  const int nu = totals[0], nc = totals[1];
+  const size_t cu = static_cast<size_t>(nu ? nu : 1), cc = static_cast<size_t>(nc ? nc : 1);
+  good = d->cells.reserve(cc * kPkCell) && d->cand.reserve(cc) && d->recs.reserve(cc) && d->cw_status.reserve(cu * kPkRows) && d->syn.reserve(cu * kPkRows * 4) &&
+         ok(launch_packet_gather(fr, d->units.get(), d->totals.get(), nc, d->loc.get(), maxv, nsub, carry, d->ncar_in.get(), d->cells.get(), st), "gather") &&
+         f.mark(3) && ok(launch_packet_rs(d->units.get(), d->totals.get(), nu, d->gf.get(), d->cells.get(), d->cw_status.get(), d->syn.get(), st), "rs") &&
+         f.mark(4) && ok(launch_packet_cand(d->units.get(), d->totals.get(), nc, d->crc_tab.get(), d->cells.get(), d->cand.get(), st), "cand") &&
+         f.mark(5) &&
+         ok(launch_packet_walk(d->units.get(), d->totals.get(), nu, d->cells.get(), d->cand.get(), d->cw_status.get(), d->recs.get(), d->counters.get(),
+                               d->totals.get() + 2, st), "walk") &&
+         f.mark(6) &&
+         ok(launch_packet_carry(fr, static_cast<int>(nlanes), d->loc.get(), maxv, nsub, carry, d->ncar_in.get(), d->ncar_out.get(), d->lo.get(),
+                                d->carry[d->cur ^ 1].get(), st), "carry") &&
+         f.mark(7) && ok(hipMemcpyAsync(totals, d->totals.get(), sizeof totals, hipMemcpyDeviceToHost, st), "totals") && f.finish();
+  if (!good) return -1;
+  d->cur ^= 1;
+  return totals[2];
+}
+
+extern "C" int64_t dabhip_packet_records(const dabhip_packet* d, int stream, int sub, dabhip_packet_rec* out, int64_t cap)
+{
+  std::vector<dabhip_packet_rec> r;
+  if (!d || !d->lane_cells(stream, sub, r, nullptr)) return -1;
+  int64_t n = 0;
+  for (const dabhip_packet_rec& x : r) {
+    if (!x.length) continue;
+    if (out && n < cap) out[n] = x;
+    ++n;
+  }
+  return n;
+}
+
+extern "C" int64_t dabhip_packet_data(const dabhip_packet* d, int stream, int sub, uint8_t* dst, int64_t cap)
+{
+  std::vector<dabhip_packet_rec> r;
+  std::vector<uint8_t> bytes;
+  if (!d || !d->lane_cells(stream, sub, r, &bytes)) return -1;
+  int64_t w = 0;
+  for (size_t c = 0; c < r.size(); ++c) {
+    if (!r[c].length) continue;
+    const int64_t len = r[c].useful_length;
+    if (dst && w + len <= cap) std::memcpy(dst + w, bytes.data() + c * kPkCell + 3, static_cast<size_t>(len));
+    w += len;
+  }
+  return w;
+}
+
+extern "C" int dabhip_packet_stats(const dabhip_packet* d, int stream, int sub, int64_t* counters8)
+{
+  if (!d || !counters8) { set_error("packet_stats: null argument"); return -1; }
+  if (!d->lane_ok(stream, sub)) return -1;
+  if (!d->f.use_device()) return -1;
+  return d->f.ok(blocking_copy(counters8, d->counters.get() + (static_cast<size_t>(stream) * d->nsub + sub) * kPkCntN, sizeof(int64_t) * kPkCntN, hipMemcpyDeviceToHost),
+                 "counters") ? 0 : -1;
+}
+
+extern "C" int dabhip_packet_stage_ms(const dabhip_packet* d, const char** names, float* ms, int cap)
+{
+  if (!d) return -1;
+  return d->f.stage_ms(names, ms, cap);
+}
+
+// ---- data groups (host only) ----------------------------------------------------------------------------------------------------------------
+struct dabhip_packet_groups {
+  PacketGroups g;
+};
+
+extern "C" dabhip_packet_groups* dabhip_packet_groups_create(void) { return new dabhip_packet_groups; }
+extern "C" void dabhip_packet_groups_destroy(dabhip_packet_groups* g) { delete g; }
+
+extern "C" int64_t dabhip_packet_groups_push(dabhip_packet_groups* g, const dabhip_packet_rec* recs, int64_t nrecs, const uint8_t* data, int64_t ndata)
+{
+  if (!g || nrecs < 0 || ndata < 0 || (nrecs > 0 && !recs) || (ndata > 0 && !data)) { set_error("packet_groups_push: bad arguments"); return -1; }
+  if (!g->g.push(recs, nrecs, data, ndata)) { set_error("packet_groups_push: fewer bytes than the records' useful lengths"); return -1; }
+  return static_cast<int64_t>(g->g.done.size());
+}
+
+extern "C" int64_t dabhip_packet_groups_get(const dabhip_packet_groups* g, int64_t i, dabhip_packet_group* rec, uint8_t* dst, int64_t cap)
+{
+  if (!g || i < 0 || i >= static_cast<int64_t>(g->g.done.size())) { set_error("packet_groups_get: no such group"); return -1; }
+  const std::vector<uint8_t>& b = g->g.done_bytes[static_cast<size_t>(i)];
+  if (rec) *rec = g->g.done[static_cast<size_t>(i)];
+  if (dst && cap > 0) std::memcpy(dst, b.data(), static_cast<size_t>(std::min<int64_t>(cap, static_cast<int64_t>(b.size()))));
+  return static_cast<int64_t>(b.size());
+}
+
+extern "C" int dabhip_packet_groups_stats(const dabhip_packet_groups* g, int64_t* counters4)
+{
+  if (!g || !counters4) { set_error("packet_groups_stats: null argument"); return -1; }
+  std::memcpy(counters4, g->g.counters, sizeof g->g.counters);
+  return 0;
+}

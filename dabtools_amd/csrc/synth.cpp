@@ -12,6 +12,7 @@
 #include "dab_bits.hpp"
 #include "dab_tables.hpp"
 #include "dabplus.hpp"
+#include "packet_sync.hpp"
 #include "synth.hpp"
 #include "tii_detect.hpp"
 
@@ -30,7 +31,7 @@ inline uint64_t mix64(uint64_t z)
 }
 inline uint64_t key(uint64_t seed, uint64_t a, uint64_t b, uint64_t c) { return mix64(mix64(mix64(seed ^ mix64(a)) + b) + c); }
 
-enum : uint64_t { kDomPayload = 1, kDomFiller = 2, kDomNoise = 3, kDomDabPlus = 4 };
+enum : uint64_t { kDomPayload = 1, kDomFiller = 2, kDomNoise = 3, kDomDabPlus = 4, kDomPacket = 5 };
 
 SubChannel to_subchannel(const dabhip_subch_cfg& c)
 {
@@ -98,6 +99,15 @@ bool validate(const dabhip_synth_cfg& cfg)
       if (r.at_cif != 0) { set_error("synth: dabplus_slots cannot be combined with reconfigurations"); return false; }
     for (int k = 0; k < cfg.nsub; ++k)
       if ((cfg.dabplus_slots >> k & 1) && to_subchannel(cfg.sub[k]).bitrate % 8) { set_error("synth: a DAB+ slot needs a multiple of 8 kbit/s"); return false; }
+  }
+  if (cfg.packet_fec_slots & ~cfg.packet_slots) { set_error("synth: packet_fec_slots names a slot that packet_slots does not"); return false; }
+  if (cfg.packet_slots) {
+    if (cfg.nsub < 64 && (cfg.packet_slots >> cfg.nsub)) { set_error("synth: packet_slots names a slot past nsub"); return false; }
+    if (cfg.packet_slots & cfg.dabplus_slots) { set_error("synth: a slot cannot be both a packet-mode and a DAB+ slot"); return false; }
+    for (const dabhip_reconf_cfg& r : cfg.reconf)
+      if (r.at_cif != 0) { set_error("synth: packet_slots cannot be combined with reconfigurations"); return false; }
+    for (int k = 0; k < cfg.nsub; ++k)
+      if ((cfg.packet_slots >> k & 1) && to_subchannel(cfg.sub[k]).bitrate % 8) { set_error("synth: a packet-mode slot needs a multiple of 8 kbit/s"); return false; }
   }
   int prev = 0;
   for (const dabhip_reconf_cfg& r : cfg.reconf) {
@@ -221,11 +231,201 @@ void dabplus_protected_part(const dabhip_synth_cfg& cfg, int n, int part, int sl
 
 int floor_div(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
+// ---- packet mode (ETSI EN 300 401 clauses 5.3.2, 5.3.3, 5.3.5; dabhip.h: dabhip_packet has the formats) ----------------------------------------
+// coefficients of prod_{i=0..15} (x + alpha^i), highest degree first
+const uint8_t* rs204_generator()
+{
+  struct Init {
+    uint8_t g[kPkRoots + 1] = {1};
+    Init()
+    {
+      for (int i = 0; i < kPkRoots; ++i) {
+        const uint8_t r = gf().exp[i];
+        for (int k = i + 1; k >= 1; --k) g[k] ^= gf_mul(g[k - 1], r);
+      }
+    }
+  };
+  static const Init g;
+  return g.g;
+}
+
+// the addresses a packet slot's groups go out on: two or three, from the slot's key
+int packet_addresses(const dabhip_synth_cfg& cfg, int slot, int* out3)
+{
+  const uint64_t pk = key(cfg.seed, kDomPacket, static_cast<uint64_t>(slot), ~0ull);
+  const int base = 1 + static_cast<int>((pk >> 8) % 300);
+  for (int i = 0; i < 3; ++i) out3[i] = base + 301 * i;
+  return 2 + static_cast<int>(pk & 1);
+}
+
+using PacketGroupList = std::vector<std::pair<int, std::vector<uint8_t>>>;
+
+// Unit j of a packet slot -- the application table of FEC frame j, or without FEC the cells of logical CIF j: ncells cells filled exactly with the
+// packets of data groups with random lengths and flags on the slot's addresses, which start and end inside the unit, with command and padding
+// packets in between.  `groups`: every group in the order their last packets go out.
+void packet_unit(const dabhip_synth_cfg& cfg, int slot, int j, int ncells, uint8_t* out, PacketGroupList* groups)
+{
+  uint64_t ctr = 0;
+  const uint64_t uk = (static_cast<uint64_t>(static_cast<uint32_t>(j)) << 8) | static_cast<uint64_t>(slot);
+  const auto below = [&](int m) { return static_cast<int>(key(cfg.seed, kDomPacket, uk, ctr++) % static_cast<uint64_t>(m)); };
+  int addr[3];
+  const int naddr = packet_addresses(cfg, slot, addr);
+  std::vector<uint8_t> open[3];
+  bool is_open[3] = {false, false, false}, crc_flag[3] = {false, false, false};
+  int ci[3], nopen = 0, room = ncells;
+  for (int a = 0; a < 3; ++a) ci[a] = below(4);
+  uint8_t* p = out;
+  // one packet of L cells; for a data packet of address index a, `useful` is what the group gets
+  const auto packet = [&](int L, int cont, int fl, int address, int cmd, const uint8_t* useful, int ulen) {
+    const int n = kPkCell * L;
+    std::memset(p, 0, static_cast<size_t>(n));
+    p[0] = static_cast<uint8_t>(((L - 1) << 6) | (cont << 4) | (fl << 2) | (address >> 8));
+    p[1] = static_cast<uint8_t>(address & 0xff);
+    p[2] = static_cast<uint8_t>((cmd << 7) | ulen);
+    if (ulen) std::memcpy(p + 3, useful, static_cast<size_t>(ulen));
+    const uint16_t crc = static_cast<uint16_t>(~crc16_ccitt(p, static_cast<size_t>(n - 2)));
+    p[n - 2] = static_cast<uint8_t>(crc >> 8);
+    p[n - 1] = static_cast<uint8_t>(crc & 0xff);
+    p += n;
+    room -= L;
+  };
+  // a data packet of address index a: opens a group (its header first), goes on with it or, with last, ends it (the group CRC last)
+  const auto data_packet = [&](int a, int L, bool last) {
+    const bool first = !is_open[a];
+    std::vector<uint8_t>& g = open[a];
+    const int cap = kPkCell * L - 5;
+    uint8_t useful[kPkCell * 4];
+    int n = 0;
+    if (first) {
+      g.clear();
+      const int flags = below(16), ua = flags & 1;
+      crc_flag[a] = flags >> 2 & 1;
+      useful[n++] = static_cast<uint8_t>((flags << 4) | below(16));
+      useful[n++] = static_cast<uint8_t>(below(256));
+      for (int i = 0; i < ((flags >> 3 & 1) ? 2 : 0) + ((flags >> 1 & 1) ? 2 : 0); ++i) useful[n++] = static_cast<uint8_t>(below(256));
+      if (ua) {
+        const int tflag = below(2), li = 2 * tflag + below(4);
+        useful[n++] = static_cast<uint8_t>((below(8) << 5) | (tflag << 4) | li);
+        for (int i = 0; i < li; ++i) useful[n++] = static_cast<uint8_t>(below(256));
+      }
+    }
+    const int tail = last && crc_flag[a] ? 2 : 0;
+    const int least = std::max(n + tail, 1);
+    const int ulen = below(4) ? cap : least + below(cap - least + 1);
+    while (n < ulen - tail) useful[n++] = static_cast<uint8_t>(below(256));
+    g.insert(g.end(), useful, useful + n);
+    if (tail) {
+      const uint16_t crc = static_cast<uint16_t>(~crc16_ccitt(g.data(), g.size()));
+      useful[n++] = static_cast<uint8_t>(crc >> 8);
+      useful[n++] = static_cast<uint8_t>(crc & 0xff);
+      g.insert(g.end(), useful + n - 2, useful + n);
+    }
+    ci[a] = (ci[a] + 1) & 3;
+    packet(L, ci[a], (first ? 2 : 0) | (last ? 1 : 0), addr[a], 0, useful, n);
+    if (first && !last) ++nopen;
+    if (!first && last) --nopen;
+    is_open[a] = !last;
+    if (last && groups) groups->emplace_back(addr[a], g);
+  };
+  while (room > 0) {
+    const int slack = room - nopen;                   // the cells free beyond one closing cell for every open group
+    if (slack == 0) {
+      int a = 0;
+      while (!is_open[a]) ++a;
+      data_packet(a, 1, true);
+      continue;
+    }
+    const int kind = below(10);
+    if (kind <= 1) {
+      const int L = 1 + below(std::min(4, slack));
+      if (kind == 0) {
+        packet(L, 0, 3, 0, 0, nullptr, 0);
+      } else {
+        uint8_t useful[kPkCell * 4];
+        const int ulen = below(kPkCell * L - 4);
+        for (int i = 0; i < ulen; ++i) useful[i] = static_cast<uint8_t>(below(256));
+        packet(L, below(4), 3, addr[below(naddr)], 1, useful, ulen);
+      }
+      continue;
+    }
+    const int a = below(naddr);
+    if (is_open[a]) {
+      const bool last = below(3) == 0;
+      data_packet(a, 1 + below(std::min(4, slack + (last ? 1 : 0))), last);
+    } else {
+      const bool only = slack < 2 || below(4) == 0;
+      data_packet(a, 1 + below(std::min(4, only ? slack : slack - 1)), only);
+    }
+  }
+}
+
+// the cells of unit j of a packet slot as sent: without FEC the ncells cells; with it the 94 table cells and the 9 FEC cells
+void packet_unit_cells(const dabhip_synth_cfg& cfg, int slot, int j, int ncells, bool fec, std::vector<uint8_t>& out)
+{
+  struct Cache {
+    uint64_t seed = 0;
+    int slot = -1, j = 0, ncells = 0;
+    bool fec = false;
+    std::vector<uint8_t> cells;
+  };
+  thread_local Cache cache;
+  if (cache.slot == slot && cache.seed == cfg.seed && cache.j == j && cache.ncells == ncells && cache.fec == fec) {
+    out = cache.cells;
+    return;
+  }
+  out.assign(static_cast<size_t>(fec ? kPkFrameCells : ncells) * kPkCell, 0);
+  packet_unit(cfg, slot, j, ncells, out.data(), nullptr);
+  if (fec) {
+    const uint8_t* g = rs204_generator();
+    uint8_t parity[kPkRoots * kPkRows + 6] = {0};
+    for (int r = 0; r < kPkRows; ++r) {
+      uint8_t rem[kPkRoots] = {0};
+      for (int c = 0; c < kPkK; ++c) {
+        const uint8_t fb = out[r + kPkRows * c] ^ rem[0];
+        for (int q = 0; q < kPkRoots - 1; ++q) rem[q] = rem[q + 1] ^ gf_mul(fb, g[q + 1]);
+        rem[kPkRoots - 1] = gf_mul(fb, g[kPkRoots]);
+      }
+      for (int q = 0; q < kPkRoots; ++q) parity[r + kPkRows * q] = rem[q];
+    }
+    for (int i = 0; i < kPkFecCells; ++i) {
+      uint8_t* cell = out.data() + (kPkDataCells + i) * kPkCell;
+      cell[0] = static_cast<uint8_t>((i << 2) | (kPkFecAddress >> 8));
+      cell[1] = static_cast<uint8_t>(kPkFecAddress & 0xff);
+      std::memcpy(cell + 2, parity + kPkFecPayload * i, kPkFecPayload);
+    }
+  }
+  cache.seed = cfg.seed;
+  cache.slot = slot;
+  cache.j = j;
+  cache.ncells = ncells;
+  cache.fec = fec;
+  cache.cells = out;
+}
+
+int64_t floor_div64(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+
+// n cells of a packet slot of s cells per CIF from cell c on, cells counted from logical CIF 0's first
+void packet_cells(const dabhip_synth_cfg& cfg, int slot, int s, int64_t c, int n, uint8_t* out)
+{
+  const bool fec = cfg.packet_fec_slots >> slot & 1;
+  std::vector<uint8_t> unit;
+  for (int i = 0; i < n; ++i, ++c) {
+    const int64_t per = fec ? kPkFrameCells : s, rel = fec ? c - cfg.packet_phase : c;
+    const int64_t j = floor_div64(rel, per);
+    packet_unit_cells(cfg, slot, static_cast<int>(j), fec ? kPkDataCells : s, fec, unit);
+    std::memcpy(out + static_cast<size_t>(i) * kPkCell, unit.data() + (rel - j * per) * kPkCell, kPkCell);
+  }
+}
+
 void payload_bytes(const dabhip_synth_cfg& cfg, int cif, int slot, uint8_t* out, int n)
 {
   if (cfg.dabplus_slots >> slot & 1) {                     // n = 24 s
     const int rel = cif - cfg.dabplus_phase, sf = floor_div(rel, kSfFrames);
     dabplus_protected_part(cfg, sf, rel - kSfFrames * sf, slot, n / 24, out);
+    return;
+  }
+  if (cfg.packet_slots >> slot & 1) {                      // n = 24 s
+    packet_cells(cfg, slot, n / 24, static_cast<int64_t>(cif) * (n / 24), n / 24, out);
     return;
   }
   for (int i = 0; i < n; i += 8) {
@@ -573,7 +773,7 @@ extern "C" int dabhip_synth_payload(const dabhip_synth_cfg* cfg, int cif_index, 
   if (!cfg) { set_error("synth_payload: bad slot"); return -1; }
   const Multiplex mux = multiplex_at(*cfg, cif_index, false);
   if (slot < 0 || slot >= mux.nsub) { set_error("synth_payload: bad slot"); return -1; }
-  if (cfg->dabplus_slots && !validate(*cfg)) return -1;
+  if ((cfg->dabplus_slots || cfg->packet_slots || cfg->packet_fec_slots) && !validate(*cfg)) return -1;
   const int n = to_subchannel(mux.sub[slot]).bitrate * 3;
   if (cap < n) { set_error("synth_payload: buffer too small"); return -1; }
   payload_bytes(*cfg, cif_index, slot, out, n);
@@ -591,6 +791,55 @@ extern "C" int dabhip_synth_dabplus_superframe(const dabhip_synth_cfg* cfg, int 
   if (cap < kRsK * s) { set_error("synth_dabplus_superframe: buffer too small"); return -1; }
   dabplus_superframe(*cfg, sf_index, slot, s, out);
   return kRsK * s;
+}
+
+namespace {
+bool packet_slot_ok(const dabhip_synth_cfg* cfg, int slot, const char* who)
+{
+  if (!cfg || slot < 0 || slot >= cfg->nsub || slot >= 64 || !(cfg->packet_slots >> slot & 1)) {
+    set_error(std::string(who) + ": not a packet-mode slot");
+    return false;
+  }
+  return validate(*cfg);
+}
+}  // namespace
+
+extern "C" int dabhip_synth_packet_addresses(const dabhip_synth_cfg* cfg, int slot, int32_t* out3)
+{
+  if (!out3 || !packet_slot_ok(cfg, slot, "synth_packet_addresses")) return -1;
+  int a[3];
+  const int n = packet_addresses(*cfg, slot, a);
+  for (int i = 0; i < n; ++i) out3[i] = a[i];
+  return n;
+}
+
+extern "C" int dabhip_synth_packet_cells(const dabhip_synth_cfg* cfg, int slot, int64_t cell_index, int ncells, uint8_t* out, int cap)
+{
+  if (!out || ncells < 0 || !packet_slot_ok(cfg, slot, "synth_packet_cells")) return -1;
+  if (cap / kPkCell < ncells) { set_error("synth_packet_cells: buffer too small"); return -1; }
+  packet_cells(*cfg, slot, to_subchannel(cfg->sub[slot]).bitrate / 8, cell_index, ncells, out);
+  return ncells * kPkCell;
+}
+
+extern "C" int dabhip_synth_packet_group(const dabhip_synth_cfg* cfg, int slot, int address, int n, uint8_t* out, int cap)
+{
+  if (n < 0 || !packet_slot_ok(cfg, slot, "synth_packet_group")) return -1;
+  const bool fec = cfg->packet_fec_slots >> slot & 1;
+  const int ncells = fec ? kPkDataCells : to_subchannel(cfg->sub[slot]).bitrate / 8;
+  std::vector<uint8_t> cells(static_cast<size_t>(ncells) * kPkCell);
+  int seen = 0;
+  for (int j = 0; j < (1 << 16); ++j) {
+    PacketGroupList groups;
+    packet_unit(*cfg, slot, j, ncells, cells.data(), &groups);
+    for (const auto& g : groups) {
+      if (g.first != address || seen++ != n) continue;
+      const int len = static_cast<int>(g.second.size());
+      if (out && cap > 0) std::memcpy(out, g.second.data(), static_cast<size_t>(std::min(len, cap)));
+      return len;
+    }
+  }
+  set_error("synth_packet_group: no such group");
+  return -1;
 }
 
 extern "C" int dabhip_synth_fibs(const dabhip_synth_cfg* cfg, int cif_index, uint8_t* out96)

@@ -607,6 +607,90 @@ int dabhip_dabplus_stats(const dabhip_dabplus *d, int stream, int sub, int64_t *
 /* GPU time of the last push in ms, stage by stage (names: "locate", "sync", "rs", "au", "carry"; as dabhip_engine_stage_ms); returns the count. */
 int dabhip_dabplus_stage_ms(const dabhip_dabplus *d, const char **names, float *ms, int cap);
 
+/* ---- packet-mode data (ETSI EN 300 401 clauses 5.3.2, 5.3.3, 5.3.5) ----------------------- */
+/* A stateful consumer of ETI frames that extracts the packets of packet-mode sub-channels on the GPU, with the enhanced packet mode's outer
+ * code RS(204,188) where a sub-channel is created with fec = 1.  Off unless asked for, and handled like dabhip_dabplus: frames are pushed
+ * stream by stream, the state of every (stream, sub-channel) carries from push to push (at most 102 cells each), and any cutting of a stream
+ * into pushes gives the same records.  These rules were written from the standard, not from a broadcast recording.
+ *
+ * Cells.  A sub-channel of 8 s kbit/s (STL = 3 s) carries s cells of 24 bytes per ETI frame; the cell stream of a (stream, SubChId) is the cells
+ * of its frames in order.  A frame that lacks the id, or lists it with STL 0, an STL that is no multiple of 3 or a payload past byte 6144, breaks
+ * the stream and gives no cells; a frame whose STL differs from the stream's breaks it and starts the next stream.  A break drops sync (counted as
+ * a sync loss when there was sync) and every cell not consumed yet (counted as skipped).  If the STC lists the id twice, the first entry counts.
+ *
+ * Packet: 3 header bytes -- length code (2 bits: 1..4 cells), continuity index (2), first/last (2: 10 first, 00 intermediate, 01 last, 11 one and
+ * only), address (10; 0 = padding), command (1), useful length (7; at most 24 L - 5) --, a data field of 24 L - 5 bytes with the useful bytes
+ * first, and the CRC (x^16 + x^12 + x^5 + 1 from 0xFFFF, complemented, most significant byte first) over header and data field.
+ *
+ * FEC frame: 103 cells, 94 data cells (the 2256-byte application table) and 9 FEC cells of 2 header bytes (length code 00, a 4-bit counter 0..8,
+ * address 1022) and 22 RS bytes: 192 parity bytes, then 6 zero bytes.  With Z the table followed by the parity, code word r (0..11) is Z[r + 12 c],
+ * c = 0..203, byte c the coefficient of x^(203 - c); GF(256) by 0x11D, alpha = 2, generator prod (x + alpha^i), i = 0..15.  Decoding is bounded-
+ * distance: a word within distance 8 of a code word is corrected, any other is left as received and counted as failed.
+ *
+ * FEC sync, per (stream, sub-channel) with fec = 1.  A run at cell k: cells k..k+8 carry the FEC header with counters 0..8.  Unsynced, the first
+ * run at k makes sync; if the 94 cells before it are unconsumed cells of the unbroken stream, cells k-94..k+8 are a frame and are decoded, else
+ * the unconsumed cells up to k+8 are skipped; the next frame starts at k+9.  Synced, every 103 cells are a frame: a hit when at least 5 of its 9
+ * FEC cells carry their own header, which is RS-decoded; else a miss, which is walked as received and flagged.  The 3rd consecutive miss is not
+ * walked: it loses sync, and the search resumes at the cell after that frame's first, with the frame's cells unconsumed.
+ *
+ * Walk.  The unit is the 94 data cells of an FEC frame after correction, or the s cells of one ETI frame without FEC.  From cell 0: the packet
+ * that would start at cell k with length L is taken when k + L fits in the unit, its useful length is at most 24 L - 5 and its CRC is good,
+ * then k += L; otherwise cell k is counted bad and k += 1.  Only taken packets give records (padding packets included). */
+typedef struct dabhip_packet dabhip_packet;
+#define DABHIP_PACKET_FROM_FEC 1    /* from an RS-decoded frame */
+#define DABHIP_PACKET_FROM_MISS 2   /* from a missed frame, walked as received */
+typedef struct dabhip_packet_rec {  /* one packet of the last push */
+  int64_t cell;                     /* index of its first cell among the cells of its (stream, sub-channel) since creation */
+  uint16_t address;
+  uint8_t length;                   /* cells, 1..4 */
+  uint8_t continuity;
+  uint8_t first_last;               /* 2 first, 0 intermediate, 1 last, 3 one and only */
+  uint8_t command;
+  uint8_t useful_length;
+  uint8_t flags;                    /* DABHIP_PACKET_FROM_* */
+} dabhip_packet_rec;
+/* nsub SubChIds with their FEC flags, the same for every stream.  NULL when there is no GPU (dabhip_last_error). */
+dabhip_packet *dabhip_packet_create(int device, int nstreams, const int32_t *subch_ids, const uint8_t *fec_flags, int nsub);
+void dabhip_packet_destroy(dabhip_packet *d);
+/* counts[s] ETI frames of stream s, stream after stream in `frames`, in DEVICE memory when on_device != 0 (no alignment needed), else in host
+ * memory.  Returns the packets taken by this call, <0 on error. */
+int64_t dabhip_packet_push(dabhip_packet *d, const uint8_t *frames, const int64_t *counts, int on_device);
+/* The packets of the last push of one (stream, sub-channel index), in order: copies min(n, cap) records, returns n. */
+int64_t dabhip_packet_records(const dabhip_packet *d, int stream, int sub, dabhip_packet_rec *out, int64_t cap);
+/* Their useful bytes, packet after packet (cap bytes at most); returns the byte count. */
+int64_t dabhip_packet_data(const dabhip_packet *d, int stream, int sub, uint8_t *dst, int64_t cap);
+/* Counters since creation: units walked (FEC frames, or ETI frames without FEC), missed frames walked, sync losses, cells skipped, bad cells,
+ * packets, RS corrected bytes, RS failed code words.  Returns 0, <0 on error. */
+int dabhip_packet_stats(const dabhip_packet *d, int stream, int sub, int64_t *counters8);
+/* GPU time of the last push in ms, stage by stage (names: "locate", "sync", "gather", "rs", "cand", "walk", "carry"); returns the count. */
+int dabhip_packet_stage_ms(const dabhip_packet *d, const char **names, float *ms, int cap);
+
+/* Data groups out of the packets of ONE (stream, sub-channel), on the host.  Assembly runs per address != 0 over command = 0 packets.  A first or
+ * only packet opens a group; an open group it finds unfinished is dropped and counted.  An intermediate or last packet is appended only to an
+ * open group whose last packet's continuity index is one less (mod 4); with an open group and another index the group is dropped; with none it is
+ * counted as an orphan.  A last or only packet completes the group.  A group that would pass 8208 bytes is dropped.  State carries from push to push. */
+typedef struct dabhip_packet_groups dabhip_packet_groups;
+typedef struct dabhip_packet_group {
+  int32_t address;
+  int32_t length;                   /* bytes, header and CRC included */
+  uint8_t ext_flag, crc_flag, seg_flag, ua_flag;
+  uint8_t type, continuity, repetition;
+  uint8_t crc_ok;                   /* crc_flag set: the packet CRC-16 over all but the last two bytes equals them; else 0 */
+  uint16_t ext_field;               /* ext_flag set */
+  uint8_t last_segment;             /* seg_flag set */
+  uint8_t header_ok;                /* the group is long enough for the header its flags announce (else the fields below are -1) */
+  int32_t segment_number;           /* seg_flag set, else -1 */
+  int32_t transport_id;             /* ua_flag and the transport id flag set, else -1 */
+} dabhip_packet_group;
+dabhip_packet_groups *dabhip_packet_groups_create(void);
+void dabhip_packet_groups_destroy(dabhip_packet_groups *g);
+/* nrecs records in order with their ndata useful bytes (dabhip_packet_records / _data).  Returns the groups this call completed, <0 on error. */
+int64_t dabhip_packet_groups_push(dabhip_packet_groups *g, const dabhip_packet_rec *recs, int64_t nrecs, const uint8_t *data, int64_t ndata);
+/* Group i of the last push: its record, and min(length, cap) of its bytes into dst (may be null); returns its length, <0 on error. */
+int64_t dabhip_packet_groups_get(const dabhip_packet_groups *g, int64_t i, dabhip_packet_group *rec, uint8_t *dst, int64_t cap);
+/* Counters since creation: groups completed, groups dropped, orphan packets, groups whose CRC failed.  Returns 0. */
+int dabhip_packet_groups_stats(const dabhip_packet_groups *g, int64_t *counters4);
+
 /* ---- ingest stage: other sample formats and rates -> the canonical cu8 at 2.048 Msps ------------------------------
  * Off unless asked for: a stateful object in front of the decoder that turns nstreams streams of cu8 / cs8 / cs16 / cf32 IQ (I first, little-endian)
  * at an integer sample rate Fin into cu8 at 2,048,000 samples/s in device memory, ready for dabhip_engine_decode(..., on_device = 1) and
@@ -919,6 +1003,17 @@ typedef struct dabhip_synth_cfg {
    * refuses a configuration with TII set. */
   int32_t tii_phase;
   dabhip_tii_cfg tii[4];
+  /* Packet-mode content (see "packet-mode data" above; all zero = off, byte-identical captures): bit k of packet_slots set = slot k carries packets
+   * instead of keyed random bytes; bit k of packet_fec_slots (a subset) = with the FEC frames of the enhanced packet mode.  With FEC, frame j of a
+   * slot starts at cell 103 j + packet_phase, cells counted from logical CIF 0's first (j may be negative: every cell belongs to a frame); without,
+   * every logical CIF's cells are a unit.  Each unit is filled from the slot's key: data groups with random lengths and flags, which start and end
+   * inside the unit, cut into packets of mixed lengths on two or three addresses, command packets in between, padding packets to fill it exactly;
+   * then the parity.  The slots' bit rates must be multiples of 8 kbit/s; refused on a DAB+ slot, on a slot past nsub, and together with
+   * reconfigurations. */
+  uint64_t packet_slots;
+  uint64_t packet_fec_slots;
+  int32_t packet_phase;
+  int32_t packet_pad;
 } dabhip_synth_cfg;
 
 /* preset 0: 12 sub-channels, 1136 kbit/s, 862 CU (the benchmark mix); 1: 4 light sub-channels. */
@@ -936,6 +1031,12 @@ int dabhip_synth_fibs(const dabhip_synth_cfg *cfg, int cif_index, uint8_t *out96
 /* The unprotected 110 s bytes of DAB+ superframe sf_index of slot (a dabplus_slots slot of 8 s kbit/s): fire code, header, au_start, the AUs
  * with their CRCs -- before the RS parity and the interleaving that dabhip_synth_payload's bytes carry.  Returns 110 s, <0 on error. */
 int dabhip_synth_dabplus_superframe(const dabhip_synth_cfg *cfg, int sf_index, int slot, uint8_t *out, int cap);
+/* Truth of a packet-mode slot, straight from the generator (not through dabhip_packet): the addresses its groups go out on (2 or 3, returns the
+ * count); ncells transmitted cells from cell_index on (cells counted from logical CIF 0's first; returns 24 ncells); the n-th data group of an
+ * address, counted from unit 0 on (FEC frame 0, or logical CIF 0 without FEC): min(length, cap) bytes, returns the length.  <0 on error. */
+int dabhip_synth_packet_addresses(const dabhip_synth_cfg *cfg, int slot, int32_t *out3);
+int dabhip_synth_packet_cells(const dabhip_synth_cfg *cfg, int slot, int64_t cell_index, int ncells, uint8_t *out, int cap);
+int dabhip_synth_packet_group(const dabhip_synth_cfg *cfg, int slot, int address, int n, uint8_t *out, int cap);
 /* Device-side modulator (needs a GPU): the ensembles cfgs[0..nstreams) modulated on `device`
  * straight into DEVICE buffers iq[i] of dabhip_synth_bytes(&cfgs[i], ntf) bytes each.  The bit content comes from the
  * same generator as dabhip_synth_generate; samples may differ from the host generator's by one LSB where fp32 and
