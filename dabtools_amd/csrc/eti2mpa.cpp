@@ -39,10 +39,15 @@ int main(int argc, char** argv)
     }
     const int ficf = buf[5] >> 7, nst = buf[5] & 0x7f;
     int offset = 12 + 4 * nst + ficf * 96, length = -1;
-    for (int i = 0; i < nst; ++i) {
+    // a sub-channel that does not lie whole inside the frame counts as absent (the kernels' test: k_packet.hip, k_dabplus.hip); the walk stops
+    // once an entry has run past the frame
+    for (int i = 0; i < nst && offset <= static_cast<int>(sizeof buf); ++i) {
       const int scid = buf[8 + 4 * i] >> 2;
       const int stl = ((buf[8 + 4 * i + 2] & 3) << 8) | buf[8 + 4 * i + 3];
-      if (scid == want) { length = stl * 8; break; }
+      if (scid == want) {
+        if (offset + stl * 8 <= static_cast<int>(sizeof buf)) length = stl * 8;
+        break;
+      }
       offset += stl * 8;
     }
     if (length < 0) { ++missing; continue; }

@@ -77,7 +77,7 @@ __device__ inline const uint8_t* cell_ptr(const PacketLoc* loc, int stream, int 
 
 __global__ void __launch_bounds__(64) packet_sync_kernel(PacketFrames fr, int nstreams, int nsub, int maxv, const uint8_t* fec, PacketLoc* loc, PacketSync* sync,
                                                          const uint8_t* carry, PacketSlot* slots, int cap, int* nunits, int* lane_buf, int* ncar_in, int* ncar_out,
-                                                         int* lo_out, int64_t* counters)
+                                                         int* lo_out, int64_t* counters, int* totals)
 {
   const int lane = blockIdx.x * blockDim.x + threadIdx.x;
   if (lane >= nstreams * nsub) return;
@@ -145,6 +145,7 @@ __global__ void __launch_bounds__(64) packet_sync_kernel(PacketFrames fr, int ns
   lo_out[lane] = w.lo;
   nunits[lane] = n <= cap ? n : 0;                   // (cap holds every unit a push can give: packet.cpp)
   lane_buf[lane] = n <= cap ? nbuf : 0;
+  if (n > cap) totals[3] = 1;                        // never, by that bound; if ever, the push fails instead of losing the lane's units
   int64_t* cnt = counters + static_cast<int64_t>(lane) * kPkCntN;
   cnt[kPkCntFrames] += w.frames;
   cnt[kPkCntMisses] += w.misses;
@@ -517,7 +518,7 @@ hipError_t launch_packet_sync(const PacketFrames& fr, int nstreams, int nsub, in
                               int* lane_unit_base, int* lane_buf_base, int* totals, hipStream_t stream)
 {
   const int nlanes = nstreams * nsub;
-  packet_sync_kernel<<<(nlanes + 63) / 64, 64, 0, stream>>>(fr, nstreams, nsub, maxv, fec, loc, sync, carry, slots, cap, nunits, lane_buf, ncar_in, ncar_out, lo, counters);
+  packet_sync_kernel<<<(nlanes + 63) / 64, 64, 0, stream>>>(fr, nstreams, nsub, maxv, fec, loc, sync, carry, slots, cap, nunits, lane_buf, ncar_in, ncar_out, lo, counters, totals);
   packet_scan_kernel<<<1, 1024, 0, stream>>>(nlanes, nunits, lane_buf, lane_unit_base, lane_buf_base, totals);
   packet_jobs_kernel<<<(nlanes + 63) / 64, 64, 0, stream>>>(nlanes, slots, cap, nunits, lane_unit_base, lane_buf_base, units);
   return hipGetLastError();

@@ -143,7 +143,9 @@ extern "C" int64_t dabhip_packet_push(dabhip_packet* d, const uint8_t* frames, c
   }
   const size_t nlanes = static_cast<size_t>(ns) * nsub;
   // the units a lane can give in one push: its frames without FEC; with it, a frame per 103 of its carried and new cells (256 per ETI frame at
-  // most) and one more for the frame a first run completes
+  // most) and one more for the frame a first run completes.  (Units never share a cell, so a lane gives floor((102 + 255 maxv) / 103) at most:
+  // cap - 2 or less.  tests/host_sanitize/packet_units.cpp reaches exactly that over every rate, carried count and maxv of 1, 2, 3 and 64: at
+  // worst 159 units in 162 slots, 0.981.)  The sync kernel flags a lane that passes cap all the same.
   const int cap = std::max(maxv, (kPkCarry + maxv * 256) / kPkFrameCells + 1) + 1;
   if (!d->meta.reserve(meta.size()) || !d->loc.reserve(static_cast<size_t>(ns) * std::max(maxv, 1) * nsub) || !d->slots.reserve(nlanes * cap) || !d->units.reserve(nlanes * cap))
     return -1;
@@ -165,6 +167,7 @@ extern "C" int64_t dabhip_packet_push(dabhip_packet* d, const uint8_t* frames, c
               f.mark(2) && ok(hipMemcpyAsync(totals, d->totals.get(), sizeof totals, hipMemcpyDeviceToHost, st), "totals") &&
               ok(hipStreamSynchronize(st), "sync stage");
   if (!good) return -1;
+  if (totals[3]) { set_error("packet_push: a lane gave more units than its slots hold; the handle's state is lost"); return -1; }
   d->n_units = totals[0];
   d->n_cells = totals[1];
   d->fetched = false;

@@ -1,7 +1,9 @@
 // packet_units.cpp — the host-only parts of the packet-mode stage under ASan + UBSan, as a stand-alone program: the data-group rule
 // (csrc/packet_groups.hpp) on every drop and on groups cut short, and the FEC sync rule (csrc/packet_sync.hpp) driven the way the sync kernel's
 // lane drives it, over arrays of exactly the planned sizes: a carry of 102 cells, unit slots of the capacity packet.cpp plans for a push.  Any
-// cutting of a stream into pushes must give the same units.  Prints "ok packet-units".
+// cutting of a stream into pushes must give the same units, at 1 .. 255 cells per ETI frame.  slot_bound() holds that capacity as a property: at
+// every rate, carried count and push size, header streams built to give as many units as the rule allows, and random ones, never fill the slots.
+// Prints "ok packet-units" and the fullest slot array it saw.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -29,10 +31,13 @@ struct LaneSim {
   std::vector<uint8_t> carry = std::vector<uint8_t>(kPkCarry);   // exactly the carry buffer's cells
   std::vector<Unit> units;
   int64_t skipped = 0, losses = 0, misses = 0;
+  int last_n = 0, last_cap = 1;                                  // units and slots of the last push
 
-  void push(const uint8_t* h, int nframes, int s)
+  // break_every > 0: the stream breaks in front of new frames break_every, 2 break_every, ... of this push (packet_break, as at a frame whose STL
+  // differs)
+  void push(const uint8_t* h, int nframes, int s, int break_every = 0)
   {
-    const int cap = std::max(nframes, (kPkCarry + nframes * 256) / kPkFrameCells + 1) + 1;
+    const int cap = std::max(nframes, (kPkCarry + nframes * 256) / kPkFrameCells + 1) + 1;   // packet.cpp
     std::vector<Unit> slots(static_cast<size_t>(cap));            // exactly the slots of this push
     int n = 0;
     PacketWalkState w{};
@@ -42,15 +47,21 @@ struct LaneSim {
     const int64_t base = st.next_cell - ncar;
     const int total = ncar + nframes * s;
     std::vector<uint8_t> all(static_cast<size_t>(total));         // virtual cells: the carried, then the new
-    for (int i = 0; i < ncar; ++i) all[i] = carry[i];
-    for (int i = 0; i < nframes * s; ++i) all[ncar + i] = h[i];
+    std::copy(carry.begin(), carry.begin() + ncar, all.begin());
+    std::copy(h, h + nframes * s, all.begin() + ncar);
     const auto emit = [&](int32_t u0, int flags) {
       CHECK(n < cap);
       CHECK(u0 >= 0 && u0 + kPkFrameCells <= total);
       slots[n++] = Unit{base + u0, flags};
     };
+    const uint8_t* cells = all.data();
+    int next_break = break_every > 0 ? ncar + break_every * s : total;
     for (int nv = ncar; nv < total; ++nv) {
-      if (packet_feed(w, nv, all[nv], emit)) {
+      if (nv == next_break) {
+        packet_break(w, nv);
+        next_break += break_every * s;
+      }
+      if (packet_feed(w, nv, cells[nv], emit)) {
         CHECK(w.lo >= 0 && nv - w.lo == kPkFrameCells - 1);
         for (int u = w.lo + 1; u <= nv; ++u) CHECK(!packet_feed(w, u, all[u], emit));
       }
@@ -64,8 +75,116 @@ struct LaneSim {
     losses += w.losses;
     misses += w.misses;
     units.insert(units.end(), slots.begin(), slots.begin() + n);
+    last_n = n;
+    last_cap = cap;
   }
 };
+
+// cells of FEC frames with every header in place, from cell `phase` of a frame on
+void perfect(std::vector<uint8_t>& h, int count, int phase = 0)
+{
+  const size_t at = h.size();
+  h.resize(at + static_cast<size_t>(count));
+  uint8_t* p = h.data() + at;
+  for (int i = 0; i < count; ++i, phase = phase + 1 == kPkFrameCells ? 0 : phase + 1) p[i] = phase < kPkDataCells ? kPkNoCounter : static_cast<uint8_t>(phase - kPkDataCells);
+}
+
+struct Fullest {
+  int n = 0, cap = 1, s = 0, car = 0, maxv = 0;
+  void see(const LaneSim& l, int s_, int car_, int maxv_)
+  {
+    CHECK(l.last_n <= l.last_cap);
+    if (static_cast<int64_t>(l.last_n) * cap > static_cast<int64_t>(n) * l.last_cap) *this = Fullest{l.last_n, l.last_cap, s_, car_, maxv_};
+  }
+};
+
+// The units of one push against the slots packet.cpp plans for it (LaneSim::push CHECKs every unit against them).  A lane's units never share a
+// cell, so floor((carried + new cells) / 103) is the most any stream can give; the built streams give exactly that, the others come close.
+Fullest slot_bound()
+{
+  Fullest worst;
+  const int sizes[] = {1, 2, 3, 64};
+  const int longest = 64 * 255 + 5 * kPkFrameCells;
+  // whole frames; and a whole frame, two frames without headers, a third with headers 0 .. 8 on its cells 1 .. 9, whole frames from its cell 10 on
+  std::vector<uint8_t> whole, lost;
+  perfect(whole, longest);
+  perfect(lost, kPkFrameCells);
+  lost.insert(lost.end(), 2 * kPkFrameCells + 1, kPkNoCounter);
+  for (int i = 0; i < kPkFecCells; ++i) lost.push_back(static_cast<uint8_t>(i));
+  perfect(lost, longest);
+  // a: an unsynced lane that carries the first cells of a frame: the run of nine completes at the first possible cell, then hits back to back
+  // b: a synced lane that carries the first cells of a frame: hits back to back
+  // c: as b, the stream breaking every few frames and starting anew with a whole frame (as often as still lets a unit through)
+  // d: a synced lane with two misses that carries the first cells of a third frame without headers; a run of nine inside the 103 cells searched
+  //    again, frames with every header behind it
+  // e: as d, cut in the first of the three frames: two units from misses, the loss and the new run in one push
+  // the lanes as the push before left them, by kind and carried count
+  const int heads[5] = {0, kPkFrameCells, kPkFrameCells, 3 * kPkFrameCells, kPkFrameCells};
+  std::vector<LaneSim> before(5 * (kPkCarry + 1));
+  for (int kind = 0; kind < 5; ++kind)
+    for (int car = 0; car <= kPkCarry; ++car) {
+      LaneSim& lane = before[kind * (kPkCarry + 1) + car];
+      lane.push((kind < 3 ? whole : lost).data(), heads[kind] + car, 1);
+      CHECK(lane.st.ncar == car && lane.st.synced == (kind != 0));
+      if (kind >= 3) CHECK(lane.st.misses == (kind == 3 ? 2 : 0) && lane.units.size() == (kind == 3 ? 3u : 1u));
+    }
+  std::vector<uint8_t> h;
+  for (int s = 1; s <= 255; ++s)
+    for (int car = 0; car <= kPkCarry; ++car)
+      for (const int maxv : sizes) {
+        const int fresh = maxv * s;
+        for (int kind = 0; kind < 5; ++kind) {
+          if (maxv == 64 && kind >= 1 && (s + car) % 8) continue;             // (the long pushes but a: every eighth (rate, carried count))
+          LaneSim lane = before[kind * (kPkCarry + 1) + car];
+          const int every = (kPkFrameCells + s - 1) / s;
+          if (kind == 2) {
+            h.clear();
+            for (int f = 0; f < maxv; ++f) perfect(h, s, (f < every ? car + f * s : (f % every) * s) % kPkFrameCells);
+            lane.push(h.data(), maxv, s, every);
+          } else {
+            lane.push((kind < 3 ? whole : lost).data() + heads[kind] + car, maxv, s);
+          }
+          worst.see(lane, s, car, maxv);
+          if (kind <= 1) CHECK(lane.last_n == (car + fresh) / kPkFrameCells);   // the most there can be
+          if (kind == 2 && s >= kPkFrameCells) CHECK(lane.last_n >= maxv * (s / kPkFrameCells) - 1);
+          if (kind == 3 && car + fresh >= kPkFrameCells) CHECK(lane.losses == 1);
+          if (kind == 3 && car + fresh >= 10 + 2 * kPkFrameCells) CHECK(lane.last_n == (car + fresh - 10) / kPkFrameCells);
+          if (kind == 4 && car + fresh >= 10 + 4 * kPkFrameCells) CHECK(lane.losses == 1 && lane.misses == 2 && lane.last_n == 2 + (car + fresh - 10 - 2 * kPkFrameCells) / kPkFrameCells);
+        }
+      }
+  // random streams, 2000 per rate: frames from a random phase on, headers lost, stray headers, frames without headers up to four in a row, cells
+  // slipped; pushes of 1, 2, 3 and (one in 64) 64 frames, breaks in some; every push is held to its slots
+  uint64_t x = 88172645463325252ull;
+  const auto next = [&x]() {
+    x ^= x << 13;
+    x ^= x >> 7;
+    x ^= x << 17;
+    return x;
+  };
+  for (int s = 1; s <= 255; ++s)
+    for (int trial = 0; trial < 2000; ++trial) {
+      LaneSim lane;
+      int phase = static_cast<int>(next() % kPkFrameCells), dead = 0;
+      const uint32_t loss = 2 + static_cast<uint32_t>(next() % 80), stray = 1 + static_cast<uint32_t>(next() % 40);     // of 256, of 1024
+      for (int push = 0; push < 2; ++push) {
+        const int maxv = next() % 64 == 0 ? 64 : sizes[next() % 3];
+        h.resize(static_cast<size_t>(maxv * s));
+        uint8_t* p = h.data();
+        for (int i = 0; i < maxv * s; ++i) {
+          const uint64_t r = next();
+          if (phase == 0) dead = dead ? dead - 1 : ((r >> 50) % 9 == 0 ? 1 + static_cast<int>((r >> 56) & 3) : 0);
+          if (phase < kPkDataCells) p[i] = (r & 1023) < stray ? static_cast<uint8_t>(((r >> 10 & 15) * kPkFecCells) >> 4) : kPkNoCounter;
+          else p[i] = dead || (r >> 16 & 255) < loss ? kPkNoCounter : static_cast<uint8_t>(phase - kPkDataCells);
+          phase += 1 + ((r >> 24 & 2047) == 0 ? static_cast<int>(r >> 40 & 31) : 0);
+          if (phase >= kPkFrameCells) phase -= kPkFrameCells;
+        }
+        const int car = lane.st.ncar;
+        lane.push(h.data(), maxv, s, next() % 4 == 0 ? 1 + static_cast<int>(next() % 3) : 0);
+        worst.see(lane, s, car, maxv);
+      }
+    }
+  return worst;
+}
 
 void sync_rule()
 {
@@ -85,7 +204,8 @@ void sync_rule()
     }
     std::vector<Unit> first;
     int64_t first_skipped = 0, first_losses = 0;
-    const int plans[][2] = {{1, 1 << 20}, {1, 1}, {1, 50}, {1, 103}, {4, 7}, {8, 3}, {255, 1}, {3, 40}};
+    const int plans[][2] = {{1, 1 << 20}, {1, 1}, {1, 50}, {1, 103}, {4, 7}, {8, 3}, {255, 1}, {3, 40}, {9, 1}, {9, 5}, {16, 2}, {17, 1}, {17, 64}, {102, 1},
+                            {102, 3}, {103, 1}, {103, 2}, {104, 1}, {104, 64}, {206, 1}, {206, 2}, {251, 1}, {251, 64}};
     for (const auto& plan : plans) {
       const int s = plan[0], chunk = plan[1];
       const int nframes = static_cast<int>(h.size()) / s;
@@ -197,6 +317,7 @@ int main()
 {
   sync_rule();
   group_rule();
-  std::printf("ok packet-units\n");
+  const Fullest w = slot_bound();
+  std::printf("ok packet-units\nfullest %d of %d slots: %d cells per frame, %d carried, %d frames\n", w.n, w.cap, w.s, w.car, w.maxv);
   return 0;
 }

@@ -236,6 +236,15 @@ def sync_streams(seed=7):
     return out
 
 
+def sent_whole(cells, s, seed=1):
+    """cells with good FEC frames behind them, up to whole ETI frames of s cells: frames_of_cells() then sends every cell given (the frames added
+    change the units a stream gives, not its misses, losses or skipped cells)."""
+    src = TableSource(np.random.default_rng(seed))
+    more = np.concatenate([m.fec_frame(src.unit()) for _ in range(s // m.FRAME_CELLS + 2)])
+    ncells = len(cells) // m.CELL
+    return np.concatenate([cells, more[:(-ncells % s) * m.CELL]])
+
+
 # ---- ETI frames ------------------------------------------------------------------------------------------------------------------------------------
 def frames_of_cells(fct0, subs, nframes=None):
     """subs = [(SubChId, s, cells as one byte array)] -> ETI frames carrying s cells of each per frame, as many as the shortest allows (cells left

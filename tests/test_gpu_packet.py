@@ -1,7 +1,7 @@
 """The packet-mode kernels (k_packet.hip through Packet.push) against the model of packet_model.py, bit for bit: records, useful bytes and
 statistics.  ETI frames are built by hand from the model and the crafted classes of packet_cases.py: Reed-Solomon words at the decoder's edges,
 cell streams at the edges of the FEC sync rule, broken streams, the walk's edges; with and without FEC in one handle; 1, 4 and 8 cells per ETI
-frame; 5, 6 and 22 FEC frames per lane (60, 72 and 264 code words: across the wave and workgroup edges); every way frames arrive and any cutting
+frame (9 to 251, more than 1024 lanes and pushes of 64 frames: test_gpu_packet_scale.py); 5, 6 and 22 FEC frames per lane (60, 72 and 264 code words: across the wave and workgroup edges); every way frames arrive and any cutting
 into pushes, pushes of 0 and 1 frame included; and the data groups of the library's host rule against what the source of the packets sent."""
 import os
 import subprocess

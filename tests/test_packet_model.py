@@ -1,7 +1,8 @@
 """The packet-mode model (tests/packet_model.py) on the CPU: its RS(204,188) against long division and against the independent decoder of
 rs204_reference.py on every crafted word, the FEC sync rule, the walk and the data-group rule on crafted inputs whose results the construction
 fixes, independence of how a stream is cut into pushes, the host rule of the library (dabhip_packet_groups_*) against the model's, and
-tests/host_sanitize/packet_units.cpp, a stand-alone program, under ASan + UBSan."""
+tests/host_sanitize/packet_units.cpp, a stand-alone program, under ASan + UBSan: the sync rule at every rate of RATES and the bound on a push's
+units per lane (packet.cpp) as a property over every rate, carried count and push size."""
 import os
 import subprocess
 
@@ -85,26 +86,32 @@ def _run(lane, frames, chunk=None):
 
 
 SYNC = cs.sync_streams()
+# 9: the second group of eight headers; 102, 103, 104: a frame to an ETI frame, less and more; 206, 251: two frames and more to an ETI frame, 251 the
+# most that fits behind the FIC bytes
+RATES = (9, 16, 17, 102, 103, 104, 206, 251)
+RATE_PLANS = tuple((s, chunk) for s in RATES for chunk in (None, 1))
 
 
 @pytest.mark.parametrize("cls", sorted(SYNC))
 def test_sync_rule_on_crafted_streams(cls):
     cells, want = SYNC[cls]
     results = []
-    for s, chunk in ((1, None), (1, 50), (4, 7), (8, 1)):
-        frames = cs.frames_of_cells(3, [(7, s, cells)])
+    for s, chunk in ((1, None), (1, 50), (4, 7), (8, 1)) + RATE_PLANS:
+        frames = cs.frames_of_cells(3, [(7, s, cs.sent_whole(cells, s) if s > 8 else cells)])
         lane = m.Lane(7, True)
         recs, data = _run(lane, frames, chunk)
         for k, v in want.items():
             if s == 1 or k != "units":                            # (with s > 1 the cells left over at the end may cost the last frame)
                 assert lane.stats[k] == v, (cls, s, chunk, k, lane.stats)
+            elif s > 8:                                           # (every cell was sent, and good frames behind them)
+                assert lane.stats[k] >= v, (cls, s, chunk, k, lane.stats)
         assert lane.stats["rs_failed_codewords"] == 0 and lane.stats["rs_corrected_bytes"] == 0
         sent = len(frames) * s
         assert lane.stats["units"] * 103 + lane.stats["cells_skipped"] + len(lane.cells) == sent, (cls, s, chunk)
         assert len(lane.cells) <= m.CARRY
-        if s == 1:
+        if s == 1 or s > 8:
             results.append((recs, [bytes(d) for d in data], lane.stat_list()))
-    assert results[0] == results[1]
+    assert all(a == b for a, b in zip(results[0::2], results[1::2])) and len(results) == 2 + len(RATE_PLANS)    # any cut gives the same
     if cls == "slip of 11 cells":
         assert lane.stats["units"] >= 6 and lane.stats["cells_skipped"] >= 92
 
@@ -275,14 +282,17 @@ def test_host_rule_under_sanitizers():
     here = os.path.join(ROOT, "tests", "host_sanitize")
     os.makedirs(os.path.join(here, "build"), exist_ok=True)
     exe = os.path.join(here, "build", "packet_units_asan")
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+    build = subprocess.run(["g++", "-std=c++17", "-O2", "-g", "-fno-omit-frame-pointer", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                             os.path.join(here, "packet_units.cpp"), "-o", exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert build.returncode == 0, build.stdout[-3000:]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1 abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=300)
     assert run.returncode == 0, (run.stdout + run.stderr)[-4000:]
     assert "Sanitizer" not in run.stderr, run.stderr[-4000:]
-    assert run.stdout.split() == ["ok", "packet-units"]
+    out = run.stdout.split("\n")
+    assert out[0].split() == ["ok", "packet-units"]
+    # the fullest slot array of the property: the most a push of 64 frames can give, floor((102 + 64 x 255) / 103), in the 162 slots planned for it
+    assert out[1].startswith("fullest 159 of 162 slots: 255 cells per frame,") and out[1].endswith("64 frames"), out[1]
 
 
 # ---- the modulator's packet-mode content ----------------------------------------------------------------------------------------------------------
