@@ -60,7 +60,8 @@ class SynthCfg(C.Structure):
                 ("fib_patch_len", C.c_int32), ("fib_patch_from_cif", C.c_int32), ("fib_patch", C.c_uint8 * 32),
                 ("reconf", ReconfCfg * 2), ("channel", ChannelCfg), ("dabplus_slots", C.c_uint64), ("dabplus_phase", C.c_int32),
                 ("tii_phase", C.c_int32), ("tii", TiiCfg * 4),
-                ("packet_slots", C.c_uint64), ("packet_fec_slots", C.c_uint64), ("packet_phase", C.c_int32), ("packet_pad", C.c_int32)]
+                ("packet_slots", C.c_uint64), ("packet_fec_slots", C.c_uint64), ("packet_phase", C.c_int32), ("packet_pad", C.c_int32),
+                ("ts_slots", C.c_uint64), ("ts_phase", C.c_int32), ("ts_pad", C.c_int32)]
 
     def set_tii(self, combs, phase=0):
         """The null symbol of every TF with (tf + phase) even carries these combs: up to four (main_id, sub_id, level_db); none = off."""
@@ -206,6 +207,14 @@ _SIGNATURES = {
     "dabhip_dabplus_au_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, u8p, C.c_int64]),
     "dabhip_dabplus_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "dabhip_dabplus_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
+    "dabhip_synth_ts_word": (C.c_int, [C.POINTER(SynthCfg), C.c_int, C.c_int64, u8p]),
+    "dabhip_ts_create": (C.c_void_p, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
+    "dabhip_ts_destroy": (None, [C.c_void_p]),
+    "dabhip_ts_push": (C.c_int64, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "dabhip_ts_records": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
+    "dabhip_ts_data": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, u8p, C.c_int64]),
+    "dabhip_ts_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "dabhip_ts_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
     "dabhip_packet_create": (C.c_void_p, [C.c_int, C.c_int, C.POINTER(C.c_int32), u8p, C.c_int]),
     "dabhip_packet_destroy": (None, [C.c_void_p]),
     "dabhip_packet_push": (C.c_int64, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
@@ -507,6 +516,13 @@ def synth_packet_cells(cfg, slot, cell_index, ncells):
     """ncells transmitted cells of a packet_slots slot from cell_index on (cells counted from logical CIF 0's first): an (ncells, 24) array."""
     buf = np.zeros((ncells, 24), dtype=np.uint8)
     _need(lib().dabhip_synth_packet_cells(C.byref(cfg), slot, cell_index, ncells, _p(buf), buf.size) == buf.size, "synth_packet_cells")
+    return buf
+
+
+def synth_ts_word(cfg, slot, n):
+    """Code word n (any sign) of a ts_slots slot before the interleaver: 188 TS bytes and 16 parity bytes."""
+    buf = np.zeros(204, dtype=np.uint8)
+    _need(lib().dabhip_synth_ts_word(C.byref(cfg), slot, int(n), _p(buf)) == 204, "synth_ts_word")
     return buf
 
 
@@ -999,6 +1015,73 @@ class Packet(_Handle):
     def stage_ms(self):
         """GPU time of the last push per stage: {"locate", "sync", "gather", "rs", "cand", "walk", "carry"} in ms."""
         return _stage_ms(lib().dabhip_packet_stage_ms, self._h, 7)
+
+
+# ---- MPEG-2 transport stream (dabhip.h: dabhip_ts_*) ------------------------------------------------------------------
+TS_REC = np.dtype([("pos", "<i8"), ("pid", "<u2"), ("continuity", "u1"), ("flags", "u1"), ("corrected", "u1"), ("pad", "u1", (3,))])
+assert TS_REC.itemsize == 16
+TS_FROM_MISS, TS_RS_FAILED, TS_TEI, TS_PUSI, TS_BAD_SYNC = 1, 2, 4, 8, 16
+TS_STATS = ("packets", "from_missed_slots", "sync_losses", "bytes_skipped", "rs_corrected_bytes", "rs_failed_words", "bad_sync_packets", "null_packets")
+TS_STAGES = ("locate", "runs", "sync", "jobs", "gather", "syndrome", "decode", "parse", "carry")
+
+
+class Ts(_Handle):
+    """MPEG-2 TS packets out of ETI frames on the GPU (dabhip_ts_*): slot sync on the 0x47 bytes, the byte de-interleaver and RS(204,188), for
+    nstreams streams and the sub-channels subch_ids of each.  State (sync, at most 2447 bytes per lane) carries from push to push."""
+    _destroy = "dabhip_ts_destroy"
+
+    def __init__(self, nstreams, subch_ids, device=0):
+        self.nstreams, self.subch_ids = int(nstreams), [int(i) for i in subch_ids]
+        ids = (C.c_int32 * len(self.subch_ids))(*self.subch_ids)
+        self._h = lib().dabhip_ts_create(device, self.nstreams, ids, len(self.subch_ids))
+        _need(self._h, "ts_create")
+
+    def push(self, frames, counts=None):
+        """frames as Packet.push takes them.  Returns the packets of this push."""
+        if isinstance(frames, tuple):
+            ptr, counts = frames
+            src, on_dev = C.c_void_p(ptr), 1
+        else:
+            if isinstance(frames, list):
+                counts = [np.asarray(f).size // ETI_BYTES for f in frames]
+                arr = np.ascontiguousarray(np.concatenate([np.asarray(f, dtype=np.uint8).reshape(-1) for f in frames]) if frames else np.zeros(0, np.uint8))
+            else:
+                arr = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+                if counts is None:
+                    _need(self.nstreams == 1, "ts_push: counts needed for several streams")
+                    counts = [arr.size // ETI_BYTES]
+            self._keep = arr
+            src, on_dev = C.c_void_p(arr.ctypes.data), 0
+        cnt = (C.c_int64 * self.nstreams)(*[int(c) for c in counts])
+        n = lib().dabhip_ts_push(self._h, src, cnt, on_dev)
+        _need(n >= 0, "ts_push")
+        return n
+
+    def records(self, stream=0, sub=0):
+        """Records of the last push's packets of (stream, sub-channel index): a TS_REC array."""
+        n = lib().dabhip_ts_records(self._h, stream, sub, None, 0)
+        _need(n >= 0, "ts_records")
+        out = np.zeros(n, dtype=TS_REC)
+        _need(lib().dabhip_ts_records(self._h, stream, sub, out.ctypes.data, n) == n, "ts_records")
+        return out
+
+    def data(self, stream=0, sub=0):
+        """Their bytes: an (n, 188) array, failed words as received."""
+        n = lib().dabhip_ts_data(self._h, stream, sub, None, 0)
+        _need(n >= 0, "ts_data")
+        out = np.zeros(n, dtype=np.uint8)
+        _need(lib().dabhip_ts_data(self._h, stream, sub, _p(out), n) == n, "ts_data")
+        return out.reshape(-1, 188)
+
+    def stats(self, stream=0, sub=0):
+        """Counters since creation, in TS_STATS order (int64 array of 8)."""
+        c = np.zeros(8, dtype=np.int64)
+        _need(lib().dabhip_ts_stats(self._h, stream, sub, c.ctypes.data_as(C.POINTER(C.c_int64))) == 0, "ts_stats")
+        return c
+
+    def stage_ms(self):
+        """GPU time of the last push per stage: TS_STAGES in ms."""
+        return _stage_ms(lib().dabhip_ts_stage_ms, self._h, len(TS_STAGES))
 
 
 class PacketGroups(_Handle):

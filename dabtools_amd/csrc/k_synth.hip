@@ -172,6 +172,7 @@ int synth_generate_device(const dabhip_synth_cfg* cfgs, int nstreams, int ntf, u
     if (!synth_validate(cfgs[i])) return -1;
     if (synth_channel_active(cfgs[i])) { set_error("synth_generate_device: the channel stages (dabhip_channel_cfg) exist in the host generator only"); return -1; }
     if (synth_tii_active(cfgs[i])) { set_error("synth_generate_device: TII combs (dabhip_synth_cfg::tii) exist in the host generator only"); return -1; }
+    if (cfgs[i].ts_slots) { set_error("synth_generate_device: MPEG-2 TS slots (dabhip_synth_cfg::ts_slots) exist in the host generator only"); return -1; }
   }
   if (!ok(hipSetDevice(device), "hipSetDevice")) return -1;
 

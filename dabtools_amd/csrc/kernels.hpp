@@ -11,6 +11,7 @@
 #include "device_types.hpp"
 #include "launch_limits.hpp"
 #include "packet.hpp"
+#include "ts.hpp"
 
 namespace dabhip {
 
@@ -222,6 +223,30 @@ hipError_t launch_packet_carry(const PacketFrames& fr, int nlanes, const PacketL
                                const int* ncar_out, const int* lo, uint8_t* carry_next, hipStream_t stream);
 size_t packet_gf_table_bytes();
 void packet_gf_table_fill(uint8_t* out);
+
+// k_ts.hip: MPEG-2 TS packets out of ETI frames (ts.hpp has the types, ts_sync.hpp the sync rule and the position map, dabhip.h the rules in
+// words).  locate (+ layout): the sub-channels of every (stream, new frame) into loc [nstreams][maxv][nsub], every lane's virtual positions and
+// its words in the run-flag buffer (flag_cap words; totals zeroed before); runs: a bit per position, "a run of five starts here"; sync: a wave per
+// lane, its units into at most cap slots; jobs (scan + jobs): the push's unit list, totals[0] = units; gather: the units' 204 bytes into the word
+// buffer (ts_word_byte); syndrome / decode: the code words, corrected in place (cw_status: symbols corrected, 0xff = failed; syn: 16 bytes of
+// scratch per code word; the tables are packet_gf_table_fill's); parse: a record and 188 bytes per unit, the counters; carry: every lane's
+// unconsumed bytes (at most 2447).
+hipError_t launch_ts_locate(const PacketFrames& fr, const int32_t* subch, int nsub, int nstreams, int maxv, TsLoc* loc, const TsSync* sync, TsLane* lanes, int flag_cap,
+                            int* totals, hipStream_t stream);
+hipError_t launch_ts_runs(const PacketFrames& fr, int nlanes, int nsub, int maxv, int per_lane, const TsLoc* loc, const TsLane* lanes, const uint8_t* carry,
+                          const int* totals, uint64_t* flags, hipStream_t stream);
+hipError_t launch_ts_sync(const PacketFrames& fr, int nlanes, int nsub, int maxv, const TsLoc* loc, TsSync* sync, TsLane* lanes, const uint8_t* carry,
+                          const uint64_t* flags, TsSlot* slots, int cap, int* nunits, int64_t* counters, int* totals, hipStream_t stream);
+hipError_t launch_ts_jobs(int nlanes, const TsSlot* slots, int cap, const int* nunits, int* lane_unit_base, const TsSync* sync, const TsLane* lanes, TsUnit* units,
+                          int64_t unit_cap, int* totals, hipStream_t stream);
+hipError_t launch_ts_gather(const PacketFrames& fr, const TsUnit* units, const int* totals, int64_t nunits, const TsLoc* loc, int maxv, int nsub, const uint8_t* carry,
+                            const TsLane* lanes, uint8_t* words, hipStream_t stream);
+hipError_t launch_ts_syndrome(const int* totals, int64_t nunits, const uint8_t* gf_tables, const uint8_t* words, uint8_t* cw_status, uint32_t* syn, hipStream_t stream);
+hipError_t launch_ts_decode(const int* totals, int64_t nunits, const uint8_t* gf_tables, uint8_t* words, uint8_t* cw_status, const uint32_t* syn, hipStream_t stream);
+hipError_t launch_ts_parse(const TsUnit* units, const int* totals, int64_t nunits, const uint8_t* words, const uint8_t* cw_status, dabhip_ts_rec* recs, uint8_t* data,
+                           int64_t* counters, hipStream_t stream);
+hipError_t launch_ts_carry(const PacketFrames& fr, int nlanes, const TsLoc* loc, int maxv, int nsub, const uint8_t* carry, const TsLane* lanes, const int* totals,
+                           uint8_t* carry_next, hipStream_t stream);
 
 // k_probe.hip: streaming rates of this device (fill, copy, K2's read/write mix) in GB/s -- bench.py's yardstick beside the K2 figure
 int stream_ceiling(int device, size_t bytes, int reps, double* gbs);

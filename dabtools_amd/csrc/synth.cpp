@@ -13,6 +13,7 @@
 #include "dab_tables.hpp"
 #include "dabplus.hpp"
 #include "packet_sync.hpp"
+#include "ts_sync.hpp"
 #include "synth.hpp"
 #include "tii_detect.hpp"
 
@@ -31,7 +32,7 @@ inline uint64_t mix64(uint64_t z)
 }
 inline uint64_t key(uint64_t seed, uint64_t a, uint64_t b, uint64_t c) { return mix64(mix64(mix64(seed ^ mix64(a)) + b) + c); }
 
-enum : uint64_t { kDomPayload = 1, kDomFiller = 2, kDomNoise = 3, kDomDabPlus = 4, kDomPacket = 5 };
+enum : uint64_t { kDomPayload = 1, kDomFiller = 2, kDomNoise = 3, kDomDabPlus = 4, kDomPacket = 5, kDomTs = 6 };
 
 SubChannel to_subchannel(const dabhip_subch_cfg& c)
 {
@@ -108,6 +109,13 @@ bool validate(const dabhip_synth_cfg& cfg)
       if (r.at_cif != 0) { set_error("synth: packet_slots cannot be combined with reconfigurations"); return false; }
     for (int k = 0; k < cfg.nsub; ++k)
       if ((cfg.packet_slots >> k & 1) && to_subchannel(cfg.sub[k]).bitrate % 8) { set_error("synth: a packet-mode slot needs a multiple of 8 kbit/s"); return false; }
+  }
+  if (cfg.ts_slots) {
+    if (cfg.nsub < 64 && (cfg.ts_slots >> cfg.nsub)) { set_error("synth: ts_slots names a slot past nsub"); return false; }
+    if (cfg.ts_slots & cfg.dabplus_slots) { set_error("synth: a slot cannot be both an MPEG-2 TS and a DAB+ slot"); return false; }
+    if (cfg.ts_slots & cfg.packet_slots) { set_error("synth: a slot cannot be both an MPEG-2 TS and a packet-mode slot"); return false; }
+    for (const dabhip_reconf_cfg& r : cfg.reconf)
+      if (r.at_cif != 0) { set_error("synth: ts_slots cannot be combined with reconfigurations"); return false; }
   }
   int prev = 0;
   for (const dabhip_reconf_cfg& r : cfg.reconf) {
@@ -417,6 +425,80 @@ void packet_cells(const dabhip_synth_cfg& cfg, int slot, int s, int64_t c, int n
   }
 }
 
+// ---- MPEG-2 TS (ETSI TS 102 427; dabhip.h: dabhip_ts has the formats) --------------------------------------------------------------------------
+// Code word n of a TS slot.  Words go in blocks of 8 with a fixed mix of the slot's two or three PIDs and null packets, shuffled by the block's
+// key: so the continuity counter of a PID is a closed form of n (n may be negative) and needs no history.
+void ts_word(const dabhip_synth_cfg& cfg, int slot, int64_t n, uint8_t* out)
+{
+  const uint64_t sk = key(cfg.seed, kDomTs, 64 + static_cast<uint64_t>(slot), 0);
+  const bool three = sk & 1;
+  const int base = 0x20 + static_cast<int>((sk >> 8) & 0xfff);
+  static const int8_t mix2[8] = {0, 0, 0, 1, 1, 1, -1, -1}, mix3[8] = {0, 0, 0, 1, 1, 2, 2, -1};
+  int8_t order[8];
+  std::memcpy(order, three ? mix3 : mix2, 8);
+  const int64_t blk = floor_div64(n, 8);
+  const int idx = static_cast<int>(n - 8 * blk);
+  for (int i = 7; i >= 1; --i) {
+    const int j = static_cast<int>(key(cfg.seed, kDomTs, 128 + static_cast<uint64_t>(slot), static_cast<uint64_t>(blk) * 8 + static_cast<uint64_t>(i)) % static_cast<uint64_t>(i + 1));
+    std::swap(order[i], order[j]);
+  }
+  const int who = order[idx];
+  const uint64_t wk = key(cfg.seed, kDomTs, static_cast<uint64_t>(slot), static_cast<uint64_t>(n));
+  int pid = kTsNullPid, cc = 0, pusi = 0;
+  if (who >= 0) {
+    int per = 0, before = 0;
+    for (int i = 0; i < 8; ++i) {
+      per += order[i] == who;
+      before += i < idx && order[i] == who;
+    }
+    pid = base + 0x101 * who;
+    cc = static_cast<int>((((blk % 16) * per + before) % 16 + 16) % 16);
+    pusi = (wk & 7) == 0;
+  }
+  out[0] = kTsSyncByte;
+  out[1] = static_cast<uint8_t>((pusi << 6) | (pid >> 8));
+  out[2] = static_cast<uint8_t>(pid & 0xff);
+  out[3] = static_cast<uint8_t>(0x10 | cc);                                // payload only
+  for (int i = 4; i < kTsData; i += 8) {
+    const uint64_t v = key(cfg.seed, kDomTs, wk, static_cast<uint64_t>(i));
+    for (int b = 0; b < 8 && i + b < kTsData; ++b) out[i + b] = static_cast<uint8_t>(v >> (8 * b));
+  }
+  const uint8_t* g = rs204_generator();
+  uint8_t rem[kPkRoots] = {0};
+  for (int c = 0; c < kTsData; ++c) {
+    const uint8_t fb = out[c] ^ rem[0];
+    for (int q = 0; q < kPkRoots - 1; ++q) rem[q] = rem[q + 1] ^ gf_mul(fb, g[q + 1]);
+    rem[kPkRoots - 1] = gf_mul(fb, g[kPkRoots]);
+  }
+  std::memcpy(out + kTsData, rem, kPkRoots);
+}
+
+// n bytes of a TS slot from stream position x on (bytes counted from logical CIF 0's first): the byte at x is byte k = (x - ts_phase) mod 204 of
+// the word whose slot started 204 (k mod 12) bytes before x - k
+void ts_bytes(const dabhip_synth_cfg& cfg, int slot, int64_t x, int n, uint8_t* out)
+{
+  struct Entry {
+    uint64_t seed = 0;
+    int slot = -1;
+    int64_t n = 0;
+    uint8_t word[kTsSlot];
+  };
+  thread_local Entry cache[64];
+  for (int i = 0; i < n; ++i, ++x) {
+    const int64_t rel = x - cfg.ts_phase;
+    const int k = static_cast<int>(rel - kTsSlot * floor_div64(rel, kTsSlot));
+    const int64_t w = (rel - k) / kTsSlot - k % kTsBranches;
+    Entry& e = cache[static_cast<uint64_t>(w) & 63];
+    if (e.slot != slot || e.seed != cfg.seed || e.n != w) {
+      ts_word(cfg, slot, w, e.word);
+      e.seed = cfg.seed;
+      e.slot = slot;
+      e.n = w;
+    }
+    out[i] = e.word[k];
+  }
+}
+
 void payload_bytes(const dabhip_synth_cfg& cfg, int cif, int slot, uint8_t* out, int n)
 {
   if (cfg.dabplus_slots >> slot & 1) {                     // n = 24 s
@@ -426,6 +508,10 @@ void payload_bytes(const dabhip_synth_cfg& cfg, int cif, int slot, uint8_t* out,
   }
   if (cfg.packet_slots >> slot & 1) {                      // n = 24 s
     packet_cells(cfg, slot, n / 24, static_cast<int64_t>(cif) * (n / 24), n / 24, out);
+    return;
+  }
+  if (cfg.ts_slots >> slot & 1) {
+    ts_bytes(cfg, slot, static_cast<int64_t>(cif) * n, n, out);
     return;
   }
   for (int i = 0; i < n; i += 8) {
@@ -773,7 +859,7 @@ extern "C" int dabhip_synth_payload(const dabhip_synth_cfg* cfg, int cif_index, 
   if (!cfg) { set_error("synth_payload: bad slot"); return -1; }
   const Multiplex mux = multiplex_at(*cfg, cif_index, false);
   if (slot < 0 || slot >= mux.nsub) { set_error("synth_payload: bad slot"); return -1; }
-  if ((cfg->dabplus_slots || cfg->packet_slots || cfg->packet_fec_slots) && !validate(*cfg)) return -1;
+  if ((cfg->dabplus_slots || cfg->packet_slots || cfg->packet_fec_slots || cfg->ts_slots) && !validate(*cfg)) return -1;
   const int n = to_subchannel(mux.sub[slot]).bitrate * 3;
   if (cap < n) { set_error("synth_payload: buffer too small"); return -1; }
   payload_bytes(*cfg, cif_index, slot, out, n);
@@ -840,6 +926,17 @@ extern "C" int dabhip_synth_packet_group(const dabhip_synth_cfg* cfg, int slot, 
   }
   set_error("synth_packet_group: no such group");
   return -1;
+}
+
+extern "C" int dabhip_synth_ts_word(const dabhip_synth_cfg* cfg, int slot, int64_t n, uint8_t* out204)
+{
+  if (!cfg || !out204 || slot < 0 || slot >= cfg->nsub || slot >= 64 || !(cfg->ts_slots >> slot & 1)) {
+    set_error("synth_ts_word: not an MPEG-2 TS slot");
+    return -1;
+  }
+  if (!validate(*cfg)) return -1;
+  ts_word(*cfg, slot, n, out204);
+  return kTsSlot;
 }
 
 extern "C" int dabhip_synth_fibs(const dabhip_synth_cfg* cfg, int cif_index, uint8_t* out96)

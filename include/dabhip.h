@@ -691,6 +691,64 @@ int64_t dabhip_packet_groups_get(const dabhip_packet_groups *g, int64_t i, dabhi
 /* Counters since creation: groups completed, groups dropped, orphan packets, groups whose CRC failed.  Returns 0. */
 int dabhip_packet_groups_stats(const dabhip_packet_groups *g, int64_t *counters4);
 
+/* ---- MPEG-2 transport stream (ETSI TS 102 427; T-DMB video, TS 102 428, rides on it) ---------- */
+/* A stateful consumer of ETI frames that extracts the MPEG-2 TS packets of stream-mode sub-channels on the GPU: slot sync on the 0x47 bytes,
+ * the convolutional byte de-interleaver, RS(204,188).  Off unless asked for, and handled like dabhip_packet: frames are pushed stream by stream,
+ * the state of every (stream, sub-channel) carries from push to push (at most 2447 bytes each), and any cutting of a stream into pushes gives
+ * the same records.  These rules were written from the standard, not from a broadcast recording.
+ *
+ * Byte stream.  The byte stream of a (stream, SubChId) is the sub-channel's payload (8 STL bytes per ETI frame) of its frames, in order; if the
+ * STC lists the id twice, the first entry counts.  A frame that lacks the id, or lists it with STL 0 or with a payload that runs past byte 6144,
+ * breaks the stream and gives no bytes; a frame whose STL differs from the stream's breaks it and starts the next one.  A break drops sync
+ * (counted as a sync loss when there was sync) and every byte not consumed yet (counted as skipped).  Positions count the bytes of the
+ * (stream, sub-channel) since creation and go on counting across breaks.  Any STL is legal.
+ *
+ * Code word: 204 bytes, 188 TS bytes and then 16 parity bytes, byte k the coefficient of x^(203 - k); GF(256) by 0x11D, alpha = 2, generator
+ * prod (x + alpha^i), i = 0..15 (the code of the enhanced packet mode above).  Decoding is bounded-distance: a word within distance 8 of a code
+ * word is corrected, any other is left as received and flagged.
+ *
+ * Interleaver (I = 12, M = 17): byte k of a code word travels in branch k mod 12, delayed by 204 (k mod 12) bytes, so byte 0, the 0x47, is never
+ * delayed.  If the slot of a code word starts at stream position P, its byte k lies at P + k + 204 (k mod 12); the word needs the 2448 bytes
+ * P .. P + 2447.
+ *
+ * Sync, per (stream, sub-channel); `end` is the position one past the last byte on hand.  Unsynced, searching from q: with p the smallest
+ * position >= q such that p + 816 < end and the five bytes at p + 204 i (i = 0..4) are all 0x47, bytes q .. p - 1 are skipped and the lane is
+ * synced with its next slot at p and 0 misses; if there is none, the bytes below max(q, end - 816) are skipped and the search waits there for
+ * the next push.  Synced with the next slot at P: if P + 2448 > end, wait (the bytes from P on carry to the next push).  Otherwise the slot is a
+ * hit when the byte at P is 0x47 (the miss count becomes 0) and a miss when it is not (the count grows by 1).  On the 3rd consecutive miss sync is
+ * lost and no packet is taken: one byte is skipped and the search resumes at P + 1 with the slot's other bytes unconsumed.  In every other case,
+ * a second miss included, the word is gathered and RS-decoded and gives one record, flagged FROM_MISS on a miss; then P += 204. */
+typedef struct dabhip_ts dabhip_ts;
+#define DABHIP_TS_FROM_MISS 1       /* from a slot whose first byte was not 0x47 */
+#define DABHIP_TS_RS_FAILED 2       /* no code word within distance 8: the bytes are as received */
+#define DABHIP_TS_TEI 4             /* transport_error_indicator, as decoded */
+#define DABHIP_TS_PUSI 8            /* payload_unit_start_indicator, as decoded */
+#define DABHIP_TS_BAD_SYNC 16       /* byte 0 after decoding is not 0x47 */
+typedef struct dabhip_ts_rec {      /* one packet of the last push */
+  int64_t pos;                      /* position of its slot's first byte among the bytes of its (stream, sub-channel) since creation */
+  uint16_t pid;
+  uint8_t continuity;
+  uint8_t flags;                    /* DABHIP_TS_* */
+  uint8_t corrected;                /* bytes the RS decoder corrected, 0..8 */
+  uint8_t pad[3];
+} dabhip_ts_rec;
+/* nsub SubChIds, the same for every stream.  NULL when there is no GPU (dabhip_last_error). */
+dabhip_ts *dabhip_ts_create(int device, int nstreams, const int32_t *subch_ids, int nsub);
+void dabhip_ts_destroy(dabhip_ts *d);
+/* counts[s] ETI frames of stream s, stream after stream in `frames`, in DEVICE memory when on_device != 0 (no alignment needed), else in host
+ * memory.  Returns the packets of this call, <0 on error. */
+int64_t dabhip_ts_push(dabhip_ts *d, const uint8_t *frames, const int64_t *counts, int on_device);
+/* The packets of the last push of one (stream, sub-channel index), in order: copies min(n, cap) records, returns n. */
+int64_t dabhip_ts_records(const dabhip_ts *d, int stream, int sub, dabhip_ts_rec *out, int64_t cap);
+/* Their 188 bytes each, packet after packet, failed words as received (whole packets, cap bytes at most); returns the byte count. */
+int64_t dabhip_ts_data(const dabhip_ts *d, int stream, int sub, uint8_t *dst, int64_t cap);
+/* Counters since creation: packets, packets from missed slots, sync losses, bytes skipped, RS corrected bytes, RS failed words, BAD_SYNC packets,
+ * null packets (PID 0x1FFF).  Returns 0, <0 on error. */
+int dabhip_ts_stats(const dabhip_ts *d, int stream, int sub, int64_t *counters8);
+/* GPU time of the last push in ms, stage by stage (names: "locate", "runs", "sync", "jobs", "gather", "syndrome", "decode", "parse", "carry");
+ * returns the count. */
+int dabhip_ts_stage_ms(const dabhip_ts *d, const char **names, float *ms, int cap);
+
 /* ---- ingest stage: other sample formats and rates -> the canonical cu8 at 2.048 Msps ------------------------------
  * Off unless asked for: a stateful object in front of the decoder that turns nstreams streams of cu8 / cs8 / cs16 / cf32 IQ (I first, little-endian)
  * at an integer sample rate Fin into cu8 at 2,048,000 samples/s in device memory, ready for dabhip_engine_decode(..., on_device = 1) and
@@ -1014,6 +1072,15 @@ typedef struct dabhip_synth_cfg {
   uint64_t packet_fec_slots;
   int32_t packet_phase;
   int32_t packet_pad;
+  /* MPEG-2 TS content (see "MPEG-2 transport stream" above; all zero = off, byte-identical captures): bit k of ts_slots set = slot k carries an
+   * interleaved transport stream instead of keyed random bytes.  The slot of code word n starts at byte 204 n + ts_phase, bytes counted from
+   * logical CIF 0's first (n may be negative: the interleaver has run forever, so every byte belongs to a word).  Each word is made from the
+   * slot's key: 0x47, two or three PIDs and null packets in between, a continuity counter per PID, a keyed payload, the
+   * payload_unit_start_indicator now and then; then the parity.  Any bit rate; refused on a DAB+ slot, on a packet-mode slot, on a slot past
+   * nsub, and together with reconfigurations.  Host generator only: dabhip_synth_generate_device refuses a configuration with ts_slots set. */
+  uint64_t ts_slots;
+  int32_t ts_phase;
+  int32_t ts_pad;
 } dabhip_synth_cfg;
 
 /* preset 0: 12 sub-channels, 1136 kbit/s, 862 CU (the benchmark mix); 1: 4 light sub-channels. */
@@ -1037,6 +1104,9 @@ int dabhip_synth_dabplus_superframe(const dabhip_synth_cfg *cfg, int sf_index, i
 int dabhip_synth_packet_addresses(const dabhip_synth_cfg *cfg, int slot, int32_t *out3);
 int dabhip_synth_packet_cells(const dabhip_synth_cfg *cfg, int slot, int64_t cell_index, int ncells, uint8_t *out, int cap);
 int dabhip_synth_packet_group(const dabhip_synth_cfg *cfg, int slot, int address, int n, uint8_t *out, int cap);
+/* Truth of a ts_slots slot, straight from the generator (not through dabhip_ts): code word n (any sign), 188 TS bytes and 16 parity bytes,
+ * before the interleaver.  Returns 204, <0 on error. */
+int dabhip_synth_ts_word(const dabhip_synth_cfg *cfg, int slot, int64_t n, uint8_t *out204);
 /* Device-side modulator (needs a GPU): the ensembles cfgs[0..nstreams) modulated on `device`
  * straight into DEVICE buffers iq[i] of dabhip_synth_bytes(&cfgs[i], ntf) bytes each.  The bit content comes from the
  * same generator as dabhip_synth_generate; samples may differ from the host generator's by one LSB where fp32 and
