@@ -61,7 +61,8 @@ class SynthCfg(C.Structure):
                 ("reconf", ReconfCfg * 2), ("channel", ChannelCfg), ("dabplus_slots", C.c_uint64), ("dabplus_phase", C.c_int32),
                 ("tii_phase", C.c_int32), ("tii", TiiCfg * 4),
                 ("packet_slots", C.c_uint64), ("packet_fec_slots", C.c_uint64), ("packet_phase", C.c_int32), ("packet_pad", C.c_int32),
-                ("ts_slots", C.c_uint64), ("ts_phase", C.c_int32), ("ts_pad", C.c_int32)]
+                ("ts_slots", C.c_uint64), ("ts_phase", C.c_int32), ("ts_pad", C.c_int32),
+                ("si_mode", C.c_int32), ("si_pad", C.c_int32)]
 
     def set_tii(self, combs, phase=0):
         """The null symbol of every TF with (tf + phase) even carries these combs: up to four (main_id, sub_id, level_db); none = off."""
@@ -215,6 +216,18 @@ _SIGNATURES = {
     "dabhip_ts_data": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, u8p, C.c_int64]),
     "dabhip_ts_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "dabhip_ts_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
+    "dabhip_dir_create": (C.c_void_p, [C.c_int, C.c_int]),
+    "dabhip_dir_destroy": (None, [C.c_void_p]),
+    "dabhip_dir_push": (C.c_int64, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "dabhip_dir_ensemble": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "dabhip_dir_subchannels": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "dabhip_dir_services": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "dabhip_dir_packet_components": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "dabhip_dir_complete": (C.c_int, [C.c_void_p, C.c_int]),
+    "dabhip_dir_resolve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p]),
+    "dabhip_dir_reset": (C.c_int, [C.c_void_p, C.c_int]),
+    "dabhip_dir_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
+    "dabhip_dir_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
     "dabhip_packet_create": (C.c_void_p, [C.c_int, C.c_int, C.POINTER(C.c_int32), u8p, C.c_int]),
     "dabhip_packet_destroy": (None, [C.c_void_p]),
     "dabhip_packet_push": (C.c_int64, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
@@ -1082,6 +1095,135 @@ class Ts(_Handle):
     def stage_ms(self):
         """GPU time of the last push per stage: TS_STAGES in ms."""
         return _stage_ms(lib().dabhip_ts_stage_ms, self._h, len(TS_STAGES))
+
+
+# ---- ensemble directory (dabhip.h: dabhip_dir_*) --------------------------------------------------------------------------
+_DIR_META = [("first_frame", "<i8"), ("last_frame", "<i8"), ("changes", "<i8")]
+DIR_ENSEMBLE = np.dtype([("have", "u1"), ("charset", "u1"), ("eid", "<u2"), ("label_eid", "<u2"), ("char_flags", "<u2"), ("label", "u1", (16,)),
+                         ("change_flag", "u1"), ("al", "u1"), ("cif_hi", "u1"), ("cif_lo", "u1"), ("lto", "u1"), ("ecc", "u1"), ("inter_table", "u1"),
+                         ("utc_flag", "u1"), ("mjd", "<u4"), ("lsi", "u1"), ("hours", "u1"), ("minutes", "u1"), ("seconds", "u1"), ("milliseconds", "<u2"),
+                         ("pad", "u1", (6,)), ("time_frame", "<i8")] + _DIR_META)
+DIR_SUBCH = np.dtype([("have", "u1"), ("id", "u1"), ("form", "u1"), ("uep_index", "u1"), ("protlev", "u1"), ("fec_scheme", "u1"), ("start_cu", "<u2"),
+                      ("size_cu", "<u2"), ("bitrate", "<u2"), ("pad", "u1", (4,))] + _DIR_META)
+DIR_SERVICE = np.dtype([("sid", "<u4"), ("pd", "u1"), ("have", "u1"), ("info", "u1"), ("ncomp", "u1"), ("comp", "u1", (30,)), ("charset", "u1"), ("pad0", "u1"),
+                        ("label", "u1", (16,)), ("char_flags", "<u2"), ("pad", "u1", (6,))] + _DIR_META)
+DIR_PKTCOMP = np.dtype([("scid", "<u2"), ("address", "<u2"), ("scca", "<u2"), ("subch", "u1"), ("dscty", "u1"), ("dg", "u1"), ("scca_flag", "u1"),
+                        ("pad", "u1", (6,))] + _DIR_META)
+DIR_TARGET = np.dtype([(n, "<i4") for n in ("kind", "subch", "address", "dg", "dscty", "fec", "scid", "primary")])
+assert (DIR_ENSEMBLE.itemsize, DIR_SUBCH.itemsize, DIR_SERVICE.itemsize, DIR_PKTCOMP.itemsize, DIR_TARGET.itemsize) == (80, 40, 88, 40, 32)
+DIR_KINDS = ("UNKNOWN", "MP2", "DABPLUS", "TS", "STREAM_DATA", "PACKET")
+DIR_NO_SERVICE, DIR_NO_COMPONENT, DIR_NO_PKTCOMP, DIR_NO_SUBCH = -2, -3, -4, -5
+DIR_STATS = ("frames", "frames_without_fic", "frames_skipped", "fibs", "fibs_crc_failed", "figs", "figs_truncated", "figs_ignored", "facts", "facts_changed",
+             "overflow_dropped")
+DIR_STAGES = ("fibs", "merge")
+
+
+class DirUnresolved(DabhipError):
+    """Dir.resolve met a missing link; .code is DIR_NO_SERVICE, DIR_NO_COMPONENT, DIR_NO_PKTCOMP or DIR_NO_SUBCH."""
+
+    def __init__(self, code, text):
+        super().__init__(text)
+        self.code = code
+
+
+class Dir(_Handle):
+    """The ensemble directory out of ETI frames on the GPU (dabhip_dir_*): per stream, the ensemble record, the sub-channels, the services with
+    their components and labels, the packet components, from the FIC bytes of the frames pushed.  plan() names what DabPlus, Packet and Ts ask for."""
+    _destroy = "dabhip_dir_destroy"
+
+    def __init__(self, nstreams=1, device=0):
+        self.nstreams = int(nstreams)
+        self._h = lib().dabhip_dir_create(device, self.nstreams)
+        _need(self._h, "dir_create")
+
+    def push(self, frames, counts=None):
+        """frames as Ts.push takes them.  Returns the FIBs of this push whose CRC held."""
+        if isinstance(frames, tuple):
+            ptr, counts = frames
+            src, on_dev = C.c_void_p(ptr), 1
+        else:
+            if isinstance(frames, list):
+                counts = [np.asarray(f).size // ETI_BYTES for f in frames]
+                arr = np.ascontiguousarray(np.concatenate([np.asarray(f, dtype=np.uint8).reshape(-1) for f in frames]) if frames else np.zeros(0, np.uint8))
+            else:
+                arr = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+                if counts is None:
+                    _need(self.nstreams == 1, "dir_push: counts needed for several streams")
+                    counts = [arr.size // ETI_BYTES]
+            self._keep = arr
+            src, on_dev = C.c_void_p(arr.ctypes.data), 0
+        cnt = (C.c_int64 * self.nstreams)(*[int(c) for c in counts])
+        n = lib().dabhip_dir_push(self._h, src, cnt, on_dev)
+        _need(n >= 0, "dir_push")
+        return n
+
+    def ensemble(self, stream=0):
+        """The ensemble record: a DIR_ENSEMBLE scalar."""
+        out = np.zeros(1, dtype=DIR_ENSEMBLE)
+        _need(lib().dabhip_dir_ensemble(self._h, stream, out.ctypes.data) == 0, "dir_ensemble")
+        return out[0]
+
+    def _table(self, fn, what, dtype, stream):
+        out = np.zeros(64, dtype=dtype)
+        n = fn(self._h, stream, out.ctypes.data, 64)
+        _need(0 <= n <= 64, what)
+        return out[:n]
+
+    def subchannels(self, stream=0):
+        """Sub-channels with any part, in SubChId order: a DIR_SUBCH array."""
+        return self._table(lib().dabhip_dir_subchannels, "dir_subchannels", DIR_SUBCH, stream)
+
+    def services(self, stream=0):
+        """Services in order of first appearance: a DIR_SERVICE array."""
+        return self._table(lib().dabhip_dir_services, "dir_services", DIR_SERVICE, stream)
+
+    def packet_components(self, stream=0):
+        """Packet components in order of first appearance: a DIR_PKTCOMP array."""
+        return self._table(lib().dabhip_dir_packet_components, "dir_packet_components", DIR_PKTCOMP, stream)
+
+    def complete(self, stream=0):
+        r = lib().dabhip_dir_complete(self._h, stream)
+        _need(r >= 0, "dir_complete")
+        return bool(r)
+
+    def resolve(self, stream, pd, sid, component=0):
+        """{kind (a DIR_KINDS name), subch, address, dg, dscty, fec, scid, primary}; DirUnresolved when a link is missing."""
+        out = np.zeros(1, dtype=DIR_TARGET)
+        r = lib().dabhip_dir_resolve(self._h, stream, int(pd), int(sid), int(component), out.ctypes.data)
+        if r in (DIR_NO_SERVICE, DIR_NO_COMPONENT, DIR_NO_PKTCOMP, DIR_NO_SUBCH):
+            raise DirUnresolved(r, last_error())
+        _need(r == 0, "dir_resolve")
+        t = {n: int(out[0][n]) for n in DIR_TARGET.names}
+        t["kind"] = DIR_KINDS[t["kind"]]
+        t["fec"] = bool(t["fec"])
+        return t
+
+    def reset(self, stream=0):
+        _need(lib().dabhip_dir_reset(self._h, stream) == 0, "dir_reset")
+
+    def stats(self, stream=0):
+        """Counters since creation, in DIR_STATS order (int64 array of 11)."""
+        c = np.zeros(11, dtype=np.int64)
+        _need(lib().dabhip_dir_stats(self._h, stream, c.ctypes.data_as(C.POINTER(C.c_int64))) == 0, "dir_stats")
+        return c
+
+    def stage_ms(self):
+        """GPU time of the last push per stage: DIR_STAGES in ms."""
+        return _stage_ms(lib().dabhip_dir_stage_ms, self._h, len(DIR_STAGES))
+
+    def plan(self, stream=0):
+        """One dict per component that resolves, services in table order: sid, pd, component, label (16 bytes), kind, subch, fec, address -- what
+        DabPlus(nstreams, [subch]), Packet(nstreams, [subch], fec=[fec]) and Ts(nstreams, [subch]) are built from."""
+        out = []
+        for s in self.services(stream):
+            for c in range(int(s["ncomp"])):
+                try:
+                    t = self.resolve(stream, int(s["pd"]), int(s["sid"]), c)
+                except DirUnresolved:
+                    continue
+                out.append({"sid": int(s["sid"]), "pd": int(s["pd"]), "component": c, "label": bytes(s["label"]), "kind": t["kind"], "subch": t["subch"],
+                            "fec": t["fec"], "address": t["address"]})
+        return out
 
 
 class PacketGroups(_Handle):

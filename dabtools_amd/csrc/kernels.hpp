@@ -9,6 +9,7 @@
 
 #include "dabplus.hpp"
 #include "device_types.hpp"
+#include "dir.hpp"
 #include "launch_limits.hpp"
 #include "packet.hpp"
 #include "ts.hpp"
@@ -247,6 +248,13 @@ hipError_t launch_ts_parse(const TsUnit* units, const int* totals, int64_t nunit
                            int64_t* counters, hipStream_t stream);
 hipError_t launch_ts_carry(const PacketFrames& fr, int nlanes, const TsLoc* loc, int maxv, int nsub, const uint8_t* carry, const TsLane* lanes, const int* totals,
                            uint8_t* carry_next, hipStream_t stream);
+
+// k_dir.hip: the ensemble directory out of ETI frames (dir.hpp has the types, dir_figs.hpp the rules, dabhip.h the rules in words).  fibs: a thread
+// per (stream, new frame, FIB): frame header, CRC, FIG walk; its facts into the FIB's kDirFactSlots slots of `facts` and its DirFib record, both
+// indexed by (base[s] + frame) * 3 + fib.  merge: a wave per stream applies the stream's facts in order to its tables (staged in LDS), adds its
+// counters and leaves the FIBs of this push whose CRC held in ok_fibs[s].
+hipError_t launch_dir_fibs(const DirFrames& fr, int nstreams, int maxv, DirFib* fibs, DirFact* facts, hipStream_t stream);
+hipError_t launch_dir_merge(const DirFrames& fr, int nstreams, const DirFib* fibs, const DirFact* facts, DirStream* state, int* ok_fibs, hipStream_t stream);
 
 // k_probe.hip: streaming rates of this device (fill, copy, K2's read/write mix) in GB/s -- bench.py's yardstick beside the K2 figure
 int stream_ceiling(int device, size_t bytes, int reps, double* gbs);

@@ -91,6 +91,8 @@ bool channel_active(const dabhip_channel_cfg& c)
   return c.sro_ppm != 0.0 || c.echo_delay[0] || c.echo_delay[1] || c.fade_depth != 0.0 || c.iq_gain_db != 0.0 || c.iq_phase_deg != 0.0;
 }
 
+bool si_fits(const dabhip_synth_cfg& cfg);
+
 bool validate(const dabhip_synth_cfg& cfg)
 {
   if (!validate_multiplex(cfg.nsub, cfg.sub)) return false;
@@ -116,6 +118,13 @@ bool validate(const dabhip_synth_cfg& cfg)
     if (cfg.ts_slots & cfg.packet_slots) { set_error("synth: a slot cannot be both an MPEG-2 TS and a packet-mode slot"); return false; }
     for (const dabhip_reconf_cfg& r : cfg.reconf)
       if (r.at_cif != 0) { set_error("synth: ts_slots cannot be combined with reconfigurations"); return false; }
+  }
+  if (cfg.si_mode) {
+    if (cfg.si_mode != 1) { set_error("synth: si_mode must be 0 or 1"); return false; }
+    for (const dabhip_reconf_cfg& r : cfg.reconf)
+      if (r.at_cif != 0) { set_error("synth: si_mode cannot be combined with reconfigurations"); return false; }
+    if (cfg.fib_patch_len > 0) { set_error("synth: si_mode cannot be combined with a FIB patch"); return false; }
+    if (!si_fits(cfg)) { set_error("synth: si_mode: the FIBs have no room for a FIG of the service information"); return false; }
   }
   int prev = 0;
   for (const dabhip_reconf_cfg& r : cfg.reconf) {
@@ -520,9 +529,90 @@ void payload_bytes(const dabhip_synth_cfg& cfg, int cif, int slot, uint8_t* out,
   }
 }
 
+// ---- service information (dabhip_synth_cfg::si_mode; the directory's rules are in dabhip.h, "ensemble directory") -----------------------------
+// The carousel: whole FIGs in a fixed order -- the ensemble label, FIG 0/9, FIG 0/10, then per slot its FIG 0/2, its label and, for a packet slot,
+// its FIG 0/3 and (with FEC) its FIG 0/14.  Only FIG 0/10 depends on the CIF.
+const char* si_kind_name(const dabhip_synth_cfg& cfg, int k)
+{
+  return (cfg.dabplus_slots >> k & 1) ? "DAB+" : (cfg.ts_slots >> k & 1) ? "TS" : (cfg.packet_slots >> k & 1) ? "PACKET" : "MP2";
+}
+std::vector<uint8_t> si_label_fig(int ext, uint32_t id, const char* text)
+{
+  std::vector<uint8_t> f;
+  const int kl = ext == 5 ? 4 : 2;
+  f.push_back(static_cast<uint8_t>(0x20 | (1 + kl + 18)));
+  f.push_back(static_cast<uint8_t>(ext));                  // charset 0, OE 0
+  for (int b = kl - 1; b >= 0; --b) f.push_back(static_cast<uint8_t>(id >> (8 * b)));
+  const size_t n = std::strlen(text);
+  for (size_t i = 0; i < 16; ++i) f.push_back(static_cast<uint8_t>(i < n ? text[i] : ' '));
+  f.push_back(0xff);                                       // character flag field
+  f.push_back(0x00);
+  return f;
+}
+std::vector<std::vector<uint8_t>> si_carousel(const dabhip_synth_cfg& cfg, int cif)
+{
+  std::vector<std::vector<uint8_t>> figs;
+  figs.push_back(si_label_fig(0, cfg.eid, "DABHIP SYNTH"));
+  figs.push_back({0x04, 0x09, 0x00, 0xe1, 0x01});          // FIG 0/9: LTO 0, ECC 0xE1, international table 1
+  {
+    const int64_t t = std::max<int64_t>(0, static_cast<int64_t>(cfg.cif_count0) + cif) * 24;     // ms since MJD 60000, 00:00 UTC
+    const uint32_t mjd = 60000 + static_cast<uint32_t>(t / 86400000), ms = static_cast<uint32_t>(t % 86400000);
+    const uint32_t hours = ms / 3600000, minutes = ms / 60000 % 60, seconds = ms / 1000 % 60, milli = ms % 1000;
+    const uint32_t w = mjd << 14 | 1u << 11 | hours << 6 | minutes;                              // rfu 0, LSI 0, rfa 0, UTC flag 1
+    figs.push_back({0x07, 0x0a, static_cast<uint8_t>(w >> 24), static_cast<uint8_t>(w >> 16), static_cast<uint8_t>(w >> 8), static_cast<uint8_t>(w),
+                    static_cast<uint8_t>(seconds << 2 | milli >> 8), static_cast<uint8_t>(milli)});
+  }
+  for (int k = 0; k < cfg.nsub && k < 64; ++k) {
+    const int id = to_subchannel(cfg.sub[k]).id;
+    const bool packet = cfg.packet_slots >> k & 1, ts = cfg.ts_slots >> k & 1, plus = cfg.dabplus_slots >> k & 1;
+    const bool data = packet || ts;
+    const uint32_t sid = data ? 0xE0001000u + static_cast<uint32_t>(k) : 0x1000u + static_cast<uint32_t>(k);
+    std::vector<uint8_t> f = {static_cast<uint8_t>(data ? 8 : 6), static_cast<uint8_t>(data ? 0x22 : 0x02)};
+    for (int b = (data ? 3 : 1); b >= 0; --b) f.push_back(static_cast<uint8_t>(sid >> (8 * b)));
+    f.push_back(0x01);                                     // local 0, CAId 0, one component
+    if (packet) { f.push_back(static_cast<uint8_t>(0xc0 | (k >> 6))); f.push_back(static_cast<uint8_t>((k & 63) << 2 | 2)); }       // TMId 3, SCId k, primary
+    else { f.push_back(static_cast<uint8_t>(ts ? (0x40 | 24) : plus ? 63 : 0)); f.push_back(static_cast<uint8_t>(id << 2 | 2)); }
+    figs.push_back(f);
+    char text[24];
+    std::snprintf(text, sizeof text, "SLOT %02d %s", k, si_kind_name(cfg, k));
+    figs.push_back(si_label_fig(data ? 5 : 1, sid, text));
+    if (packet) {
+      int addr[3];
+      packet_addresses(cfg, k, addr);
+      figs.push_back({0x06, 0x03, static_cast<uint8_t>(k >> 4), static_cast<uint8_t>((k & 15) << 4), static_cast<uint8_t>(0x80 | 60),     // no SCCA; DG flag 1, DSCTy 60
+                      static_cast<uint8_t>(id << 2 | addr[0] >> 8), static_cast<uint8_t>(addr[0])});
+      if (cfg.packet_fec_slots >> k & 1) figs.push_back({0x02, 0x0e, static_cast<uint8_t>(id << 2 | 1)});
+    }
+  }
+  return figs;
+}
+// Which FIGs of the carousel go where: the carousel is cut into loads, CIF c carries load c mod the number of loads.  A load takes FIGs in order,
+// each into the first of the three FIBs with room left behind FIG 0/0 and FIG 0/1 (pos[f] bytes used); the first FIG that fits nowhere waits
+// for the next load.  False: a FIG fits in no FIB at all.
+bool si_loads(const std::vector<std::vector<uint8_t>>& figs, const int pos[3], std::vector<std::vector<std::pair<int, int>>>& loads)
+{
+  loads.clear();
+  size_t next = 0;
+  while (next < figs.size()) {
+    int used[3] = {pos[0], pos[1], pos[2]};
+    std::vector<std::pair<int, int>> load;
+    for (; next < figs.size(); ++next) {
+      int f = 0;
+      while (f < 3 && used[f] + static_cast<int>(figs[next].size()) > 30) ++f;
+      if (f == 3) break;
+      used[f] += static_cast<int>(figs[next].size());
+      load.emplace_back(f, static_cast<int>(next));
+    }
+    if (load.empty()) return false;
+    loads.push_back(load);
+  }
+  return true;
+}
+
 // the three FIBs of one CIF: FIG 0/0 (ensemble, CIF counter) and FIG 0/1 (sub-channel
-// organisation) entries packed greedily, then end marker / padding and the FIB CRC
-void build_fibs(const dabhip_synth_cfg& cfg, int cif, uint8_t* out96)
+// organisation) entries packed greedily, then with si_mode the carousel's load, then end marker / padding and the FIB CRC.
+// False: si_mode is set and a FIG of the carousel fits in no FIB.
+bool build_fibs(const dabhip_synth_cfg& cfg, int cif, uint8_t* out96)
 {
   const int count = ((cfg.cif_count0 + cif) % 5000 + 5000) % 5000;
   std::vector<std::vector<uint8_t>> entries;
@@ -541,6 +631,7 @@ void build_fibs(const dabhip_synth_cfg& cfg, int cif, uint8_t* out96)
     entries.push_back(e);
   }
   size_t next = 0;
+  int used[3];
   for (int f = 0; f < 3; ++f) {
     uint8_t* fib = out96 + 32 * f;
     std::memset(fib, 0, 32);
@@ -568,11 +659,34 @@ void build_fibs(const dabhip_synth_cfg& cfg, int cif, uint8_t* out96)
       pos = std::min(cfg.fib_patch_len, 30);
       std::memcpy(fib, cfg.fib_patch, static_cast<size_t>(pos));
     }
+    used[f] = pos;
+  }
+  if (cfg.si_mode) {
+    const std::vector<std::vector<uint8_t>> figs = si_carousel(cfg, cif);
+    std::vector<std::vector<std::pair<int, int>>> loads;
+    if (!si_loads(figs, used, loads)) return false;
+    const int nl = static_cast<int>(loads.size());
+    for (const std::pair<int, int>& at : loads[static_cast<size_t>((cif % nl + nl) % nl)]) {
+      const std::vector<uint8_t>& g = figs[static_cast<size_t>(at.second)];
+      std::memcpy(out96 + 32 * at.first + used[at.first], g.data(), g.size());
+      used[at.first] += static_cast<int>(g.size());
+    }
+  }
+  for (int f = 0; f < 3; ++f) {
+    uint8_t* fib = out96 + 32 * f;
+    const int pos = used[f];
     if (pos < 30) fib[pos] = 0xff;            // end marker, rest zero padding
     const uint16_t crc = static_cast<uint16_t>(~crc16_ccitt(fib, 30));
     fib[30] = static_cast<uint8_t>(crc >> 8);
     fib[31] = static_cast<uint8_t>(crc & 0xff);
   }
+  return true;
+}
+
+bool si_fits(const dabhip_synth_cfg& cfg)
+{
+  uint8_t fibs[96];
+  return build_fibs(cfg, 0, fibs);
 }
 
 // keep the mother-code bits the puncturing plan transmits
@@ -942,6 +1056,7 @@ extern "C" int dabhip_synth_ts_word(const dabhip_synth_cfg* cfg, int slot, int64
 extern "C" int dabhip_synth_fibs(const dabhip_synth_cfg* cfg, int cif_index, uint8_t* out96)
 {
   if (!cfg || !out96) return -1;
+  if (cfg->si_mode && !validate(*cfg)) return -1;
   build_fibs(*cfg, cif_index, out96);
   return 96;
 }

@@ -749,6 +749,168 @@ int dabhip_ts_stats(const dabhip_ts *d, int stream, int sub, int64_t *counters8)
  * returns the count. */
 int dabhip_ts_stage_ms(const dabhip_ts *d, const char **names, float *ms, int cap);
 
+/* ---- ensemble directory (EN 300 401 clauses 5.2, 6, 8: the FIC's service information) ---------- */
+/* A stateful consumer of ETI frames that reads the 96 FIC bytes of each on the GPU and keeps, per stream, what the ensemble carries: the
+ * ensemble record, the sub-channels, the services with their components and labels, the packet-mode components.  Its answer names, for every
+ * component, the sub-channel (and packet address, and FEC flag) that dabhip_dabplus, dabhip_packet and dabhip_ts ask their caller for.  Off
+ * unless asked for and handled like dabhip_ts: frames are pushed stream by stream.  It is a strict parser of its own: the engine's control
+ * plane keeps the reference's parse (control_plane.hpp), over-reads included.  These rules were written from the standard as remembered, not
+ * from a copy of it nor from a broadcast recording; what this text, tests/dir_model.py, the modulator's si_mode and the
+ * kernels agree on is what counts.
+ *
+ * Frames.  ETI(NI), 6144 bytes.  NST = byte 5 & 0x7F, FICF = byte 5 >> 7, MID = (byte 6 >> 3) & 3.  Every frame counts in `frames`.  FICF = 0:
+ * the frame gives nothing and counts in `frames_without_fic`.  Else MID != 1 or NST > 64: nothing, `frames_skipped`.  Else the FIC is the 96
+ * bytes at 12 + 4 NST: FIB 0, 1, 2 of 32 bytes, each counted in `fibs`.  The frames of a stream are numbered from 0 since creation (`frames`
+ * before the frame); reset does not restart the numbers.
+ *
+ * FIB.  Bytes 30, 31 = ~CRC (high byte first), CRC-16-CCITT (x^16 + x^12 + x^5 + 1, initial value 0xFFFF, MSB first) of bytes 0..29.  A FIB
+ * whose CRC fails counts in `fibs_crc_failed` and gives nothing else.
+ *
+ * FIG walk over bytes 0..29; nothing outside them is ever read.  i = 0.  While i < 30 and byte i != 0xFF: the FIG header is byte i, type =
+ * top 3 bits, length = low 5 bits; `figs` += 1.  Length 0, or i + 1 + length > 30: `figs_truncated` += 1 and the walk of this FIB ends.  Else
+ * the data field is the `length` bytes from i + 1, the FIG is taken as below, and i += 1 + length.  A FIG is exactly one of: handled, ignored
+ * (`figs_ignored` += 1, no facts), or refused whole as truncated (type 1, 0/0, 0/9, 0/10).  Inside a handled FIG with a list of entries, the
+ * entries are taken one after another from the body (the data field without its first byte); an entry that does not lie wholly inside the
+ * body ends the FIG, `figs_truncated` += 1, earlier entries stand.  An empty body is legal and gives nothing.
+ *
+ * Type 0.  First data byte: C/N (bit 7), OE (6), P/D (5), extension (low 5).  OE = 1: ignored.  Else C/N = 1 and extension 1, 2, 3 or 14:
+ * ignored.  Else by extension (every other one: ignored); multi-byte fields are big-endian:
+ *   0/0   body >= 4 bytes, else truncated: EId(16); change flag(2) Al(1) CIF count high(5); CIF count low(8).  Further bytes are skipped.  One fact.
+ *   0/1   entry: SubChId(6) start address(10); then the form bit (bit 7 of the third byte).  Short form, 3 bytes: form(1) table switch(1)
+ *         UEP index(6); size, bit rate and protection level are the rows of ETSI table 7 (dab_tables.hpp: uep_table).  Long form, 4 bytes:
+ *         form(1) option(3) level(2) size(10); protlev = level | option << 2, bit rate = size / m[protlev & 7] * (protlev & 4 ? 32 : 8)
+ *         with m = 12, 8, 6, 4, 27, 21, 18, 15 (integer division; eep_size_multiple).  The table switch is not kept.  One fact per entry.
+ *   0/2   entry: SId (16 bits if P/D = 0, 32 if P/D = 1); one byte local(1) CAId(3) number of components(4); then 2 bytes per component:
+ *         TMId(2) and, TMId 0: ASCTy(6) SubChId(6) P/S(1) CA(1); TMId 1: DSCTy(6) SubChId(6) P/S CA; TMId 3: SCId(12) P/S CA; TMId 2: kept
+ *         raw.  One fact per entry, with the whole component list.
+ *   0/3   entry: SCId(12) rfa(3) SCCA flag(1); DG flag(1) rfu(1) DSCTy(6); SubChId(6) packet address(10); SCCA(16) only with the flag: 5 or 7
+ *         bytes.  rfa and rfu are not kept; SCCA is kept as 0 without the flag.  One fact per entry.
+ *   0/9   body >= 3 bytes, else truncated: the three bytes are kept raw (LTO byte, ECC, international table id); the rest is skipped.  One fact.
+ *   0/10  body >= 4 bytes: rfu(1) MJD(17) LSI(1) rfa(1) UTC flag(1) hours(5) minutes(6); with the UTC flag, 2 more bytes: seconds(6)
+ *         milliseconds(10), kept as 0 without.  A body shorter than 4, or 6 with the flag: truncated.  The rest is skipped.  One fact.
+ *   0/14  every body byte is an entry: SubChId(6) FEC scheme(2).  One fact per byte.
+ * Type 1.  First data byte: charset (high 4), OE (bit 3), extension (low 3).  OE = 1: ignored.  Extension 0: EId(16), 1: SId(16), 5: SId(32),
+ * then 16 character bytes and a 16-bit character flag field: the data field must be exactly 21 bytes (0, 1) or 23 (5), else truncated.  One
+ * fact: a label.  1/1 names the service (P/D 0, SId), 1/5 the service (P/D 1, SId).  Every other extension: ignored.
+ * Types 2..7: ignored.
+ * A FIB gives at most 28 facts (28 bytes of 0/14).  `facts` counts them.
+ *
+ * Directory, per stream since creation or the last reset: the ensemble record; 64 sub-channels indexed by SubChId; at most 64 services keyed
+ * by (P/D, SId), each with its 0/2 byte, up to 15 raw two-byte component descriptors, and its label, charset and flag field; at most 64 packet
+ * components keyed by SCId.  Facts are applied in the order (frame, FIB, byte offset).  An entry has one part per kind of fact that can reach
+ * it: ensemble: 0/0, 0/9, 0/10, label (with the label's EId); sub-channel: 0/1, 0/14; service: 0/2, label; packet component: 0/3.  A fact
+ * whose key exists replaces the part of its kind and no other (a 0/2 fact the whole component list; a label leaves the components alone and
+ * the reverse).  A new key is appended, so services and packet components stand in order of first appearance.  A fact that needs a new key
+ * in a full table is dropped and counts in `overflow_dropped`.  Every entry keeps first_frame and last_frame, the frame numbers of the first
+ * and the latest fact applied to it, and `changes`: the facts that found their part present and altered a kept field of it (a first fact of
+ * its kind is no change).  `facts_changed` counts the same over the stream.  The ensemble's time_frame is the frame of the latest 0/10.
+ * A FIG never spans FIBs, so nothing is carried: any cutting of a stream into pushes gives the same directory.
+ *
+ * Complete: 0/0 and the ensemble label seen; at least one service; every service has its 0/2 part and its label; every TMId 0 or 1 component's
+ * sub-channel has its 0/1 part; every TMId 3 component's SCId has a 0/3 entry whose sub-channel has its 0/1 part.
+ *
+ * Resolve (stream, P/D, SId, component index): kind MP2 (TMId 0, ASCTy 0), DABPLUS (TMId 0, ASCTy 63), TS (TMId 1, DSCTy 24), STREAM_DATA
+ * (other TMId 1), PACKET (TMId 3), UNKNOWN (TMId 2: no sub-channel, subch = -1; other TMId 0); the SubChId; for PACKET the packet address, DG
+ * flag, DSCTy and fec = (the sub-channel's 0/14 scheme == 1; 0 when no 0/14 was seen).  A missing link is an error, never a guess:
+ * DABHIP_DIR_NO_SERVICE, _NO_COMPONENT (no 0/2 part, or the index past its list), _NO_PKTCOMP (no 0/3 for the SCId), _NO_SUBCH (no 0/1 for
+ * the sub-channel). */
+typedef struct dabhip_dir dabhip_dir;
+enum { DABHIP_DIR_UNKNOWN = 0, DABHIP_DIR_MP2 = 1, DABHIP_DIR_DABPLUS = 2, DABHIP_DIR_TS = 3, DABHIP_DIR_STREAM_DATA = 4, DABHIP_DIR_PACKET = 5 };
+enum { DABHIP_DIR_NO_SERVICE = -2, DABHIP_DIR_NO_COMPONENT = -3, DABHIP_DIR_NO_PKTCOMP = -4, DABHIP_DIR_NO_SUBCH = -5 };
+#define DABHIP_DIR_HAVE_00 1        /* dabhip_dir_ensemble_rec.have */
+#define DABHIP_DIR_HAVE_09 2
+#define DABHIP_DIR_HAVE_10 4
+#define DABHIP_DIR_HAVE_LABEL 8
+#define DABHIP_DIR_SUB_HAVE_01 1    /* dabhip_dir_subch.have */
+#define DABHIP_DIR_SUB_HAVE_14 2
+#define DABHIP_DIR_SVC_HAVE_02 1    /* dabhip_dir_service.have */
+#define DABHIP_DIR_SVC_HAVE_LABEL 2
+typedef struct dabhip_dir_ensemble_rec {
+  uint8_t have;                     /* DABHIP_DIR_HAVE_*; 0: nothing seen, the rest is zero */
+  uint8_t charset;
+  uint16_t eid;                     /* 0/0 */
+  uint16_t label_eid;               /* 1/0 */
+  uint16_t char_flags;
+  uint8_t label[16];
+  uint8_t change_flag, al, cif_hi, cif_lo;
+  uint8_t lto, ecc, inter_table, utc_flag;
+  uint32_t mjd;
+  uint8_t lsi, hours, minutes, seconds;
+  uint16_t milliseconds;
+  uint8_t pad[6];
+  int64_t time_frame;               /* frame of the latest 0/10; -1 without */
+  int64_t first_frame, last_frame, changes;
+} dabhip_dir_ensemble_rec;
+typedef struct dabhip_dir_subch {
+  uint8_t have;                     /* DABHIP_DIR_SUB_HAVE_* */
+  uint8_t id;
+  uint8_t form;                     /* 0 short (UEP), 1 long (EEP) */
+  uint8_t uep_index;                /* short form */
+  uint8_t protlev;                  /* short: 1..5; long: level | option << 2 */
+  uint8_t fec_scheme;               /* 0/14 */
+  uint16_t start_cu;
+  uint16_t size_cu;
+  uint16_t bitrate;                 /* kbit/s */
+  uint8_t pad[4];
+  int64_t first_frame, last_frame, changes;
+} dabhip_dir_subch;
+typedef struct dabhip_dir_service {
+  uint32_t sid;
+  uint8_t pd;
+  uint8_t have;                     /* DABHIP_DIR_SVC_HAVE_* */
+  uint8_t info;                     /* 0/2: local(1) CAId(3) number of components(4) */
+  uint8_t ncomp;
+  uint8_t comp[30];                 /* two raw bytes per component */
+  uint8_t charset;
+  uint8_t pad0;
+  uint8_t label[16];
+  uint16_t char_flags;
+  uint8_t pad[6];
+  int64_t first_frame, last_frame, changes;
+} dabhip_dir_service;
+typedef struct dabhip_dir_pktcomp {
+  uint16_t scid;
+  uint16_t address;
+  uint16_t scca;
+  uint8_t subch;
+  uint8_t dscty;
+  uint8_t dg;
+  uint8_t scca_flag;
+  uint8_t pad[6];
+  int64_t first_frame, last_frame, changes;
+} dabhip_dir_pktcomp;
+typedef struct dabhip_dir_target {
+  int32_t kind;                     /* DABHIP_DIR_MP2 ... */
+  int32_t subch;                    /* -1: none */
+  int32_t address, dg, dscty, fec;  /* PACKET only, else 0 */
+  int32_t scid;                     /* PACKET only, else -1 */
+  int32_t primary;                  /* the component's P/S bit */
+} dabhip_dir_target;
+/* NULL when there is no GPU (dabhip_last_error). */
+dabhip_dir *dabhip_dir_create(int device, int nstreams);
+void dabhip_dir_destroy(dabhip_dir *d);
+/* counts[s] ETI frames of stream s, stream after stream in `frames`, in DEVICE memory when on_device != 0 (no alignment needed), else in host
+ * memory.  A push of no frames is legal; one push takes at most 65536 frames in all (3840 bytes of fact slots per frame).  Returns the FIBs
+ * with a valid CRC in this call, <0 on error. */
+int64_t dabhip_dir_push(dabhip_dir *d, const uint8_t *frames, const int64_t *counts, int on_device);
+/* The tables of one stream.  _ensemble returns 0; the others copy min(n, cap) entries (out may be null) and return n: sub-channels with any
+ * part, in SubChId order; services and packet components in order of first appearance.  <0 on error. */
+int dabhip_dir_ensemble(const dabhip_dir *d, int stream, dabhip_dir_ensemble_rec *out);
+int dabhip_dir_subchannels(const dabhip_dir *d, int stream, dabhip_dir_subch *out, int cap);
+int dabhip_dir_services(const dabhip_dir *d, int stream, dabhip_dir_service *out, int cap);
+int dabhip_dir_packet_components(const dabhip_dir *d, int stream, dabhip_dir_pktcomp *out, int cap);
+/* 1 complete, 0 not, <0 on error. */
+int dabhip_dir_complete(const dabhip_dir *d, int stream);
+/* 0 and *out, or DABHIP_DIR_NO_* (a missing link), or -1 (bad arguments, HIP error). */
+int dabhip_dir_resolve(const dabhip_dir *d, int stream, int pd, uint32_t sid, int component, dabhip_dir_target *out);
+/* Empties the tables of one stream; its counters and frame numbers go on. */
+int dabhip_dir_reset(dabhip_dir *d, int stream);
+/* Counters since creation: frames, frames_without_fic, frames_skipped, fibs, fibs_crc_failed, figs, figs_truncated, figs_ignored, facts,
+ * facts_changed, overflow_dropped.  Returns 0, <0 on error. */
+int dabhip_dir_stats(const dabhip_dir *d, int stream, int64_t *counters11);
+/* GPU time of the last push in ms, stage by stage (names: "fibs", "merge"); returns the count. */
+int dabhip_dir_stage_ms(const dabhip_dir *d, const char **names, float *ms, int cap);
+
 /* ---- ingest stage: other sample formats and rates -> the canonical cu8 at 2.048 Msps ------------------------------
  * Off unless asked for: a stateful object in front of the decoder that turns nstreams streams of cu8 / cs8 / cs16 / cf32 IQ (I first, little-endian)
  * at an integer sample rate Fin into cu8 at 2,048,000 samples/s in device memory, ready for dabhip_engine_decode(..., on_device = 1) and
@@ -1081,6 +1243,19 @@ typedef struct dabhip_synth_cfg {
   uint64_t ts_slots;
   int32_t ts_phase;
   int32_t ts_pad;
+  /* Service information (see "ensemble directory" above; 0 = off, byte-identical captures and dabhip_synth_fibs).  1: the room that FIG 0/0 and
+   * FIG 0/1 leave in the three FIBs of a CIF carries a carousel of whole FIGs, in this order: FIG 1/0 "DABHIP SYNTH"; FIG 0/9 (LTO 0, ECC 0xE1,
+   * table 1); FIG 0/10 (long form: MJD 60000 at 00:00:00.000 UTC plus 24 ms x (cif_count0 + CIF index)); then for every slot k a service --
+   * SId 0x1000 + k, P/D 0 for a plain (MP2) or DAB+ slot, SId 0xE0001000 + k, P/D 1 for a ts_slots or packet_slots slot -- as a FIG 0/2 entry
+   * with one primary component (plain: TMId 0, ASCTy 0; DAB+: TMId 0, ASCTy 63; TS: TMId 1, DSCTy 24; packet: TMId 3, SCId k), its label FIG
+   * 1/1 or 1/5 "SLOT kk KIND" (kk in two decimal digits; KIND = MP2, DAB+, TS, PACKET; padded with spaces to 16; charset 0, flag field 0xFF00)
+   * and, for a packet slot, a FIG 0/3 entry (SCId k, the slot's SubChId, its first address as dabhip_synth_packet_addresses gives it, DG flag
+   * 1, DSCTy 60, no SCCA) and, when packet_fec_slots names it, a FIG 0/14 byte with scheme 1.  The carousel is cut into loads: a load takes FIGs
+   * in order, each into the first FIB with room; the first that fits nowhere starts the next load; CIF c carries load c mod the number of loads.
+   * A FIG never splits.  Refused together with reconfigurations, with fib_patch_len > 0, and when a FIG fits in no FIB.  Both generators honour
+   * it: the device modulator takes its FIBs from the same host function. */
+  int32_t si_mode;
+  int32_t si_pad;
 } dabhip_synth_cfg;
 
 /* preset 0: 12 sub-channels, 1136 kbit/s, 862 CU (the benchmark mix); 1: 4 light sub-channels. */
