@@ -497,7 +497,7 @@ def synth_generate_device(cfgs, ntf, ptrs, device=0):
 
 
 def synth_payload(cfg, cif_index, slot):
-    buf = np.zeros(1152 * 2, dtype=np.uint8)
+    buf = np.zeros(ETI_BYTES, dtype=np.uint8)          # a sub-channel's bytes per CIF lie inside one ETI frame (EEP 4-B at n = 57: 5472)
     n = lib().dabhip_synth_payload(C.byref(cfg), cif_index, slot, _p(buf), buf.size)
     _need(n >= 0, "synth_payload")
     return buf[:n].copy()

@@ -215,7 +215,9 @@ inline uint32_t layout_fault(const std::vector<SubChannel>& active, int header_l
     if (sc.start_cu * 64 + pp.coded_bits() > kCifBits) f |= kFaultOutsideCif;
     bytes += (((pp.trellis_steps() - 6) / 8) + 7) & 0xfff8;          // misc.c:259-260: obytes
   }
-  if (bytes + 8 > 6144) f |= kFaultMuxOverflow;                       // EOF (4) + TIST (4), misc.c:281-292
+  // EOF (4) + TIST (4), misc.c:281-292.  A multiplex that passes has every sub-channel's bytes inside the frame: none longer than kMaxCodewordBytes
+  // (dab_tables.hpp), the size of the decoders' descrambling table
+  if (bytes + 8 > kEtiBytes) f |= kFaultMuxOverflow;
   return f;
 }
 

@@ -24,6 +24,13 @@ constexpr int kFicBits = 3 * kBitsPerSym;    // 9216
 constexpr int kMscBits = 72 * kBitsPerSym;   // 221184
 constexpr int kCifBits = 18 * kBitsPerSym;   // 55296 = 864 CU x 64
 constexpr int kEtiBytes = 6144;
+// The most decoded bytes one code word may have: every sub-channel of a multiplex that layout_fault (control_plane.hpp) passes lies inside the ETI
+// frame, so its obytes are below kEtiBytes (one sub-channel alone: 6144 - 16 header - 96 FIC - 8 trailer = 6024; EEP 4-B at n = 57 has 5472, EEP 4-A at
+// n = 216 has 5184).  The descrambling table every chain-back indexes by output word, and the zero table of the S1 entry, hold this many bytes;
+// prepare_msc_work (worklist.hpp) and Engine::viterbi_batch refuse a longer code word.
+constexpr int kMaxCodewordBytes = kEtiBytes;
+constexpr int kMaxCodewordWords = kMaxCodewordBytes / 4;
+static_assert(kMaxCodewordBytes % 4 == 0 && kMaxCodewordBytes >= kEtiBytes, "the chain-backs read the descrambling table a 32-bit word at a time, for every code word an ETI frame can hold");
 constexpr int kChunkBytes = 262144;          // librtlsdr buffer size used by dab2eti.c:238
 
 struct UepProfile {            // ETSI Table 7 + Table 36; pi holds PI (1..24), 0 = unused

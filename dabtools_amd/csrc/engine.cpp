@@ -86,7 +86,9 @@ Engine::Engine(int device, int host_threads, std::vector<int> cpus) : device_(de
         crc_shift[i * 16 + bit] = y;
       }
     }
-  std::vector<uint32_t> prbs(1024), zeros(1024, 0u);     // 4096 bytes >= the largest sub-channel (1152 bytes per CIF at 384 kbit/s)
+  // the descrambling words of the longest code word an ETI frame can hold (dab_tables.hpp: kMaxCodewordBytes; EEP 4-B at n = 57 is 5472 bytes per CIF),
+  // and as many zero words for the S1 entry, which descrambles nothing
+  std::vector<uint32_t> prbs(kMaxCodewordWords), zeros(kMaxCodewordWords, 0u);
   {
     Prbs g;
     for (auto& w : prbs) {

@@ -245,6 +245,8 @@ int Engine::viterbi_batch(const uint8_t* symbols, uint8_t* data, int framebits, 
   if (!ok_) { set_error("engine not initialised (no GPU?)"); return -1; }
   if (n <= 0) return 0;
   if (framebits <= 0 || framebits % 32 != 0) { set_error("viterbi: framebits must be a positive multiple of 32"); return -1; }
+  // (the chain-back reads a zero word per output word: engine.cpp; refused before the plan enters the table the kernels read)
+  if (framebits / 32 > kMaxCodewordWords) { set_error("viterbi: code word too long (at most " + std::to_string(32 * kMaxCodewordWords) + " bits)"); return -1; }
   const int nsteps = framebits + 6, n16 = (nsteps + 15) / 16;
   const int ngroups = (n + 63) / 64;
   CodewordPlan plan;
@@ -275,7 +277,7 @@ int Engine::viterbi_batch(const uint8_t* symbols, uint8_t* data, int framebits, 
   }
   // no gather: upload the step rows directly, then run the decoder with an all-zero scrambler
   const size_t out_bytes = static_cast<size_t>(n) * (framebits / 8);
-  if (framebits / 32 > 1024) { set_error("viterbi: code word too long"); return -1; }
+  if (framebits / 32 > kMaxCodewordWords) { set_error("viterbi: code word too long"); return -1; }      // (the zero words the chain-back reads: engine.cpp)
   if (!d_plans_.upload(plan_table_.plans(), stream_) || !d_groups_.upload(groups, stream_) || !d_steps_.upload(steps, stream_) ||
       !d_decisions_.reserve(static_cast<size_t>(ngroups) * dr * 64) || !d_bytes_.reserve(out_bytes))
     return -1;

@@ -227,6 +227,12 @@ bool prepare_msc_work(PlanTable& plans, ThreadPool& pool, const std::vector<cons
         int off = job_header_len + 96;
         for (const SubChannel& sc : subs) {
           CodewordPlan cp = make_codeword_plan(puncture_plan(sc), sc.start_cu * 64, off);
+          // (the chain-backs index the descrambling table by output word: a plan past its end would be read out of bounds.  layout_fault lets none
+          // through -- a sub-channel that long does not fit the frame --; held here as well, in front of the plan table the kernels read)
+          if (cp.out_bytes > kMaxCodewordBytes) {
+            if (error) *error = "sub-channel of " + std::to_string(cp.out_bytes) + " bytes per CIF: longer than the descrambling table";
+            return false;
+          }
           lay.plan_ids.push_back(plans.id(cp));
           off += (cp.out_bytes + 7) & 0xfff8;          // misc.c:259-260: obytes = ((bits/8)+7) & 0xfff8
         }

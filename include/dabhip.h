@@ -79,7 +79,10 @@ void dabhip_dab_free(dabhip_dab *d);
 uint8_t *dabhip_dab_tf_fic(dabhip_dab *d);   /* 9216 bytes */
 uint8_t *dabhip_dab_tf_msc(dabhip_dab *d);   /* 221184 bytes */
 /* Replaces dab_process_frame(dab) (dab.h:92, dab.c:35-98): invokes the callback 0 or 4
- * times, synchronously, with a pointer to a 6144-byte frame valid during the call. */
+ * times, synchronously, with a pointer to a 6144-byte frame valid during the call.
+ * Sub-channels of every size are decoded: all that fit the CIF and the ETI frame (see dabhip_engine_stream_status), up to 43,782 trellis steps and
+ * 5,472 bytes per CIF (EEP 4-B at n = 57).  Above 13,824 data bits per code word -- EEP A levels beyond n = 72, B levels beyond n = 18 -- the
+ * reference's own decoder is past its allocation (create_viterbi(768*18), dab.c:29): parity there is with the oracle and with the transmitted payload. */
 int dabhip_dab_process_frame(dabhip_dab *d);
 int dabhip_dab_locked(const dabhip_dab *d);
 /* What the reference's dab_process_frame prints on stderr for its operator -- "Locked" (dab.c:51), "Lock lost, resetting ringbuffer" (dab.c:57), the one-time
@@ -128,7 +131,9 @@ int64_t dabhip_engine_eti_count(const dabhip_engine *e, int stream);      /* fra
  * (misc.c:233,246-296), uep_/eep_depuncture read past cif_time_deinterleaved[55296] (depuncture.c:84-132), eeptable[] is indexed past its 8 rows
  * (fic.c:84): undefined behaviour, no parity target.  Here such a stream is flagged and emits NO frames while its multiplex is in that state (for
  * good: the reference only ever adds sub-channels, misc.c:14-21); lock rule, CIF ring and frame counter move on as they would; every other stream
- * of the batch decodes exactly as if it were alone.  0 = fine; 0xffffffff = no such stream. */
+ * of the batch decodes exactly as if it were alone.  0 = fine; 0xffffffff = no such stream.
+ * A multiplex that raises none of the flags is decoded whatever the sizes of its sub-channels, one that fills all 864 capacity units included; above
+ * 13,824 data bits per code word the reference's decoder is past its own allocation (dab.c:29) and parity is with the oracle and the transmitted payload. */
 #define DABHIP_STREAM_MUX_OVERFLOW 1u       /* header + FIC + sub-channel bytes + trailer exceed 6144 bytes */
 #define DABHIP_STREAM_SUBCH_OUTSIDE_CIF 2u  /* a sub-channel's transmitted bits end beyond capacity unit 863 */
 #define DABHIP_STREAM_EEP_OPTION 4u         /* EEP protection option > 1: outside ETSI EN 300 401 and past the reference's table */

@@ -285,9 +285,48 @@ static void test_launch_limits()
   }
 }
 
+// the longest code word an ETI frame can hold (EEP 4-B at n = 57: 43,782 steps, 5,472 bytes per CIF) through the control plane and the work lists: its plan
+// stays inside the decoders' descrambling table (kMaxCodewordBytes), its decision rows are sized by its length in both layouts; one unit more is refused
+static void largest_codeword()
+{
+  dabhip_synth_cfg cfg;
+  CHECK(dabhip_synth_preset(1, &cfg) == 0);
+  cfg.nsub = 1;
+  cfg.sub[0].id = 5; cfg.sub[0].start_cu = 9; cfg.sub[0].slform = 1; cfg.sub[0].uep_index = 0; cfg.sub[0].eep_protlev = 7; cfg.sub[0].size_cu = 15 * 57;
+  const int ntf = 16;
+  std::vector<uint8_t> fibs(static_cast<size_t>(ntf) * 384), ok(static_cast<size_t>(ntf) * 12, 1);
+  for (int c = 0; c < 4 * ntf; ++c) CHECK(dabhip_synth_fibs(&cfg, c, fibs.data() + static_cast<size_t>(c) * 96) == 96);
+  ControlPlane plane;
+  JobList jobs;
+  for (int t = 0; t < ntf; ++t) plane.on_tf(t, fibs.data() + static_cast<size_t>(t) * 384, ok.data() + static_cast<size_t>(t) * 12, jobs);
+  CHECK(plane.fault() == 0 && jobs.size() == 12);
+  ThreadPool pool(2);
+  std::vector<const ControlPlane*> plane_ptrs = {&plane};
+  std::vector<const JobList*> job_ptrs = {&jobs};
+  std::vector<int> row_base = {15}, fib_base = {0};
+  for (int64_t wave_max : {int64_t(0), int64_t(12288)}) {
+    PlanTable plans;
+    MscWorkT<StdAlloc> work;
+    std::string error;
+    CHECK(prepare_msc_work(plans, pool, job_ptrs, plane_ptrs, row_base, fib_base, int64_t(48) << 20, work, &error, nullptr, wave_max));
+    CHECK(plans.plans().size() == 1 && work.batch.groups.size() == 1 && work.batch.wave_form == (wave_max > 0));
+    const CodewordPlan& p = plans[0];
+    CHECK(p.nsteps == 43782 && p.out_bytes == 5472 && p.out_bytes <= kMaxCodewordBytes && p.start_bit == 9 * 64);
+    CHECK(p.out_offset + p.out_bytes + 8 <= kEtiBytes && work.meta[0].mst_bytes == 5472);
+    CHECK(work.batch.max_dec_rows == (wave_max > 0 ? int64_t(64) * 730 : int64_t(43784)));
+  }
+  std::vector<SubChannel> active = plane.layouts().back();
+  CHECK(active.size() == 1 && layout_fault(active, 16) == 0);
+  active[0].size_cu = 15 * 58;                             // one unit more: past CU 863
+  active[0].bitrate = 32 * 58;
+  CHECK(layout_fault(active, 16) & kFaultOutsideCif);
+  static_assert(kMaxCodewordWords * 4 == kMaxCodewordBytes && kMaxCodewordBytes >= kEtiBytes, "the table covers every code word of a frame");
+}
+
 static void test_control_and_worklist()
 {
   test_launch_limits();
+  largest_codeword();
   control_and_worklist(24, 30, int64_t(48) << 20, 0);
   control_and_worklist(9, 22, 20000, 1);                 // a small record cap: many slices
   // several engines' host sides at once in one process (dabhip_multi: one lane + one pool per slice)
