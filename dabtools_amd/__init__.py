@@ -228,6 +228,15 @@ _SIGNATURES = {
     "dabhip_dir_reset": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_dir_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
     "dabhip_dir_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
+    "dabhip_edi_plan": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "dabhip_edi_create": (C.c_void_p, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dabhip_edi_destroy": (None, [C.c_void_p]),
+    "dabhip_edi_push": (C.c_int64, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    "dabhip_edi_records": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
+    "dabhip_edi_data": (C.c_int64, [C.c_void_p, C.c_int, u8p, C.c_int64]),
+    "dabhip_edi_reset": (C.c_int, [C.c_void_p, C.c_int]),
+    "dabhip_edi_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
+    "dabhip_edi_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
     "dabhip_packet_create": (C.c_void_p, [C.c_int, C.c_int, C.POINTER(C.c_int32), u8p, C.c_int]),
     "dabhip_packet_destroy": (None, [C.c_void_p]),
     "dabhip_packet_push": (C.c_int64, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
@@ -1224,6 +1233,84 @@ class Dir(_Handle):
                 out.append({"sid": int(s["sid"]), "pd": int(s["pd"]), "component": c, "label": bytes(s["label"]), "kind": t["kind"], "subch": t["subch"],
                             "fec": t["fec"], "address": t["address"]})
         return out
+
+
+# ---- EDI out of ETI (dabhip.h: dabhip_edi_*) --------------------------------------------------------------------------------
+EDI_REC = np.dtype([("offset", "<i8"), ("frame", "<i8"), ("length", "<i4"), ("findex", "<i4"), ("fcount", "<i4"), ("seq", "<u2"), ("pad", "<u2")])
+EDI_SIZES = np.dtype([(n, "<i4") for n in ("c", "k", "z", "B", "f", "s")])
+assert (EDI_REC.itemsize, EDI_SIZES.itemsize) == (32, 24)
+EDI_AF, EDI_PFT, EDI_PFT_FEC = 0, 1, 2
+EDI_STATS = ("frames", "frames_skipped", "frames_without_fic", "packets", "bytes_out", "chunks_encoded")
+EDI_STAGES = ("plan", "scan", "assemble", "rs", "fragment")
+
+
+def edi_plan(l, mode=EDI_PFT_FEC, recover=0, max_frag=1400):
+    """The sizes of one AF packet of l bytes by the function the kernels use (host only): {c, k, z, B, f, s}.  DabhipError on a refused argument."""
+    out = np.zeros(1, dtype=EDI_SIZES)
+    _need(lib().dabhip_edi_plan(int(l), int(mode), int(recover), int(max_frag), out.ctypes.data) == 0, "edi_plan")
+    return {n: int(out[0][n]) for n in EDI_SIZES.names}
+
+
+class Edi(_Handle):
+    """EDI packets out of ETI frames on the GPU (dabhip_edi_*): every frame as TAG items in an AF packet (mode EDI_AF), cut into PFT fragments
+    (EDI_PFT), or protected by RS(255,207) and interleaved over the fragments (EDI_PFT_FEC), for nstreams streams.  FCTH and SEQ carry from push
+    to push."""
+    _destroy = "dabhip_edi_destroy"
+
+    def __init__(self, nstreams=1, mode=EDI_AF, recover=0, max_frag=1400, seq0=0, device=0):
+        self.nstreams, self.mode = int(nstreams), int(mode)
+        self._h = lib().dabhip_edi_create(device, self.nstreams, self.mode, int(recover), int(max_frag), int(seq0))
+        _need(self._h, "edi_create")
+
+    def push(self, frames, counts=None):
+        """frames as Ts.push takes them.  Returns the packets of this push."""
+        if isinstance(frames, tuple):
+            ptr, counts = frames
+            src, on_dev = C.c_void_p(ptr), 1
+        else:
+            if isinstance(frames, list):
+                counts = [np.asarray(f).size // ETI_BYTES for f in frames]
+                arr = np.ascontiguousarray(np.concatenate([np.asarray(f, dtype=np.uint8).reshape(-1) for f in frames]) if frames else np.zeros(0, np.uint8))
+            else:
+                arr = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+                if counts is None:
+                    _need(self.nstreams == 1, "edi_push: counts needed for several streams")
+                    counts = [arr.size // ETI_BYTES]
+            self._keep = arr
+            src, on_dev = C.c_void_p(arr.ctypes.data), 0
+        cnt = (C.c_int64 * self.nstreams)(*[int(c) for c in counts])
+        n = lib().dabhip_edi_push(self._h, src, cnt, on_dev)
+        _need(n >= 0, "edi_push")
+        return n
+
+    def records(self, stream=0):
+        """Records of the last push's packets of a stream: an EDI_REC array."""
+        n = lib().dabhip_edi_records(self._h, stream, None, 0)
+        _need(n >= 0, "edi_records")
+        out = np.zeros(n, dtype=EDI_REC)
+        _need(lib().dabhip_edi_records(self._h, stream, out.ctypes.data, n) == n, "edi_records")
+        return out
+
+    def data(self, stream=0):
+        """Their bytes, packet after packet: a uint8 array."""
+        n = lib().dabhip_edi_data(self._h, stream, None, 0)
+        _need(n >= 0, "edi_data")
+        out = np.zeros(n, dtype=np.uint8)
+        _need(lib().dabhip_edi_data(self._h, stream, _p(out), n) == n, "edi_data")
+        return out
+
+    def reset(self, stream=0):
+        _need(lib().dabhip_edi_reset(self._h, stream) == 0, "edi_reset")
+
+    def stats(self, stream=0):
+        """Counters since creation, in EDI_STATS order (int64 array of 6)."""
+        c = np.zeros(6, dtype=np.int64)
+        _need(lib().dabhip_edi_stats(self._h, stream, c.ctypes.data_as(C.POINTER(C.c_int64))) == 0, "edi_stats")
+        return c
+
+    def stage_ms(self):
+        """GPU time of the last push per stage: EDI_STAGES in ms."""
+        return _stage_ms(lib().dabhip_edi_stage_ms, self._h, len(EDI_STAGES))
 
 
 class PacketGroups(_Handle):

@@ -916,6 +916,92 @@ int dabhip_dir_stats(const dabhip_dir *d, int stream, int64_t *counters11);
 /* GPU time of the last push in ms, stage by stage (names: "fibs", "merge"); returns the count. */
 int dabhip_dir_stage_ms(const dabhip_dir *d, const char **names, float *ms, int cap);
 
+/* ---- EDI out of ETI (ETSI TS 102 693, the DAB layer, over ETSI TS 102 821: AF packets, PFT) ---------- */
+/* A stateful consumer of ETI frames that repackages every frame as an EDI packet on the GPU: the TAG items of the frame in an AF packet with
+ * its CRC, and, when asked for, PFT fragments with or without RS(255,207) protection.  Off unless asked for and handled like dabhip_ts: frames
+ * are pushed stream by stream, the state of every stream (FCTH, SEQ) carries from push to push, and any cutting of a stream into pushes gives
+ * the same bytes.  These rules were written from the standards as remembered, not from a copy of them nor from a second EDI implementation
+ * (which marks the points least sure of); what this text, tests/edi_model.py and the kernels agree on is what counts.
+ *
+ * Multi-byte fields are big-endian.  CRC-16 everywhere is the ETI one: x^16 + x^12 + x^5 + 1, start 0xFFFF, MSB first, result complemented;
+ * the nine ASCII bytes "123456789" give 0xD64E.
+ *
+ * Frames.  ETI(NI), 6144 bytes, numbered per stream from 0 since creation, skipped ones included.  ERR = byte 0, FCT = byte 4, FICF = byte 5
+ * >> 7, NST = byte 5 & 0x7F, FP = byte 6 >> 5, MID = (byte 6 >> 3) & 3.  STC entry i is the 4 bytes at 8 + 4 i: SCID 6 bits, SAD 10, TPL 6,
+ * STL 10.  MNSC is the 2 bytes at 8 + 4 NST.  The main stream starts at 12 + 4 NST: the FIC (96 bytes) if FICF, then 8 STL bytes per entry in
+ * STC order.  A frame is skipped when NST > 64, when FICF = 1 and MID != 1, or when its main stream would run past byte 6140.  A skipped frame
+ * gives no packet, counts in `frames_skipped`, consumes no sequence number and is invisible to the FCTH rule.  FSYNC and the frame's own CRCs
+ * are not checked.  Every other frame is accepted.
+ *
+ * TAG items: a name of 4 bytes, a length in BITS as u32, then the value.  In order:
+ *   *ptr   64 bits: "DETI", major 0x0000, minor 0x0000.
+ *   deti   16 bits ATSTF (= 0) << 15 | FICF << 14 | RFUDF (= 0) << 13 | FCTH << 8 | FCT; 32 bits STAT (= ERR) << 24 | MID << 22 | FP << 19 |
+ *          RFA (= 0) << 17 | RFU (= 0) << 16 | MNSC; the 96 FIC bytes when FICF.  48 or 816 bits.
+ *   est n  for entry n = 1..NST, named 'e', 's', 't', byte n: 24 bits SCID << 18 | SAD << 8 | TPL << 2 | 0, then the entry's 8 STL bytes (STL 0
+ *          gives a 3-byte value).
+ * The TAG packet is then padded with zero bytes to a multiple of 8 bytes.
+ *
+ * FCTH, per stream: the first accepted frame has FCTH 0; an accepted frame whose FCT is below the previous accepted frame's takes
+ * (FCTH + 1) mod 20, any other keeps it.
+ *
+ * AF packet: "AF", LEN u32 = the TAG packet's bytes, padding included, SEQ u16, 0x90 (CRC present, major 1, minor 0), 'T', the TAG packet, the
+ * CRC-16 over everything before it; l = LEN + 12 bytes.  SEQ is seq0 for a stream's first accepted frame and grows by 1 mod 65536 per accepted
+ * frame.
+ *
+ * Modes.  0: the AF packet as it is.  1: PFT without FEC: with F = max_frag the packet is cut into f = ceil(l / F) consecutive slices of F
+ * bytes, the last one shorter.  2: PFT with RS.
+ *
+ * PF header: "PF", PSEQ u16 = the AF packet's SEQ, FINDEX u24 from 0, FCOUNT u24, u16 FEC << 15 | ADDR (= 0) << 14 | PLEN, with FEC RSk u8
+ * and RSz u8: 12 bytes, 14 with FEC; then HCRC, the CRC-16 over them.  A fragment is its header, the HCRC and PLEN bytes.
+ *
+ * Mode 2.  c = ceil(l / 207), k = ceil(l / c), z = c k - l.  The packet is padded with z zero bytes and cut into c chunks of k bytes.  The
+ * code word of a chunk has 255 bytes, byte j the coefficient of x^(254 - j): the k chunk bytes, then 207 - k zero bytes, then 48 parity bytes,
+ * the remainder of (the first 207 bytes) x^48 by g(x) = prod (x + alpha^i), i = 0..47; GF(256) by 0x11D, alpha = 2.  RS block: chunk 0's k
+ * bytes, its 48 parity bytes, chunk 1's k bytes, its 48 parity bytes, and so on: B = c (k + 48) bytes.  With m = recover (0..5) and F =
+ * max_frag (64..1472): s_max = min(floor(48 c / (m + 1)), F), f = ceil(B / s_max), s = ceil(B / f); byte j of fragment i is block byte
+ * j f + i, and 0 where that is >= B; every fragment has PLEN = s, RSk = k, RSz = z.  So any m fragments carry at most 48 bytes of any one code
+ * word, and a receiver finds c = floor(f s / (k + 48)).
+ *
+ * Output, per stream: the packets of the last push in frame order, then fragment order, and one record per packet.  Not done (DESIGN.md
+ * section 6): ATST time stamps, RFUD, ADDR, transmission modes other than I, a UDP sender, the reverse direction, ETI(NA). */
+typedef struct dabhip_edi dabhip_edi;
+typedef struct dabhip_edi_rec {     /* one packet of the last push */
+  int64_t offset;                   /* of its first byte among the stream's bytes of the last push */
+  int64_t frame;                    /* the frame's number */
+  int32_t length;                   /* bytes */
+  int32_t findex;                   /* 0 in mode 0 */
+  int32_t fcount;                   /* 1 in mode 0 */
+  uint16_t seq;
+  uint16_t pad;
+} dabhip_edi_rec;
+typedef struct dabhip_edi_sizes {   /* dabhip_edi_plan */
+  int32_t c, k, z;                  /* mode 2, else 0 */
+  int32_t B;                        /* bytes cut into fragments: c (k + 48) in mode 2, else l */
+  int32_t f;                        /* packets */
+  int32_t s;                        /* PLEN of every fragment (mode 1: but the last); l in mode 0 */
+} dabhip_edi_sizes;
+/* The sizes of one AF packet of l bytes (13 .. 2^20), by the function the kernels use; host only, no GPU needed.  recover counts in mode 2
+ * only, max_frag in modes 1 and 2.  Returns 0, <0 when an argument is out of range (dabhip_last_error names it). */
+int dabhip_edi_plan(int64_t l, int mode, int recover, int max_frag, dabhip_edi_sizes *out);
+/* mode 0..2, recover 0..5 (mode 2), max_frag 64..1472 (modes 1, 2), seq0 0..65535.  NULL when there is no GPU or an argument is out of range
+ * (dabhip_last_error). */
+dabhip_edi *dabhip_edi_create(int device, int nstreams, int mode, int recover, int max_frag, int seq0);
+void dabhip_edi_destroy(dabhip_edi *d);
+/* counts[s] ETI frames of stream s, stream after stream in `frames`, in DEVICE memory when on_device != 0 (no alignment needed), else in host
+ * memory.  A push of no frames is legal; one push takes at most 131072 frames in all.  Returns the packets of this call, <0 on error. */
+int64_t dabhip_edi_push(dabhip_edi *d, const uint8_t *frames, const int64_t *counts, int on_device);
+/* The packets of the last push of one stream, in order: copies min(n, cap) records, returns n. */
+int64_t dabhip_edi_records(const dabhip_edi *d, int stream, dabhip_edi_rec *out, int64_t cap);
+/* Their bytes, packet after packet: copies min(n, cap) bytes, returns n. */
+int64_t dabhip_edi_data(const dabhip_edi *d, int stream, uint8_t *dst, int64_t cap);
+/* The stream's FCTH and SEQ as after creation; its counters and frame numbers go on. */
+int dabhip_edi_reset(dabhip_edi *d, int stream);
+/* Counters since creation: frames, frames_skipped, frames_without_fic (accepted frames with FICF = 0), packets, bytes out, chunks encoded.
+ * Returns 0, <0 on error. */
+int dabhip_edi_stats(const dabhip_edi *d, int stream, int64_t *counters6);
+/* GPU time of the last push in ms, stage by stage (names: "plan", "scan", "assemble", "rs", "fragment"); returns the count. */
+int dabhip_edi_stage_ms(const dabhip_edi *d, const char **names, float *ms, int cap);
+
 /* ---- ingest stage: other sample formats and rates -> the canonical cu8 at 2.048 Msps ------------------------------
  * Off unless asked for: a stateful object in front of the decoder that turns nstreams streams of cu8 / cs8 / cs16 / cf32 IQ (I first, little-endian)
  * at an integer sample rate Fin into cu8 at 2,048,000 samples/s in device memory, ready for dabhip_engine_decode(..., on_device = 1) and
