@@ -237,6 +237,15 @@ _SIGNATURES = {
     "dabhip_edi_reset": (C.c_int, [C.c_void_p, C.c_int]),
     "dabhip_edi_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),
     "dabhip_edi_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
+    "dabhip_edirx_create": (C.c_void_p, [C.c_int, C.c_int, C.c_int]),
+    "dabhip_edirx_destroy": (None, [C.c_void_p]),
+    "dabhip_edirx_push": (C.c_int64, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_int]),
+    "dabhip_edirx_flush": (C.c_int64, [C.c_void_p, C.c_int]),
+    "dabhip_edirx_records": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
+    "dabhip_edirx_frames": (C.c_int64, [C.c_void_p, C.c_int, u8p, C.c_int64]),
+    "dabhip_edirx_reset": (C.c_int, [C.c_void_p, C.c_int]),
+    "dabhip_edirx_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]),
+    "dabhip_edirx_stage_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]),
     "dabhip_packet_create": (C.c_void_p, [C.c_int, C.c_int, C.POINTER(C.c_int32), u8p, C.c_int]),
     "dabhip_packet_destroy": (None, [C.c_void_p]),
     "dabhip_packet_push": (C.c_int64, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
@@ -1311,6 +1320,86 @@ class Edi(_Handle):
     def stage_ms(self):
         """GPU time of the last push per stage: EDI_STAGES in ms."""
         return _stage_ms(lib().dabhip_edi_stage_ms, self._h, len(EDI_STAGES))
+
+
+# ---- EDI in (dabhip.h: dabhip_edirx_*) ----------------------------------------------------------------------------------------
+EDIRX_REC = np.dtype([("frame", "<i8"), ("received", "<i4"), ("expected", "<i4"), ("words_filled", "<i4"), ("erasures_filled", "<i4"), ("seq", "<u2"),
+                      ("fcth", "u1"), ("fct", "u1"), ("pad", "<u4")])
+assert EDIRX_REC.itemsize == 32
+EDIRX_STATS = ("packets", "bad_packets", "late", "duplicates", "mismatched", "missing", "groups_incomplete", "groups_rs_failed", "groups_crc_failed",
+               "groups_refused", "words_filled", "erasures_filled", "items_ignored", "with_atst", "frames")
+EDIRX_STAGES = ("parse", "window", "gather", "rs", "frame", "emit", "carry")
+
+
+class EdiRx(_Handle):
+    """ETI frames out of EDI packets on the GPU (dabhip_edirx_*): AF packets as they are, PFT fragments reassembled within a window of `depth`
+    sequence numbers, lost fragments recovered by RS(255,207) erasure decoding, for nstreams streams.  The window and the held fragments
+    carry from push to push."""
+    _destroy = "dabhip_edirx_destroy"
+
+    def __init__(self, nstreams=1, depth=4, device=0):
+        self.nstreams = int(nstreams)
+        self._h = lib().dabhip_edirx_create(device, self.nstreams, int(depth))
+        _need(self._h, "edirx_create")
+
+    def push(self, packets, counts=None):
+        """packets: the datagrams (bytes or uint8 arrays) of all streams, stream after stream, counts[s] of stream s (one stream: all of them);
+        or a tuple (device pointer, lengths, counts) of their bytes concatenated in device memory.  Returns the ETI frames of this push."""
+        if isinstance(packets, tuple):
+            ptr, lengths, counts = packets
+            src, on_dev = C.c_void_p(ptr), 1
+        else:
+            packets = [np.frombuffer(bytes(x), np.uint8) if isinstance(x, (bytes, bytearray)) else np.asarray(x, np.uint8).reshape(-1) for x in packets]
+            lengths = [x.size for x in packets]
+            if counts is None:
+                _need(self.nstreams == 1, "edirx_push: counts needed for several streams")
+                counts = [len(packets)]
+            _need(sum(int(c) for c in counts) == len(packets), "edirx_push: counts and packets disagree")
+            arr = np.ascontiguousarray(np.concatenate(packets)) if packets else np.zeros(0, np.uint8)
+            self._keep = arr
+            src, on_dev = C.c_void_p(arr.ctypes.data), 0
+        _need(len(counts) == self.nstreams, "edirx_push: one count per stream")
+        _need(sum(int(c) for c in counts) == len(lengths), "edirx_push: counts and lengths disagree")
+        cnt = (C.c_int64 * self.nstreams)(*[int(c) for c in counts])
+        lens = np.ascontiguousarray(lengths, dtype=np.int32)
+        n = lib().dabhip_edirx_push(self._h, src, lens.ctypes.data_as(C.POINTER(C.c_int32)), cnt, on_dev)
+        _need(n >= 0, "edirx_push")
+        return n
+
+    def flush(self, stream=-1):
+        """Finalises the open groups of a stream (-1: of all).  Returns the frames this gave."""
+        n = lib().dabhip_edirx_flush(self._h, int(stream))
+        _need(n >= 0, "edirx_flush")
+        return n
+
+    def records(self, stream=0):
+        """Records of the last push's or flush's frames of a stream: an EDIRX_REC array."""
+        n = lib().dabhip_edirx_records(self._h, stream, None, 0)
+        _need(n >= 0, "edirx_records")
+        out = np.zeros(n, dtype=EDIRX_REC)
+        _need(lib().dabhip_edirx_records(self._h, stream, out.ctypes.data, n) == n, "edirx_records")
+        return out
+
+    def frames(self, stream=0):
+        """Their bytes: a uint8 array (n, 6144)."""
+        n = lib().dabhip_edirx_frames(self._h, stream, None, 0)
+        _need(n >= 0, "edirx_frames")
+        out = np.zeros((n, ETI_BYTES), dtype=np.uint8)
+        _need(lib().dabhip_edirx_frames(self._h, stream, _p(out), out.size) == n, "edirx_frames")
+        return out
+
+    def reset(self, stream=0):
+        _need(lib().dabhip_edirx_reset(self._h, stream) == 0, "edirx_reset")
+
+    def stats(self, stream=0):
+        """Counters since creation, in EDIRX_STATS order (int64 array of 15)."""
+        c = np.zeros(len(EDIRX_STATS), dtype=np.int64)
+        _need(lib().dabhip_edirx_stats(self._h, stream, c.ctypes.data_as(C.POINTER(C.c_int64)), c.size) == c.size, "edirx_stats")
+        return c
+
+    def stage_ms(self):
+        """GPU time of the last push or flush per stage: EDIRX_STAGES in ms."""
+        return _stage_ms(lib().dabhip_edirx_stage_ms, self._h, len(EDIRX_STAGES))
 
 
 class PacketGroups(_Handle):

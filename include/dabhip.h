@@ -963,7 +963,7 @@ int dabhip_dir_stage_ms(const dabhip_dir *d, const char **names, float *ms, int 
  * word, and a receiver finds c = floor(f s / (k + 48)).
  *
  * Output, per stream: the packets of the last push in frame order, then fragment order, and one record per packet.  Not done (DESIGN.md
- * section 6): ATST time stamps, RFUD, ADDR, transmission modes other than I, a UDP sender, the reverse direction, ETI(NA). */
+ * section 6): ATST time stamps, RFUD, ADDR, transmission modes other than I, a UDP sender, ETI(NA).  The reverse direction is dabhip_edirx, below. */
 typedef struct dabhip_edi dabhip_edi;
 typedef struct dabhip_edi_rec {     /* one packet of the last push */
   int64_t offset;                   /* of its first byte among the stream's bytes of the last push */
@@ -1001,6 +1001,98 @@ int dabhip_edi_reset(dabhip_edi *d, int stream);
 int dabhip_edi_stats(const dabhip_edi *d, int stream, int64_t *counters6);
 /* GPU time of the last push in ms, stage by stage (names: "plan", "scan", "assemble", "rs", "fragment"); returns the count. */
 int dabhip_edi_stage_ms(const dabhip_edi *d, const char **names, float *ms, int cap);
+
+/* ---- EDI in: PFT reassembly, RS(255,207) erasure recovery, ETI frames back ---------------------------- */
+/* The receiving half of dabhip_edi: a stateful consumer of EDI packets (datagrams) that gives ETI(NI) frames back, on the GPU, for nstreams
+ * streams.  It inverts dabhip_edi: for every frame the engine writes, the frames of edirx(edi(F)) are F byte for byte.  Field layouts, the
+ * CRC-16 and the code are those stated above; like them these rules were written without a copy of the standards or a second implementation
+ * (DESIGN.md section 6 marks the points least sure of).  tests/edirx_model.py restates them; csrc/edirx_plan.hpp is their text as functions.
+ *
+ * A packet, given its length n (n < 12: bad).
+ *   AF: "AF", LEN u32 with LEN + 12 = n, SEQ u16, byte 8 with (byte & 0xF0) = 0x90 (CRC flag set, major version 1, any minor), then 'T'.  It
+ *       is a group of its own: f = 1, FINDEX 0, numbered by SEQ, its payload the whole packet.  Its CRC is judged later, with every AF packet.
+ *   PF: "PF", PSEQ u16, FINDEX u24, FCOUNT u24, u16 FEC << 15 | ADDR << 14 | PLEN, with FEC RSk u8 and RSz u8, then HCRC over all bytes in
+ *       front of it.  n >= 14, n = 14 + PLEN or 16 + PLEN with FEC; the HCRC right; ADDR = 0; FINDEX < FCOUNT; 1 <= FCOUNT <= 256;
+ *       1 <= PLEN <= 1472; with FEC 1 <= RSk <= 207 and c = floor(FCOUNT PLEN / (RSk + 48)) in 1..32 with RSz < c.
+ * Anything else is dropped and counted in bad_packets; nothing is read past n.
+ *
+ * The window, per stream, over its packets in arrival order (every one counts in `packets`), q the packet's SEQ / PSEQ.  The first good packet
+ * since creation or reset sets next = q.  d = (q - next) mod 65536.
+ *   1. d >= 32768: dropped, `late`.
+ *   2. d >= depth: the d - depth + 1 numbers from next on leave the window in order: one with an open group is finalised, one without counts
+ *      in `missing`; next = q - depth + 1.  (Work bounded by the open groups.)
+ *   3. The packet joins the group of q, which it opens if there is none.  The first packet fixes the kind (AF, PF, PF with FEC), FCOUNT, RSk,
+ *      RSz and, with FEC, PLEN; a packet that disagrees is dropped, `mismatched`; one whose FINDEX is held is dropped, `duplicates`.  A group
+ *      has at most 8416 payload bytes (32 code words and their padding): a packet whose bytes would lie past that -- FCOUNT PLEN with FEC,
+ *      (FINDEX + 1) PLEN without (the last fragment of several excepted, see below), n for AF -- is dropped, `mismatched`, and opens no group.
+ *   4. While the group of next is open and complete (all f = FCOUNT fragments held; an AF packet at once): it is finalised, next + 1.  (Also
+ *      after a dropped packet.)
+ * Ready: complete, or, with FEC, at least f - m_max fragments held, m_max = floor(48 / ceil((RSk + 48) / f)): any m_max fragments hold at most
+ * 48 bytes of any code word, and the sender's `recover` is never above m_max.  A group that is ready but not complete waits for its missing
+ * fragments until it leaves the window (step 2) or is flushed: a stream without loss is never decoded and none of its fragments is `late`.
+ * Finalised while not ready: lost, `groups_incomplete`.  flush finalises the open groups in order and sets next behind the last of them.  reset: as after creation; the
+ * counters and the frame numbers go on.  State carries, the held fragments' bytes included: any cutting of a stream's packets into pushes,
+ * followed by a flush, gives the same frames, records and counters.
+ *
+ * A ready group becomes an AF packet.
+ *   Without FEC: the fragments in FINDEX order.  The fragments but the last must agree on PLEN, the last have no more, and the whole no more
+ *   than 8416 bytes, else `groups_refused` (counted when the group is finalised).
+ *   With FEC: block byte j f + i is byte j of fragment i.  Code word w is the block bytes from w (RSk + 48) on: RSk data bytes, then (known)
+ *   207 - RSk zero bytes, then 48 parity bytes; byte j of the 255 is the coefficient of x^(254 - j).  Its bytes in missing fragments are its
+ *   erasures, at most 48.  A word without erasures is taken as it is.  A word with erasures is filled in by erasure decoding (locator from the
+ *   places, Forney, first root alpha^0) and must then have 48 zero syndromes, else the group is lost, `groups_rs_failed`: that is an error
+ *   beside the erasures, and no error correction is tried.  The AF packet is the c RSk data bytes without the last RSz.  words_filled and
+ *   erasures_filled count over the groups that pass here.
+ *   Then: at least 12 bytes, "AF", LEN + 12 = its length, byte 8 and 'T' as above, the CRC-16 right, else `groups_crc_failed`.
+ *
+ * An AF packet becomes an ETI(NI) frame.  From byte 10 to the CRC, while 8 bytes or more remain: a TAG item: name, length in bits (a multiple
+ * of 8, the value inside what remains), value.  At most 7 bytes may remain, all zero.
+ *   *ptr   must be 8 bytes beginning "DETI".
+ *   deti   once, required: the 2 + 4 bytes as dabhip_edi writes them (ATSTF, FICF, RFUDF, FCTH, FCT; STAT, MID, FP, RFA, RFU, MNSC), then 8
+ *          bytes of time stamp when ATSTF (skipped; the frame counts in `with_atst`), 96 FIC bytes when FICF, 3 bytes when RFUDF (skipped);
+ *          exactly that long.
+ *   est n  n = 1, 2, .. in that order, at most 64: 3 bytes SCID << 18 | SAD << 8 | TPL << 2, then 8 STL bytes: length 3 + 8 STL, STL <= 1023.
+ *   Any other item is skipped and, for a frame that comes out, counted in `items_ignored`.
+ * Refused (`groups_refused`): a broken walk, no deti, FICF with MID != 1, or 12 + 4 NST + 96 FICF + 8 sum(STL) > 6140.
+ * The frame: byte 0 STAT; FSYNC 07 3A B6 for even FCT, F8 C5 49 for odd; FCT; FICF << 7 | NST; FP << 5 | MID << 3 | FL >> 8; FL & 255 with
+ * FL = NST + 1 + 24 FICF + 2 sum(STL); the STC entries SCID << 26 | SAD << 16 | TPL << 10 | STL; MNSC; the CRC-16 over bytes 4 .. 9 + 4 NST;
+ * the FIC and the sub-channels' bytes; the CRC-16 over them; FF FF; FF FF FF FF; then 0x55 up to byte 6143 (a main stream that ends past
+ * byte 6136 cuts the FF bytes short at the frame's end).
+ *
+ * Not done: correction of errors beside erasures, any use of the time stamps, ADDR, ETI(NA), a UDP socket reader, transmission modes other
+ * than I. */
+#define DABHIP_EDIRX_COUNTERS 15
+typedef struct dabhip_edirx dabhip_edirx;
+typedef struct dabhip_edirx_rec {   /* one frame of the last push or flush */
+  int64_t frame;                    /* its number among the stream's frames since creation */
+  int32_t received;                 /* fragments held when its group was finalised */
+  int32_t expected;                 /* FCOUNT; 1 for an AF packet */
+  int32_t words_filled;             /* code words that had erasures */
+  int32_t erasures_filled;          /* bytes filled in */
+  uint16_t seq;
+  uint8_t fcth;
+  uint8_t fct;
+  uint32_t pad;
+} dabhip_edirx_rec;
+/* depth 1..16: the sequence numbers (groups) kept open per stream.  NULL when there is no GPU or an argument is out of range. */
+dabhip_edirx *dabhip_edirx_create(int device, int nstreams, int depth);
+void dabhip_edirx_destroy(dabhip_edirx *d);
+/* counts[s] packets of stream s, stream after stream; lengths[p] (host memory) the bytes of packet p, a datagram boundary; the packets' bytes
+ * concatenated in `data`, in DEVICE memory when on_device != 0 (no alignment needed).  A push of no packets is legal; one push takes at most
+ * 2^21 packets and 2^31 - 1 bytes.  Returns the ETI frames this call produced, <0 on error. */
+int64_t dabhip_edirx_push(dabhip_edirx *d, const uint8_t *data, const int32_t *lengths, const int64_t *counts, int on_device);
+/* Finalises the open groups of one stream (-1: of every stream).  Returns the frames this produced, <0 on error. */
+int64_t dabhip_edirx_flush(dabhip_edirx *d, int stream);
+/* The frames of the last push or flush of one stream, in the order their groups were finalised: copies min(n, cap) records, returns n. */
+int64_t dabhip_edirx_records(const dabhip_edirx *d, int stream, dabhip_edirx_rec *out, int64_t cap);
+/* Their bytes, 6144 per record: copies the whole frames that fit in cap bytes, returns n (frames). */
+int64_t dabhip_edirx_frames(const dabhip_edirx *d, int stream, uint8_t *dst, int64_t cap);
+int dabhip_edirx_reset(dabhip_edirx *d, int stream);
+/* Counters since creation, min(cap, 15) of: packets, bad_packets, late, duplicates, mismatched, missing, groups_incomplete, groups_rs_failed,
+ * groups_crc_failed, groups_refused, words_filled, erasures_filled, items_ignored, with_atst, frames.  Returns how many, <0 on error. */
+int dabhip_edirx_stats(const dabhip_edirx *d, int stream, int64_t *counters, int cap);
+/* GPU time of the last push or flush in ms, stage by stage (names: "parse", "window", "gather", "rs", "frame", "emit", "carry"). */
+int dabhip_edirx_stage_ms(const dabhip_edirx *d, const char **names, float *ms, int cap);
 
 /* ---- ingest stage: other sample formats and rates -> the canonical cu8 at 2.048 Msps ------------------------------
  * Off unless asked for: a stateful object in front of the decoder that turns nstreams streams of cu8 / cs8 / cs16 / cf32 IQ (I first, little-endian)
