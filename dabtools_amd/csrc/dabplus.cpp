@@ -12,6 +12,7 @@
 #include "dab_bits.hpp"
 #include "dabplus.hpp"
 #include "kernels.hpp"
+#include "rs_code.hpp"
 #include "stage_frame.hpp"
 
 using namespace dabhip;
@@ -83,8 +84,8 @@ extern "C" dabhip_dabplus* dabhip_dabplus_create(int device, int nstreams, const
   d->nsub = nsub;
   d->ncarry.assign(static_cast<size_t>(nstreams), 0);
   const size_t nlanes = static_cast<size_t>(nstreams) * nsub;
-  std::vector<uint8_t> gf(dabplus_gf_table_bytes());
-  dabplus_gf_table_fill(gf.data());
+  GfRs<kRsRoots> gf;
+  rs_tables_fill(gf);
   std::vector<uint16_t> crc(256 + kRsK * kMaxS);
   for (int v = 0; v < 256; ++v) {
     const uint8_t b = static_cast<uint8_t>(v);
@@ -96,12 +97,12 @@ extern "C" dabhip_dabplus* dabhip_dabplus_create(int device, int nstreams, const
     crc[256 + n] = static_cast<uint16_t>(r);
     for (int b = 0; b < 8; ++b) r = (r & 0x8000u) ? ((r << 1) ^ 0x1021u) & 0xffffu : (r << 1) & 0xffffu;
   }
-  bool good = d->subch.reserve(nsub) && d->sync.reserve(nlanes) && d->counters.reserve(nlanes * kCntN) && d->gf.reserve(gf.size()) && d->crc_tab.reserve(crc.size()) &&
+  bool good = d->subch.reserve(nsub) && d->sync.reserve(nlanes) && d->counters.reserve(nlanes * kCntN) && d->gf.reserve(sizeof gf) && d->crc_tab.reserve(crc.size()) &&
          d->carry[0].reserve(static_cast<size_t>(nstreams) * 4 * DABHIP_ETI_BYTES) && d->carry[1].reserve(static_cast<size_t>(nstreams) * 4 * DABHIP_ETI_BYTES) &&
          d->totals.reserve(2);
   good = good && ok(hipMemcpy(d->subch.get(), subch_ids, sizeof(int32_t) * nsub, hipMemcpyHostToDevice), "upload") &&
          ok(hipMemset(d->sync.get(), 0, sizeof(DabPlusSync) * nlanes), "clear") && ok(hipMemset(d->counters.get(), 0, sizeof(int64_t) * nlanes * kCntN), "clear") &&
-         ok(hipMemcpy(d->gf.get(), gf.data(), gf.size(), hipMemcpyHostToDevice), "upload") &&
+         ok(hipMemcpy(d->gf.get(), &gf, sizeof gf, hipMemcpyHostToDevice), "upload") &&
          ok(hipMemcpy(d->crc_tab.get(), crc.data(), crc.size() * 2, hipMemcpyHostToDevice), "upload");
   return good ? d.release() : nullptr;
 }

@@ -1,6 +1,6 @@
-// dabplus.hpp — DAB+ audio superframes (ETSI TS 102 563): the sizes, the audio-superframe header rules, the fire code and the GF(256) field of
-// the RS(120,110) code, shared by the synthetic modulator (synth.cpp), the host object (dabplus.cpp) and the kernels (k_dabplus.hip), plus the
-// device-side types of those kernels.  The plain-numpy restatement of all of it is tests/dabplus_model.py.
+// dabplus.hpp — DAB+ audio superframes (ETSI TS 102 563): the sizes, the audio-superframe header rules and the fire code, shared by the
+// synthetic modulator (synth.cpp), the host object (dabplus.cpp) and the kernels (k_dabplus.hip), plus the device-side types of those kernels.
+// The field and the decoder of the RS(120,110) code are rs_code.hpp's.  The plain-numpy restatement of all of it is tests/dabplus_model.py.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,7 +12,8 @@
 namespace dabhip {
 
 // A sub-channel of 8 s kbit/s carries 24 s bytes per logical frame; 5 frames form a superframe of 120 s bytes: 110 s audio bytes, then 10 s RS
-// parity bytes.  Codeword j (0 <= j < s) is superframe bytes j + k s, k = 0..119 (the "virtual interleaving").
+// parity bytes.  Codeword j (0 <= j < s) is superframe bytes j + k s, k = 0..119 (the "virtual interleaving"); byte k is the coefficient of
+// x^(119 - k), and the generator has the roots alpha^0..alpha^9 (rs_code.hpp).
 constexpr int kRsN = 120, kRsK = 110, kRsRoots = 10, kRsT = 5;
 constexpr int kSfFrames = 5;
 constexpr int kFctMod = 250;
@@ -47,25 +48,6 @@ __host__ __device__ inline uint16_t fire_code(const uint8_t* b2)
     for (int k = 0; k < 8; ++k) c = (c & 0x8000u) ? ((c << 1) ^ 0x782Fu) & 0xffffu : (c << 1) & 0xffffu;
   }
   return static_cast<uint16_t>(c);
-}
-
-// GF(256) with x^8+x^4+x^3+x^2+1 (0x11D), alpha = 0x02; the RS generator is prod (x + alpha^i), i = 0..9 (first consecutive root 0).
-struct GfTables {
-  uint8_t exp[512];                         // doubled: exp[a + b] for log sums up to 508 needs no modulo
-  int16_t log[256];                         // log[0] = -1
-};
-inline void gf_build(GfTables& t)
-{
-  int x = 1;
-  for (int i = 0; i < 255; ++i) {
-    t.exp[i] = t.exp[i + 255] = static_cast<uint8_t>(x);
-    t.log[x] = static_cast<int16_t>(i);
-    x <<= 1;
-    if (x & 0x100) x ^= 0x11d;
-  }
-  t.exp[510] = t.exp[0];
-  t.exp[511] = t.exp[1];
-  t.log[0] = -1;
 }
 
 // ---- device-side records of k_dabplus.hip ----------------------------------------------------------------------------------------------------

@@ -6,7 +6,8 @@
 //   scan     one workgroup: prefix sums over the lanes' superframe and codeword counts; jobs: one thread per candidate -> the push's
 //            superframe list, codeword and data numbering
 //   rs       one lane per codeword: syndromes and the data copy (the hot path); then, for the codewords with errors only, Berlekamp-Massey,
-//            Chien search, Forney and the check by syndromes in a second kernel
+//            Chien search, Forney and the check by syndromes in a second kernel.  The code's tables, its Horner step and its solver are
+//            rs_code.hpp's, shared with k_packet.hip and k_ts.hip; the addressing (loc_at, the stride s) is this file's
 //   au       one wave per superframe: fire code, header, au_start checks, AU CRCs, the record, the counters
 //   carry    one workgroup per stream: the last 4 frames, for the next push
 //
@@ -17,6 +18,7 @@
 
 #include "dabplus.hpp"
 #include "kernels.hpp"
+#include "rs_code.hpp"
 
 namespace dabhip {
 namespace {
@@ -164,115 +166,6 @@ __global__ void __launch_bounds__(256) dabplus_jobs_kernel(int nlanes, int nsub,
   jobs[lane_sf_base[l] + i] = DabPlusJob{l / nsub, l % nsub, c.v0, c.s, static_cast<int64_t>(cw) * kRsK, cw, i};
 }
 
-// GF(256) tables in LDS: mul[i][x] = x alpha^i (i = 0..9: the syndromes' Horner steps and the Chien search's term updates), exp (doubled) and log
-struct GfShared {
-  uint8_t mul[kRsRoots][256];
-  uint8_t exp[512];
-  int16_t log[256];
-};
-
-__device__ inline uint8_t gmul(const GfShared& g, uint8_t a, uint8_t b)
-{
-  return (a && b) ? g.exp[g.log[a] + g.log[b]] : 0;
-}
-__device__ inline uint8_t ginv(const GfShared& g, uint8_t a) { return g.exp[255 - g.log[a]]; }
-
-// Error path of one codeword with syndromes S (not all zero): the unique codeword within distance 5, if there is one.  Returns the symbols
-// corrected (1..5) with their positions and error values, or -1.
-__device__ int rs_solve(const GfShared& g, const uint8_t (&S)[kRsRoots], int (&pos)[kRsT], uint8_t (&val)[kRsT])
-{
-  // Berlekamp-Massey (Massey's form: B kept as b^-1 x^m B), every index a constant once unrolled
-  uint8_t lam[kRsRoots + 1] = {1}, B[kRsRoots + 1] = {1};
-  int L = 0;
-#pragma unroll
-  for (int n = 0; n < kRsRoots; ++n) {
-    uint8_t d = 0;
-#pragma unroll
-    for (int i = 0; i <= n; ++i) d ^= gmul(g, lam[i], S[n - i]);
-#pragma unroll
-    for (int i = kRsRoots; i >= 1; --i) B[i] = B[i - 1];
-    B[0] = 0;
-    if (d) {
-      uint8_t Tn[kRsRoots + 1];
-#pragma unroll
-      for (int i = 0; i <= kRsRoots; ++i) Tn[i] = lam[i] ^ gmul(g, d, B[i]);
-      if (2 * L <= n) {
-        const uint8_t di = ginv(g, d);
-#pragma unroll
-        for (int i = 0; i <= kRsRoots; ++i) B[i] = gmul(g, di, lam[i]);
-        L = n + 1 - L;
-      }
-#pragma unroll
-      for (int i = 0; i <= kRsRoots; ++i) lam[i] = Tn[i];
-    }
-  }
-  int deg = 0;
-#pragma unroll
-  for (int i = 1; i <= kRsRoots; ++i)
-    if (lam[i]) deg = i;
-  if (deg > kRsT || deg != L) return -1;
-  // Chien search over the 120 live positions: byte k is the coefficient of x^(119 - k); it is in error iff lambda(alpha^-(119-k)) = 0.
-  // term[i] = lam[i] alpha^(-(119-k) i), stepped by alpha^i per position.
-  uint8_t term[kRsT + 1];
-#pragma unroll
-  for (int i = 0; i <= kRsT; ++i) term[i] = lam[i] ? g.exp[(g.log[lam[i]] + (255 - (119 * i) % 255)) % 255] : 0;
-  int nroots = 0;
-  for (int k = 0; k < kRsN; ++k) {
-    uint8_t v = 0;
-#pragma unroll
-    for (int i = 0; i <= kRsT; ++i) v ^= term[i];
-    if (v == 0) {
-      if (nroots < kRsT) {
-#pragma unroll
-        for (int r = 0; r < kRsT; ++r)
-          if (r == nroots) pos[r] = k;
-      }
-      ++nroots;
-    }
-#pragma unroll
-    for (int i = 1; i <= kRsT; ++i) term[i] = g.mul[i][term[i]];
-  }
-  if (nroots != deg) return -1;
-  // Forney, first consecutive root 0: e = X omega(X^-1) / lambda'(X^-1), omega = S lambda mod x^10
-  uint8_t om[kRsRoots];
-#pragma unroll
-  for (int i = 0; i < kRsRoots; ++i) {
-    uint8_t o = 0;
-#pragma unroll
-    for (int j = 0; j <= i && j <= kRsT; ++j) o ^= gmul(g, S[i - j], lam[j]);
-    om[i] = o;
-  }
-  uint8_t chk[kRsRoots];
-#pragma unroll
-  for (int i = 0; i < kRsRoots; ++i) chk[i] = S[i];
-#pragma unroll
-  for (int r = 0; r < kRsT; ++r) {
-    if (r >= deg) break;
-    const int p = 119 - pos[r];
-    const uint8_t X = g.exp[p], Xi = g.exp[255 - p];
-    uint8_t num = 0, den = 0, xp = 1;
-#pragma unroll
-    for (int i = 0; i < kRsRoots; ++i) {             // xp = Xi^i
-      num ^= gmul(g, om[i], xp);
-      if ((i & 1) && i <= kRsT) den ^= gmul(g, lam[i], g.exp[(g.log[Xi] * (i - 1)) % 255]);
-      xp = gmul(g, xp, Xi);
-    }
-    if (!den) return -1;
-    const uint8_t e = gmul(g, X, gmul(g, num, ginv(g, den)));
-    val[r] = e;
-    uint8_t xq = e;                                  // the corrected word's syndromes: S_i + sum e X^i
-#pragma unroll
-    for (int i = 0; i < kRsRoots; ++i) {
-      chk[i] ^= xq;
-      xq = gmul(g, xq, X);
-    }
-  }
-  uint8_t any = 0;
-#pragma unroll
-  for (int i = 0; i < kRsRoots; ++i) any |= chk[i];
-  return any ? -1 : deg;
-}
-
 // the superframe of codeword cw: the last job with cw_base <= cw
 __device__ inline int job_of(const DabPlusJob* jobs, int nsf, int cw)
 {
@@ -290,7 +183,7 @@ __device__ inline int job_of(const DabPlusJob* jobs, int nsf, int cw)
 __global__ void __launch_bounds__(256) dabplus_syndrome_kernel(const DabPlusJob* jobs, const int* totals, const DabPlusLoc* loc, int maxv, int nsub,
                                                               const uint8_t* gf_global, uint8_t* data, uint8_t* cw_status, uint32_t* syn)
 {
-  __shared__ uint32_t mul_w[kRsRoots * 64];          // GfShared::mul, x alpha^i for i = 0..9
+  __shared__ uint32_t mul_w[kRsRoots * 64];          // GfRs::mul, x alpha^i for i = 0..9
   const uint32_t* src = reinterpret_cast<const uint32_t*>(gf_global);
   for (int i = threadIdx.x; i < kRsRoots * 64; i += blockDim.x) mul_w[i] = src[i];
   __syncthreads();
@@ -309,21 +202,14 @@ __global__ void __launch_bounds__(256) dabplus_syndrome_kernel(const DabPlusJob*
       const uint8_t b = p[r * s];
       const int k = 24 * m + r;
       if (k < kRsK) out[k * s] = b;
-      S[0] ^= b;
-#pragma unroll
-      for (int i = 1; i < kRsRoots; ++i) S[i] = mul[i * 256 + S[i]] ^ b;
+      rs_horner(mul, S, b);
     }
   }
   uint32_t any = 0;
 #pragma unroll
   for (int i = 0; i < kRsRoots; ++i) any |= S[i];
   cw_status[cw] = any ? 0xfe : 0;
-  if (any) {
-    uint32_t* o = syn + static_cast<int64_t>(cw) * 4;
-    o[0] = S[0] | (S[1] << 8) | (S[2] << 16) | (S[3] << 24);
-    o[1] = S[4] | (S[5] << 8) | (S[6] << 16) | (S[7] << 24);
-    o[2] = S[8] | (S[9] << 8);
-  }
+  if (any) rs_pack(S, syn + static_cast<int64_t>(cw) * 4);
 }
 
 // The error path of the codewords the syndrome kernel left (status 0xfe): corrected bytes written over the copied ones, status = symbols
@@ -331,7 +217,7 @@ __global__ void __launch_bounds__(256) dabplus_syndrome_kernel(const DabPlusJob*
 __global__ void __launch_bounds__(256) dabplus_decode_kernel(const DabPlusJob* jobs, const int* totals, const DabPlusLoc* loc, int maxv, int nsub,
                                                             const uint8_t* gf_global, uint8_t* data, uint8_t* cw_status, const uint32_t* syn)
 {
-  __shared__ GfShared g;
+  __shared__ GfRs<kRsRoots> g;
   const int nsf = totals[0], ncw = totals[1];
   const int cw = blockIdx.x * blockDim.x + threadIdx.x;
   const bool need = cw < ncw && cw_status[cw] == 0xfe;
@@ -339,7 +225,7 @@ __global__ void __launch_bounds__(256) dabplus_decode_kernel(const DabPlusJob* j
   {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(gf_global);
     uint32_t* dst = reinterpret_cast<uint32_t*>(&g);
-    for (int i = threadIdx.x; i < static_cast<int>(sizeof(GfShared) / 4); i += blockDim.x) dst[i] = src[i];
+    for (int i = threadIdx.x; i < static_cast<int>(sizeof(g) / 4); i += blockDim.x) dst[i] = src[i];
   }
   __syncthreads();
   if (!need) return;
@@ -351,7 +237,7 @@ __global__ void __launch_bounds__(256) dabplus_decode_kernel(const DabPlusJob* j
   for (int i = 0; i < kRsRoots; ++i) S8[i] = static_cast<uint8_t>(o[i >> 2] >> (8 * (i & 3)));
   int pos[kRsT] = {0};
   uint8_t val[kRsT] = {0};
-  const int n = rs_solve(g, S8, pos, val);
+  const int n = rs_solve<kRsN, kRsRoots, kRsT>(g, S8, pos, val);
   if (n < 0) {
     cw_status[cw] = 0xff;
     return;
@@ -524,21 +410,6 @@ hipError_t launch_dabplus_carry(const DabPlusFrames& fr, int nstreams, uint8_t* 
 {
   if (nstreams > 0) dabplus_carry_kernel<<<nstreams, 256, 0, stream>>>(fr, carry_next);
   return hipGetLastError();
-}
-
-size_t dabplus_gf_table_bytes() { return sizeof(GfShared); }
-
-void dabplus_gf_table_fill(uint8_t* out)
-{
-  GfTables t;
-  gf_build(t);
-  GfShared g;
-  for (int i = 0; i < kRsRoots; ++i)
-    for (int x = 0; x < 256; ++x) g.mul[i][x] = x ? t.exp[t.log[x] + i] : 0;
-  for (int i = 0; i < 512; ++i) g.exp[i] = t.exp[i];
-  for (int i = 0; i < 256; ++i) g.log[i] = t.log[i];
-  const uint8_t* src = reinterpret_cast<const uint8_t*>(&g);
-  for (size_t i = 0; i < sizeof g; ++i) out[i] = src[i];
 }
 
 }  // namespace dabhip

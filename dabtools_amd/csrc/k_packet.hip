@@ -9,7 +9,8 @@
 //   gather   one thread per cell of every unit: its 24 bytes into the contiguous cell buffer (103 cells per FEC frame)
 //   rs       one lane per code word, 12 per FEC frame side by side: the 16 syndromes by Horner through LDS tables (the hot path); then, for the
 //            code words with errors only, Berlekamp-Massey, Chien search, Forney and the check by syndromes in a second kernel, which
-//            corrects the cell buffer in place
+//            corrects the cell buffer in place.  The code's tables, its Horner step and its solver are rs_code.hpp's, shared with
+//            k_dabplus.hip and k_ts.hip; the addressing (fec_byte_offset) is this stage's
 //   cand     one lane per data cell: header check and CRC of the packet that would start there
 //   walk     one lane per unit over the candidates' flags: a record per cell (length 0: no packet starts here), the counters
 //   carry    one workgroup per lane: its unconsumed cells (at most 102), for the next push
@@ -19,10 +20,9 @@
 
 #include <cstdint>
 
-#include "dabplus.hpp"
 #include "kernels.hpp"
 #include "packet.hpp"
-#include "rs204.hpp"
+#include "rs_code.hpp"
 
 namespace dabhip {
 namespace {
@@ -243,7 +243,7 @@ __global__ void __launch_bounds__(256) packet_gather_kernel(PacketFrames fr, con
 __global__ void __launch_bounds__(256) packet_syndrome_kernel(const PacketUnit* units, const int* totals, const uint8_t* gf_global, const uint8_t* cells,
                                                              uint8_t* cw_status, uint32_t* syn)
 {
-  __shared__ uint32_t mul_w[kPkRoots * 64];          // Gf204::mul
+  __shared__ uint32_t mul_w[kPkRoots * 64];          // GfRs::mul
   const uint32_t* src = reinterpret_cast<const uint32_t*>(gf_global);
   for (int i = threadIdx.x; i < kPkRoots * 64; i += blockDim.x) mul_w[i] = src[i];
   __syncthreads();
@@ -261,19 +261,13 @@ __global__ void __launch_bounds__(256) packet_syndrome_kernel(const PacketUnit* 
 #pragma unroll 4
   for (int c = 0; c < kPkN; ++c) {
     const uint8_t b = z[fec_byte_offset(r, c)];
-    S[0] ^= b;
-#pragma unroll
-    for (int i = 1; i < kPkRoots; ++i) S[i] = mul[i * 256 + S[i]] ^ b;
+    rs_horner(mul, S, b);
   }
   uint32_t any = 0;
 #pragma unroll
   for (int i = 0; i < kPkRoots; ++i) any |= S[i];
   cw_status[cw] = any ? 0xfe : 0;
-  if (any) {
-    uint32_t* o = syn + static_cast<int64_t>(cw) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = S[4 * i] | (S[4 * i + 1] << 8) | (S[4 * i + 2] << 16) | (S[4 * i + 3] << 24);
-  }
+  if (any) rs_pack(S, syn + static_cast<int64_t>(cw) * 4);
 }
 
 // The error path of the code words the syndrome kernel left (status 0xfe): the table bytes corrected in place in the cell buffer, status = symbols
@@ -281,14 +275,14 @@ __global__ void __launch_bounds__(256) packet_syndrome_kernel(const PacketUnit* 
 __global__ void __launch_bounds__(256) packet_decode_kernel(const PacketUnit* units, const int* totals, const uint8_t* gf_global, uint8_t* cells,
                                                            uint8_t* cw_status, const uint32_t* syn)
 {
-  __shared__ Gf204 g;
+  __shared__ GfRs<kPkRoots> g;
   const int cw = blockIdx.x * blockDim.x + threadIdx.x;
   const bool need = cw < totals[0] * kPkRows && cw_status[cw] == 0xfe;
   if (!__syncthreads_or(need)) return;
   {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(gf_global);
     uint32_t* dst = reinterpret_cast<uint32_t*>(&g);
-    for (int i = threadIdx.x; i < static_cast<int>(sizeof(Gf204) / 4); i += blockDim.x) dst[i] = src[i];
+    for (int i = threadIdx.x; i < static_cast<int>(sizeof(g) / 4); i += blockDim.x) dst[i] = src[i];
   }
   __syncthreads();
   if (!need) return;
@@ -300,7 +294,7 @@ __global__ void __launch_bounds__(256) packet_decode_kernel(const PacketUnit* un
   for (int i = 0; i < kPkRoots; ++i) S8[i] = static_cast<uint8_t>(o[i >> 2] >> (8 * (i & 3)));
   int pos[kPkT] = {0};
   uint8_t val[kPkT] = {0};
-  const int n = rs204_solve(g, S8, pos, val);
+  const int n = rs_solve<kPkN, kPkRoots, kPkT>(g, S8, pos, val);
   if (n < 0) {
     cw_status[cw] = 0xff;
     return;
@@ -451,21 +445,6 @@ hipError_t launch_packet_carry(const PacketFrames& fr, int nlanes, const PacketL
 {
   if (nlanes > 0) packet_carry_kernel<<<nlanes, 128, 0, stream>>>(fr, loc, maxv, nsub, carry, ncar_in, ncar_out, lo, carry_next);
   return hipGetLastError();
-}
-
-size_t packet_gf_table_bytes() { return sizeof(Gf204); }
-
-void packet_gf_table_fill(uint8_t* out)
-{
-  GfTables t;
-  gf_build(t);
-  Gf204 g;
-  for (int i = 0; i < kPkRoots; ++i)
-    for (int x = 0; x < 256; ++x) g.mul[i][x] = x ? t.exp[t.log[x] + i] : 0;
-  for (int i = 0; i < 512; ++i) g.exp[i] = t.exp[i];
-  for (int i = 0; i < 256; ++i) g.log[i] = t.log[i];
-  const uint8_t* src = reinterpret_cast<const uint8_t*>(&g);
-  for (size_t i = 0; i < sizeof g; ++i) out[i] = src[i];
 }
 
 }  // namespace dabhip

@@ -13,8 +13,10 @@
 //   scan      one workgroup: prefix sums over the lanes' unit counts; jobs: one workgroup per lane -> the push's unit list
 //   gather    one thread per byte of every code word: P + k + 204 (k mod 12) read from the carry or the frame where it lies, byte by byte
 //             (so aligned or not), into the word buffer (ts.hpp: ts_word_byte)
-//   syndrome  one lane per code word: the 16 syndromes by Horner through an LDS table, four bytes per load, 64 lanes 256 contiguous bytes
-//   decode    the code words with errors only: Berlekamp-Massey, Chien, Forney and the check by syndromes (rs204.hpp), in place
+//   syndrome  one lane per code word: the 16 syndromes by Horner (rs_code.hpp's step) through an LDS table, four bytes per load, 64 lanes 256
+//             contiguous bytes
+//   decode    the code words with errors only: Berlekamp-Massey, Chien, Forney and the check by syndromes (rs_code.hpp's rs_solve, the packet
+//             stage's tables), in place
 //   parse     one thread per packet: its record, its 188 bytes, the counters
 //   carry     one workgroup per lane: its unconsumed bytes (at most 2447), for the next push
 //
@@ -24,7 +26,7 @@
 #include <cstdint>
 
 #include "kernels.hpp"
-#include "rs204.hpp"
+#include "rs_code.hpp"
 #include "ts.hpp"
 
 namespace dabhip {
@@ -361,7 +363,7 @@ __global__ void __launch_bounds__(256) ts_gather_kernel(PacketFrames fr, const T
 // here; the others leave their syndromes for the decode kernel, which keeps this loop's register count low.
 __global__ void __launch_bounds__(256) ts_syndrome_kernel(const int* totals, const uint8_t* gf_global, const uint8_t* words, uint8_t* cw_status, uint32_t* syn)
 {
-  __shared__ uint32_t mul_w[kPkRoots * 64];          // Gf204::mul
+  __shared__ uint32_t mul_w[kPkRoots * 64];          // GfRs::mul
   const uint32_t* src = reinterpret_cast<const uint32_t*>(gf_global);
   for (int i = threadIdx.x; i < kPkRoots * 64; i += blockDim.x) mul_w[i] = src[i];
   __syncthreads();
@@ -374,36 +376,27 @@ __global__ void __launch_bounds__(256) ts_syndrome_kernel(const int* totals, con
   for (int c = 0; c < kTsSlot / 4; ++c) {
     const uint32_t four = z[c * 64];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const uint32_t b = (four >> (8 * j)) & 0xff;
-      S[0] ^= b;
-#pragma unroll
-      for (int i = 1; i < kPkRoots; ++i) S[i] = mul[i * 256 + S[i]] ^ b;
-    }
+    for (int j = 0; j < 4; ++j) rs_horner(mul, S, (four >> (8 * j)) & 0xff);
   }
   uint32_t any = 0;
 #pragma unroll
   for (int i = 0; i < kPkRoots; ++i) any |= S[i];
   cw_status[w] = any ? 0xfe : 0;
-  if (any) {
-    uint32_t* o = syn + w * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = S[4 * i] | (S[4 * i + 1] << 8) | (S[4 * i + 2] << 16) | (S[4 * i + 3] << 24);
-  }
+  if (any) rs_pack(S, syn + w * 4);
 }
 
 // The error path of the code words the syndrome kernel left (status 0xfe): corrected in place in the word buffer, status = symbols corrected
 // or 0xff.  A workgroup without such a code word returns before it loads the tables.
 __global__ void __launch_bounds__(256) ts_decode_kernel(const int* totals, const uint8_t* gf_global, uint8_t* words, uint8_t* cw_status, const uint32_t* syn)
 {
-  __shared__ Gf204 g;
+  __shared__ GfRs<kPkRoots> g;
   const int64_t w = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   const bool need = w < totals[kTsTotUnits] && cw_status[w] == 0xfe;
   if (!__syncthreads_or(need)) return;
   {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(gf_global);
     uint32_t* dst = reinterpret_cast<uint32_t*>(&g);
-    for (int i = threadIdx.x; i < static_cast<int>(sizeof(Gf204) / 4); i += blockDim.x) dst[i] = src[i];
+    for (int i = threadIdx.x; i < static_cast<int>(sizeof(g) / 4); i += blockDim.x) dst[i] = src[i];
   }
   __syncthreads();
   if (!need) return;
@@ -413,7 +406,7 @@ __global__ void __launch_bounds__(256) ts_decode_kernel(const int* totals, const
   for (int i = 0; i < kPkRoots; ++i) S8[i] = static_cast<uint8_t>(o[i >> 2] >> (8 * (i & 3)));
   int pos[kPkT] = {0};
   uint8_t val[kPkT] = {0};
-  const int n = rs204_solve(g, S8, pos, val);
+  const int n = rs_solve<kPkN, kPkRoots, kPkT>(g, S8, pos, val);
   if (n < 0) {
     cw_status[w] = 0xff;
     return;

@@ -1,4 +1,4 @@
-// kernels.hpp — host-callable launchers of the HIP kernels (k_sync.hip, k_fft.hip, k_decode.hip).
+// kernels.hpp — host-callable launchers of the HIP kernels.  The tables of the Reed-Solomon launchers (gf_tables) are rs_code.hpp's GfRs.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -189,8 +189,9 @@ hipError_t launch_eti_finish(const EtiFrameMeta* meta, int nframes, const uint8_
 // k_dabplus.hip: DAB+ superframes out of ETI frames (dabplus.hpp has the types, dabhip.h the sync rule).  locate: the sub-channels of every
 // (stream, frame) into loc [nstreams][maxv][nsub]; sync + scan + jobs: the candidates of every (stream, sub-channel) (at most cap each), the push's
 // superframe list, totals = {superframes, codewords}; rs: the ncw codewords into data (110 s bytes per superframe) and cw_status (symbols
-// corrected, 0xff = failed), syn: 16 bytes of scratch per codeword; au: one record per superframe and the counters (crc_tab: the CRC-16 byte table, then
-// x^(8 n) mod G for n < kRsK kMaxS; data: 16 bytes of slack at its end); carry: the last 4 frames of every stream.
+// corrected, 0xff = failed), gf_tables: a GfRs<kRsRoots> filled by rs_tables_fill (rs_code.hpp), syn: 16 bytes of scratch per codeword; au: one
+// record per superframe and the counters (crc_tab: the CRC-16 byte table, then x^(8 n) mod G for n < kRsK kMaxS; data: 16 bytes of slack at its
+// end); carry: the last 4 frames of every stream.
 hipError_t launch_dabplus_locate(const DabPlusFrames& fr, const int32_t* subch, int nsub, int nstreams, int maxv, DabPlusLoc* loc, hipStream_t stream);
 hipError_t launch_dabplus_sync(const DabPlusFrames& fr, int nstreams, int nsub, int maxv, const DabPlusLoc* loc, DabPlusSync* sync, DabPlusCand* cand,
                                int cap, int* ncand, int* lane_cw, int64_t* counters, DabPlusJob* jobs, int* lane_sf_base, int* lane_cw_base, int* totals,
@@ -200,13 +201,12 @@ hipError_t launch_dabplus_rs(const DabPlusJob* jobs, const int* totals, int ncw,
 hipError_t launch_dabplus_au(const DabPlusJob* jobs, int nsf, const DabPlusLoc* loc, int maxv, int nsub, const uint8_t* data, const uint8_t* cw_status,
                              const uint16_t* crc_tab, dabhip_dabplus_sf* recs, int64_t* counters, hipStream_t stream);
 hipError_t launch_dabplus_carry(const DabPlusFrames& fr, int nstreams, uint8_t* carry_next, hipStream_t stream);
-size_t dabplus_gf_table_bytes();                 // the rs kernel's GF(256) tables: their size, and filled on the host
-void dabplus_gf_table_fill(uint8_t* out);
 
 // k_packet.hip: packet-mode data out of ETI frames (packet.hpp has the types and the sync rule, dabhip.h the rules in words).  locate: the
 // sub-channels of every (stream, new frame) into loc [nstreams][maxv][nsub]; sync + scan + jobs: every lane's virtual cell numbering, its units (at
 // most cap each) and the push's unit list, totals = {units, buffer cells}; gather: the units' cells into the cell buffer; rs: the 12 code words of
-// every RS-decoded frame, corrected in place (cw_status: symbols corrected, 0xff = failed; syn: 16 bytes of scratch per code word); cand: per
+// every RS-decoded frame, corrected in place (gf_tables: a GfRs<kPkRoots> filled by rs_tables_fill; cw_status: symbols corrected, 0xff = failed;
+// syn: 16 bytes of scratch per code word); cand: per
 // buffer cell, the length of the packet the walk may take there (crc_tab: the CRC-16 byte table); walk: a record per buffer cell (length 0: none)
 // and the counters; carry: every lane's unconsumed cells (at most 102).
 hipError_t launch_packet_locate(const PacketFrames& fr, const int32_t* subch, int nsub, int nstreams, int maxv, PacketLoc* loc, hipStream_t stream);
@@ -222,15 +222,13 @@ hipError_t launch_packet_walk(const PacketUnit* units, const int* totals, int nu
                               dabhip_packet_rec* recs, int64_t* counters, int* npackets, hipStream_t stream);
 hipError_t launch_packet_carry(const PacketFrames& fr, int nlanes, const PacketLoc* loc, int maxv, int nsub, const uint8_t* carry, const int* ncar_in,
                                const int* ncar_out, const int* lo, uint8_t* carry_next, hipStream_t stream);
-size_t packet_gf_table_bytes();
-void packet_gf_table_fill(uint8_t* out);
 
 // k_ts.hip: MPEG-2 TS packets out of ETI frames (ts.hpp has the types, ts_sync.hpp the sync rule and the position map, dabhip.h the rules in
 // words).  locate (+ layout): the sub-channels of every (stream, new frame) into loc [nstreams][maxv][nsub], every lane's virtual positions and
 // its words in the run-flag buffer (flag_cap words; totals zeroed before); runs: a bit per position, "a run of five starts here"; sync: a wave per
 // lane, its units into at most cap slots; jobs (scan + jobs): the push's unit list, totals[0] = units; gather: the units' 204 bytes into the word
 // buffer (ts_word_byte); syndrome / decode: the code words, corrected in place (cw_status: symbols corrected, 0xff = failed; syn: 16 bytes of
-// scratch per code word; the tables are packet_gf_table_fill's); parse: a record and 188 bytes per unit, the counters; carry: every lane's
+// scratch per code word; gf_tables as the packet stage's); parse: a record and 188 bytes per unit, the counters; carry: every lane's
 // unconsumed bytes (at most 2447).
 hipError_t launch_ts_locate(const PacketFrames& fr, const int32_t* subch, int nsub, int nstreams, int maxv, TsLoc* loc, const TsSync* sync, TsLane* lanes, int flag_cap,
                             int* totals, hipStream_t stream);

@@ -11,6 +11,7 @@
 #include "../../include/dabhip.h"
 #include "dab_bits.hpp"
 #include "kernels.hpp"
+#include "rs_code.hpp"
 #include "packet.hpp"
 #include "packet_groups.hpp"
 #include "stage_frame.hpp"
@@ -89,22 +90,22 @@ extern "C" dabhip_packet* dabhip_packet_create(int device, int nstreams, const i
   d->nstreams = nstreams;
   d->nsub = nsub;
   const size_t nlanes = static_cast<size_t>(nstreams) * nsub;
-  std::vector<uint8_t> gf(packet_gf_table_bytes());
-  packet_gf_table_fill(gf.data());
+  GfRs<kPkRoots> gf;
+  rs_tables_fill(gf);
   std::vector<uint16_t> crc(256);
   for (int v = 0; v < 256; ++v) {
     const uint8_t b = static_cast<uint8_t>(v);
     crc[v] = crc16_ccitt(&b, 1, 0);   // the CRC register after byte v from 0: the kernel's table-driven step
   }
   const size_t carry_bytes = nlanes * kPkCarry * kPkCell;
-  bool good = d->subch.reserve(nsub) && d->fec.reserve(nsub) && d->sync.reserve(nlanes) && d->counters.reserve(nlanes * kPkCntN) && d->gf.reserve(gf.size()) &&
+  bool good = d->subch.reserve(nsub) && d->fec.reserve(nsub) && d->sync.reserve(nlanes) && d->counters.reserve(nlanes * kPkCntN) && d->gf.reserve(sizeof gf) &&
               d->crc_tab.reserve(crc.size()) && d->carry[0].reserve(carry_bytes) && d->carry[1].reserve(carry_bytes) && d->totals.reserve(4) &&
               d->nunits.reserve(nlanes) && d->lane_buf.reserve(nlanes) && d->ncar_in.reserve(nlanes) && d->ncar_out.reserve(nlanes) && d->lo.reserve(nlanes) &&
               d->lane_unit_base.reserve(nlanes + 1) && d->lane_buf_base.reserve(nlanes + 1);
   good = good && ok(hipMemcpy(d->subch.get(), subch_ids, sizeof(int32_t) * nsub, hipMemcpyHostToDevice), "upload") &&
          ok(hipMemcpy(d->fec.get(), fec_flags, static_cast<size_t>(nsub), hipMemcpyHostToDevice), "upload") &&
          ok(hipMemset(d->sync.get(), 0, sizeof(PacketSync) * nlanes), "clear") && ok(hipMemset(d->counters.get(), 0, sizeof(int64_t) * nlanes * kPkCntN), "clear") &&
-         ok(hipMemcpy(d->gf.get(), gf.data(), gf.size(), hipMemcpyHostToDevice), "upload") &&
+         ok(hipMemcpy(d->gf.get(), &gf, sizeof gf, hipMemcpyHostToDevice), "upload") &&
          ok(hipMemcpy(d->crc_tab.get(), crc.data(), crc.size() * 2, hipMemcpyHostToDevice), "upload");
   return good ? d.release() : nullptr;
 }

@@ -16,7 +16,7 @@ namespace dabhip {
 
 // A sub-channel of 8 s kbit/s carries s cells of 24 bytes per ETI frame.  An FEC frame is 94 data cells (the 2256-byte application table) and
 // 9 FEC cells of 2 header and 22 RS bytes: 192 parity bytes, then 6 zero bytes.  Z = table | parity (2448 bytes); code word r (0..11) is
-// Z[r + 12 c], c = 0..203, byte c the coefficient of x^(203 - c).  Field and generator roots as the DAB+ code's (dabplus.hpp: GfTables).
+// Z[r + 12 c], c = 0..203, byte c the coefficient of x^(203 - c).  Field, generator roots (alpha^0..alpha^15) and decoder: rs_code.hpp.
 constexpr int kPkCell = 24;
 constexpr int kPkDataCells = 94, kPkFecCells = 9, kPkFrameCells = 103;
 constexpr int kPkTable = kPkDataCells * kPkCell;         // 2256

@@ -13,6 +13,7 @@
 #include "dab_tables.hpp"
 #include "dabplus.hpp"
 #include "packet_sync.hpp"
+#include "rs_code.hpp"
 #include "ts_sync.hpp"
 #include "synth.hpp"
 #include "tii_detect.hpp"
@@ -146,7 +147,7 @@ bool validate(const dabhip_synth_cfg& cfg)
   return true;
 }
 
-// ---- DAB+ superframes (ETSI TS 102 563) --------------------------------------------------------------------------------------------------------
+// ---- the outer codes' field and encoder (rs_code.hpp has the codes) -----------------------------------------------------------------------------
 const GfTables& gf()
 {
   struct Init {
@@ -162,14 +163,15 @@ inline uint8_t gf_mul(uint8_t a, uint8_t b)
   return (a && b) ? gf().exp[gf().log[a] + gf().log[b]] : 0;
 }
 
-// coefficients of prod_{i=0..9} (x + alpha^i), highest degree first (gen[0] = 1)
+// coefficients of prod_{i=0..kRoots-1} (x + alpha^i), highest degree first (gen[0] = 1)
+template <int kRoots>
 const uint8_t* rs_generator()
 {
   struct Init {
-    uint8_t g[kRsRoots + 1] = {1};
+    uint8_t g[kRoots + 1] = {1};
     Init()
     {
-      for (int i = 0; i < kRsRoots; ++i) {
+      for (int i = 0; i < kRoots; ++i) {
         const uint8_t r = gf().exp[i];
         for (int k = i + 1; k >= 1; --k) g[k] ^= gf_mul(g[k - 1], r);
       }
@@ -179,6 +181,21 @@ const uint8_t* rs_generator()
   return g.g;
 }
 
+// the kRoots parity bytes of the systematic code word whose ndata data bytes are data[0], data[dstride], ...: parity[0], parity[pstride], ...
+template <int kRoots>
+void rs_parity(int ndata, const uint8_t* data, size_t dstride, uint8_t* parity, size_t pstride)
+{
+  const uint8_t* g = rs_generator<kRoots>();
+  uint8_t rem[kRoots] = {0};
+  for (int k = 0; k < ndata; ++k) {
+    const uint8_t fb = data[k * dstride] ^ rem[0];
+    for (int q = 0; q < kRoots - 1; ++q) rem[q] = rem[q + 1] ^ gf_mul(fb, g[q + 1]);
+    rem[kRoots - 1] = gf_mul(fb, g[kRoots]);
+  }
+  for (int q = 0; q < kRoots; ++q) parity[q * pstride] = rem[q];
+}
+
+// ---- DAB+ superframes (ETSI TS 102 563) --------------------------------------------------------------------------------------------------------
 // the 110 s unprotected bytes of superframe n of a DAB+ slot of 8 s kbit/s
 void dabplus_superframe(const dabhip_synth_cfg& cfg, int n, int slot, int s, uint8_t* out)
 {
@@ -233,39 +250,14 @@ void dabplus_protected_part(const dabhip_synth_cfg& cfg, int n, int part, int sl
 {
   std::vector<uint8_t> sf(static_cast<size_t>(kRsN) * s);
   dabplus_superframe(cfg, n, slot, s, sf.data());
-  const uint8_t* g = rs_generator();
-  for (int j = 0; j < s; ++j) {
-    uint8_t rem[kRsRoots] = {0};
-    for (int k = 0; k < kRsK; ++k) {
-      const uint8_t fb = sf[j + k * s] ^ rem[0];
-      for (int q = 0; q < kRsRoots - 1; ++q) rem[q] = rem[q + 1] ^ gf_mul(fb, g[q + 1]);
-      rem[kRsRoots - 1] = gf_mul(fb, g[kRsRoots]);
-    }
-    for (int q = 0; q < kRsRoots; ++q) sf[static_cast<size_t>(kRsK + q) * s + j] = rem[q];
-  }
+  uint8_t* parity = sf.data() + static_cast<size_t>(kRsK) * s;
+  for (int j = 0; j < s; ++j) rs_parity<kRsRoots>(kRsK, sf.data() + j, s, parity + j, s);
   std::memcpy(out, sf.data() + static_cast<size_t>(24) * s * part, static_cast<size_t>(24) * s);
 }
 
 int floor_div(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
 // ---- packet mode (ETSI EN 300 401 clauses 5.3.2, 5.3.3, 5.3.5; dabhip.h: dabhip_packet has the formats) ----------------------------------------
-// coefficients of prod_{i=0..15} (x + alpha^i), highest degree first
-const uint8_t* rs204_generator()
-{
-  struct Init {
-    uint8_t g[kPkRoots + 1] = {1};
-    Init()
-    {
-      for (int i = 0; i < kPkRoots; ++i) {
-        const uint8_t r = gf().exp[i];
-        for (int k = i + 1; k >= 1; --k) g[k] ^= gf_mul(g[k - 1], r);
-      }
-    }
-  };
-  static const Init g;
-  return g.g;
-}
-
 // the addresses a packet slot's groups go out on: two or three, from the slot's key
 int packet_addresses(const dabhip_synth_cfg& cfg, int slot, int* out3)
 {
@@ -393,17 +385,8 @@ void packet_unit_cells(const dabhip_synth_cfg& cfg, int slot, int j, int ncells,
   out.assign(static_cast<size_t>(fec ? kPkFrameCells : ncells) * kPkCell, 0);
   packet_unit(cfg, slot, j, ncells, out.data(), nullptr);
   if (fec) {
-    const uint8_t* g = rs204_generator();
     uint8_t parity[kPkRoots * kPkRows + 6] = {0};
-    for (int r = 0; r < kPkRows; ++r) {
-      uint8_t rem[kPkRoots] = {0};
-      for (int c = 0; c < kPkK; ++c) {
-        const uint8_t fb = out[r + kPkRows * c] ^ rem[0];
-        for (int q = 0; q < kPkRoots - 1; ++q) rem[q] = rem[q + 1] ^ gf_mul(fb, g[q + 1]);
-        rem[kPkRoots - 1] = gf_mul(fb, g[kPkRoots]);
-      }
-      for (int q = 0; q < kPkRoots; ++q) parity[r + kPkRows * q] = rem[q];
-    }
+    for (int r = 0; r < kPkRows; ++r) rs_parity<kPkRoots>(kPkK, out.data() + r, kPkRows, parity + r, kPkRows);
     for (int i = 0; i < kPkFecCells; ++i) {
       uint8_t* cell = out.data() + (kPkDataCells + i) * kPkCell;
       cell[0] = static_cast<uint8_t>((i << 2) | (kPkFecAddress >> 8));
@@ -472,14 +455,7 @@ void ts_word(const dabhip_synth_cfg& cfg, int slot, int64_t n, uint8_t* out)
     const uint64_t v = key(cfg.seed, kDomTs, wk, static_cast<uint64_t>(i));
     for (int b = 0; b < 8 && i + b < kTsData; ++b) out[i + b] = static_cast<uint8_t>(v >> (8 * b));
   }
-  const uint8_t* g = rs204_generator();
-  uint8_t rem[kPkRoots] = {0};
-  for (int c = 0; c < kTsData; ++c) {
-    const uint8_t fb = out[c] ^ rem[0];
-    for (int q = 0; q < kPkRoots - 1; ++q) rem[q] = rem[q + 1] ^ gf_mul(fb, g[q + 1]);
-    rem[kPkRoots - 1] = gf_mul(fb, g[kPkRoots]);
-  }
-  std::memcpy(out + kTsData, rem, kPkRoots);
+  rs_parity<kPkRoots>(kTsData, out, 1, out + kTsData, 1);
 }
 
 // n bytes of a TS slot from stream position x on (bytes counted from logical CIF 0's first): the byte at x is byte k = (x - ts_phase) mod 204 of

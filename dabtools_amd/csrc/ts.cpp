@@ -10,6 +10,7 @@
 
 #include "../../include/dabhip.h"
 #include "kernels.hpp"
+#include "rs_code.hpp"
 #include "stage_frame.hpp"
 #include "ts.hpp"
 
@@ -85,15 +86,15 @@ extern "C" dabhip_ts* dabhip_ts_create(int device, int nstreams, const int32_t* 
   d->nstreams = nstreams;
   d->nsub = nsub;
   const size_t nlanes = static_cast<size_t>(nstreams) * nsub;
-  std::vector<uint8_t> gf(packet_gf_table_bytes());
-  packet_gf_table_fill(gf.data());
+  GfRs<kPkRoots> gf;
+  rs_tables_fill(gf);
   const size_t carry_bytes = nlanes * kTsCarryStride;
-  bool good = d->subch.reserve(nsub) && d->sync.reserve(nlanes) && d->lanes.reserve(nlanes) && d->counters.reserve(nlanes * kTsCntN) && d->gf.reserve(gf.size()) &&
+  bool good = d->subch.reserve(nsub) && d->sync.reserve(nlanes) && d->lanes.reserve(nlanes) && d->counters.reserve(nlanes * kTsCntN) && d->gf.reserve(sizeof gf) &&
               d->carry[0].reserve(carry_bytes) && d->carry[1].reserve(carry_bytes) && d->totals.reserve(kTsTotN) && d->nunits.reserve(nlanes) &&
               d->lane_unit_base.reserve(nlanes + 1);
   good = good && ok(hipMemcpy(d->subch.get(), subch_ids, sizeof(int32_t) * nsub, hipMemcpyHostToDevice), "upload") &&
          ok(hipMemset(d->sync.get(), 0, sizeof(TsSync) * nlanes), "clear") && ok(hipMemset(d->counters.get(), 0, sizeof(int64_t) * nlanes * kTsCntN), "clear") &&
-         ok(hipMemcpy(d->gf.get(), gf.data(), gf.size(), hipMemcpyHostToDevice), "upload");
+         ok(hipMemcpy(d->gf.get(), &gf, sizeof gf, hipMemcpyHostToDevice), "upload");
   return good ? d.release() : nullptr;
 }
 

@@ -15,7 +15,7 @@
 
 namespace dabhip {
 
-// A code word is 204 bytes, 188 TS bytes and 16 parity bytes (the code is rs204.hpp's).  Byte k of the word whose slot starts at stream
+// A code word is 204 bytes, 188 TS bytes and 16 parity bytes (the code is packet_sync.hpp's, its decoder rs_code.hpp's).  Byte k of the word whose slot starts at stream
 // position P lies at P + k + 204 (k mod 12): the convolutional interleaver (I = 12, M = 17) in closed form.  So a word needs the
 // kTsLook = 203 + 204 * 11 + 1 bytes from P on, and a lane carries kTsLook - 1 bytes at most from push to push.
 constexpr int kTsSlot = 204, kTsData = 188;
