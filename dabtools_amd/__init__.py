@@ -608,6 +608,37 @@ def _sample_bytes(what, nstreams, arrays):
     return [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in arrays]
 
 
+def _one_stream_counts(what, nstreams, n):
+    """The counts of a push that names none: all n items are the one stream's."""
+    _need(nstreams == 1, what + ": counts needed for several streams")
+    return [n]
+
+
+def _eti_frames_arg(what, nstreams, frames, counts):
+    """The frames of a push of ETI frames (DabPlus.push has the forms) as (src, cnt, on_device, keepalive): the address, the per-stream counts
+    as the C entry takes them, and for host frames the array that holds them (else None), which the caller keeps alive."""
+    if isinstance(frames, tuple):
+        (ptr, counts), arr = frames, None
+    elif isinstance(frames, list):
+        counts = [np.asarray(f).size // ETI_BYTES for f in frames]
+        arr = np.ascontiguousarray(np.concatenate([np.asarray(f, dtype=np.uint8).reshape(-1) for f in frames]) if frames else np.zeros(0, np.uint8))
+    else:
+        arr = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
+        if counts is None:
+            counts = _one_stream_counts(what, nstreams, arr.size // ETI_BYTES)
+    cnt = (C.c_int64 * nstreams)(*[int(c) for c in counts])
+    return C.c_void_p(ptr if arr is None else arr.ctypes.data), cnt, int(arr is None), arr
+
+
+def _fetch(fn, what, dtype, *at):
+    """The records / data entries of the stages of ETI frames: fn(*at, None, 0) says how many items there are, fn(*at, dst, n) brings them."""
+    n = fn(*at, None, 0)
+    _need(n >= 0, what)
+    out = np.zeros(n, dtype=dtype)
+    _need(fn(*at, _p(out), n) == n, what)
+    return out
+
+
 class HostBuffer:
     """nbytes of page-locked host memory (dabhip_host_alloc): .array is a numpy view, .ptr its address.  Uploads from it are
     plain asynchronous DMA at the PCIe rate; pageable memory goes through the engine's staging ring instead."""
@@ -905,48 +936,24 @@ class DabPlus(_Handle):
     def push(self, frames, counts=None):
         """frames: a list of per-stream arrays of ETI frames (n x 6144 bytes each), one array of all frames stream after stream with counts, or
         (device_ptr, counts) for frames in device memory (Engine.eti_device_ptr's layout).  Returns the superframes this push completed."""
-        if isinstance(frames, tuple):
-            ptr, counts = frames
-            src, on_dev = C.c_void_p(ptr), 1
-        else:
-            if isinstance(frames, list):
-                counts = [np.asarray(f).size // ETI_BYTES for f in frames]
-                arr = np.ascontiguousarray(np.concatenate([np.asarray(f, dtype=np.uint8).reshape(-1) for f in frames]) if frames else np.zeros(0, np.uint8))
-            else:
-                arr = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
-                if counts is None:
-                    _need(self.nstreams == 1, "dabplus_push: counts needed for several streams")
-                    counts = [arr.size // ETI_BYTES]
-            self._keep = arr
-            src, on_dev = C.c_void_p(arr.ctypes.data), 0
-        cnt = (C.c_int64 * self.nstreams)(*[int(c) for c in counts])
+        src, cnt, on_dev, keep = _eti_frames_arg("dabplus_push", self.nstreams, frames, counts)
+        if keep is not None:
+            self._keep = keep
         n = lib().dabhip_dabplus_push(self._h, src, cnt, on_dev)
         _need(n >= 0, "dabplus_push")
         return n
 
     def superframes(self, stream=0, sub=0):
         """Records of the last push's superframes of (stream, sub-channel index): a DABPLUS_SF array."""
-        n = lib().dabhip_dabplus_superframes(self._h, stream, sub, None, 0)
-        _need(n >= 0, "dabplus_superframes")
-        out = np.zeros(n, dtype=DABPLUS_SF)
-        _need(lib().dabhip_dabplus_superframes(self._h, stream, sub, out.ctypes.data, n) == n, "dabplus_superframes")
-        return out
+        return _fetch(lib().dabhip_dabplus_superframes, "dabplus_superframes", DABPLUS_SF, self._h, stream, sub)
 
     def data(self, stream=0, sub=0):
         """The corrected 110 s audio bytes of those superframes, one after another."""
-        n = lib().dabhip_dabplus_data(self._h, stream, sub, None, 0)
-        _need(n >= 0, "dabplus_data")
-        out = np.zeros(n, dtype=np.uint8)
-        _need(lib().dabhip_dabplus_data(self._h, stream, sub, _p(out), n) == n, "dabplus_data")
-        return out
+        return _fetch(lib().dabhip_dabplus_data, "dabplus_data", np.uint8, self._h, stream, sub)
 
     def au_bytes(self, stream=0, sub=0):
         """The AUs of the last push with a good CRC, CRC bytes stripped, one after another."""
-        n = lib().dabhip_dabplus_au_bytes(self._h, stream, sub, None, 0)
-        _need(n >= 0, "dabplus_au_bytes")
-        out = np.zeros(n, dtype=np.uint8)
-        _need(lib().dabhip_dabplus_au_bytes(self._h, stream, sub, _p(out), n) == n, "dabplus_au_bytes")
-        return out
+        return _fetch(lib().dabhip_dabplus_au_bytes, "dabplus_au_bytes", np.uint8, self._h, stream, sub)
 
     def aus(self, stream=0, sub=0):
         """The same AUs as a list of uint8 arrays, in order."""
@@ -1002,40 +1009,20 @@ class Packet(_Handle):
 
     def push(self, frames, counts=None):
         """frames as DabPlus.push takes them.  Returns the packets this push took."""
-        if isinstance(frames, tuple):
-            ptr, counts = frames
-            src, on_dev = C.c_void_p(ptr), 1
-        else:
-            if isinstance(frames, list):
-                counts = [np.asarray(f).size // ETI_BYTES for f in frames]
-                arr = np.ascontiguousarray(np.concatenate([np.asarray(f, dtype=np.uint8).reshape(-1) for f in frames]) if frames else np.zeros(0, np.uint8))
-            else:
-                arr = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
-                if counts is None:
-                    _need(self.nstreams == 1, "packet_push: counts needed for several streams")
-                    counts = [arr.size // ETI_BYTES]
-            self._keep = arr
-            src, on_dev = C.c_void_p(arr.ctypes.data), 0
-        cnt = (C.c_int64 * self.nstreams)(*[int(c) for c in counts])
+        src, cnt, on_dev, keep = _eti_frames_arg("packet_push", self.nstreams, frames, counts)
+        if keep is not None:
+            self._keep = keep
         n = lib().dabhip_packet_push(self._h, src, cnt, on_dev)
         _need(n >= 0, "packet_push")
         return n
 
     def records(self, stream=0, sub=0):
         """Records of the last push's packets of (stream, sub-channel index): a PACKET_REC array."""
-        n = lib().dabhip_packet_records(self._h, stream, sub, None, 0)
-        _need(n >= 0, "packet_records")
-        out = np.zeros(n, dtype=PACKET_REC)
-        _need(lib().dabhip_packet_records(self._h, stream, sub, out.ctypes.data, n) == n, "packet_records")
-        return out
+        return _fetch(lib().dabhip_packet_records, "packet_records", PACKET_REC, self._h, stream, sub)
 
     def data(self, stream=0, sub=0):
         """The useful bytes of those packets, one after another."""
-        n = lib().dabhip_packet_data(self._h, stream, sub, None, 0)
-        _need(n >= 0, "packet_data")
-        out = np.zeros(n, dtype=np.uint8)
-        _need(lib().dabhip_packet_data(self._h, stream, sub, _p(out), n) == n, "packet_data")
-        return out
+        return _fetch(lib().dabhip_packet_data, "packet_data", np.uint8, self._h, stream, sub)
 
     def stats(self, stream=0, sub=0):
         """Counters since creation, in PACKET_STATS order (int64 array of 8)."""
@@ -1069,40 +1056,20 @@ class Ts(_Handle):
 
     def push(self, frames, counts=None):
         """frames as Packet.push takes them.  Returns the packets of this push."""
-        if isinstance(frames, tuple):
-            ptr, counts = frames
-            src, on_dev = C.c_void_p(ptr), 1
-        else:
-            if isinstance(frames, list):
-                counts = [np.asarray(f).size // ETI_BYTES for f in frames]
-                arr = np.ascontiguousarray(np.concatenate([np.asarray(f, dtype=np.uint8).reshape(-1) for f in frames]) if frames else np.zeros(0, np.uint8))
-            else:
-                arr = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
-                if counts is None:
-                    _need(self.nstreams == 1, "ts_push: counts needed for several streams")
-                    counts = [arr.size // ETI_BYTES]
-            self._keep = arr
-            src, on_dev = C.c_void_p(arr.ctypes.data), 0
-        cnt = (C.c_int64 * self.nstreams)(*[int(c) for c in counts])
+        src, cnt, on_dev, keep = _eti_frames_arg("ts_push", self.nstreams, frames, counts)
+        if keep is not None:
+            self._keep = keep
         n = lib().dabhip_ts_push(self._h, src, cnt, on_dev)
         _need(n >= 0, "ts_push")
         return n
 
     def records(self, stream=0, sub=0):
         """Records of the last push's packets of (stream, sub-channel index): a TS_REC array."""
-        n = lib().dabhip_ts_records(self._h, stream, sub, None, 0)
-        _need(n >= 0, "ts_records")
-        out = np.zeros(n, dtype=TS_REC)
-        _need(lib().dabhip_ts_records(self._h, stream, sub, out.ctypes.data, n) == n, "ts_records")
-        return out
+        return _fetch(lib().dabhip_ts_records, "ts_records", TS_REC, self._h, stream, sub)
 
     def data(self, stream=0, sub=0):
         """Their bytes: an (n, 188) array, failed words as received."""
-        n = lib().dabhip_ts_data(self._h, stream, sub, None, 0)
-        _need(n >= 0, "ts_data")
-        out = np.zeros(n, dtype=np.uint8)
-        _need(lib().dabhip_ts_data(self._h, stream, sub, _p(out), n) == n, "ts_data")
-        return out.reshape(-1, 188)
+        return _fetch(lib().dabhip_ts_data, "ts_data", np.uint8, self._h, stream, sub).reshape(-1, 188)
 
     def stats(self, stream=0, sub=0):
         """Counters since creation, in TS_STATS order (int64 array of 8)."""
@@ -1156,21 +1123,9 @@ class Dir(_Handle):
 
     def push(self, frames, counts=None):
         """frames as Ts.push takes them.  Returns the FIBs of this push whose CRC held."""
-        if isinstance(frames, tuple):
-            ptr, counts = frames
-            src, on_dev = C.c_void_p(ptr), 1
-        else:
-            if isinstance(frames, list):
-                counts = [np.asarray(f).size // ETI_BYTES for f in frames]
-                arr = np.ascontiguousarray(np.concatenate([np.asarray(f, dtype=np.uint8).reshape(-1) for f in frames]) if frames else np.zeros(0, np.uint8))
-            else:
-                arr = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
-                if counts is None:
-                    _need(self.nstreams == 1, "dir_push: counts needed for several streams")
-                    counts = [arr.size // ETI_BYTES]
-            self._keep = arr
-            src, on_dev = C.c_void_p(arr.ctypes.data), 0
-        cnt = (C.c_int64 * self.nstreams)(*[int(c) for c in counts])
+        src, cnt, on_dev, keep = _eti_frames_arg("dir_push", self.nstreams, frames, counts)
+        if keep is not None:
+            self._keep = keep
         n = lib().dabhip_dir_push(self._h, src, cnt, on_dev)
         _need(n >= 0, "dir_push")
         return n
@@ -1273,40 +1228,20 @@ class Edi(_Handle):
 
     def push(self, frames, counts=None):
         """frames as Ts.push takes them.  Returns the packets of this push."""
-        if isinstance(frames, tuple):
-            ptr, counts = frames
-            src, on_dev = C.c_void_p(ptr), 1
-        else:
-            if isinstance(frames, list):
-                counts = [np.asarray(f).size // ETI_BYTES for f in frames]
-                arr = np.ascontiguousarray(np.concatenate([np.asarray(f, dtype=np.uint8).reshape(-1) for f in frames]) if frames else np.zeros(0, np.uint8))
-            else:
-                arr = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1)
-                if counts is None:
-                    _need(self.nstreams == 1, "edi_push: counts needed for several streams")
-                    counts = [arr.size // ETI_BYTES]
-            self._keep = arr
-            src, on_dev = C.c_void_p(arr.ctypes.data), 0
-        cnt = (C.c_int64 * self.nstreams)(*[int(c) for c in counts])
+        src, cnt, on_dev, keep = _eti_frames_arg("edi_push", self.nstreams, frames, counts)
+        if keep is not None:
+            self._keep = keep
         n = lib().dabhip_edi_push(self._h, src, cnt, on_dev)
         _need(n >= 0, "edi_push")
         return n
 
     def records(self, stream=0):
         """Records of the last push's packets of a stream: an EDI_REC array."""
-        n = lib().dabhip_edi_records(self._h, stream, None, 0)
-        _need(n >= 0, "edi_records")
-        out = np.zeros(n, dtype=EDI_REC)
-        _need(lib().dabhip_edi_records(self._h, stream, out.ctypes.data, n) == n, "edi_records")
-        return out
+        return _fetch(lib().dabhip_edi_records, "edi_records", EDI_REC, self._h, stream)
 
     def data(self, stream=0):
         """Their bytes, packet after packet: a uint8 array."""
-        n = lib().dabhip_edi_data(self._h, stream, None, 0)
-        _need(n >= 0, "edi_data")
-        out = np.zeros(n, dtype=np.uint8)
-        _need(lib().dabhip_edi_data(self._h, stream, _p(out), n) == n, "edi_data")
-        return out
+        return _fetch(lib().dabhip_edi_data, "edi_data", np.uint8, self._h, stream)
 
     def reset(self, stream=0):
         _need(lib().dabhip_edi_reset(self._h, stream) == 0, "edi_reset")
@@ -1352,8 +1287,7 @@ class EdiRx(_Handle):
             packets = [np.frombuffer(bytes(x), np.uint8) if isinstance(x, (bytes, bytearray)) else np.asarray(x, np.uint8).reshape(-1) for x in packets]
             lengths = [x.size for x in packets]
             if counts is None:
-                _need(self.nstreams == 1, "edirx_push: counts needed for several streams")
-                counts = [len(packets)]
+                counts = _one_stream_counts("edirx_push", self.nstreams, len(packets))
             _need(sum(int(c) for c in counts) == len(packets), "edirx_push: counts and packets disagree")
             arr = np.ascontiguousarray(np.concatenate(packets)) if packets else np.zeros(0, np.uint8)
             self._keep = arr

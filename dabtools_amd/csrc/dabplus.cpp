@@ -11,9 +11,8 @@
 #include "../../include/dabhip.h"
 #include "dab_bits.hpp"
 #include "dabplus.hpp"
+#include "eti_lanes.hpp"
 #include "kernels.hpp"
-#include "rs_code.hpp"
-#include "stage_frame.hpp"
 
 using namespace dabhip;
 
@@ -22,8 +21,7 @@ const char* const kStages[5] = {"locate", "sync", "rs", "au", "carry"};
 }
 
 struct dabhip_dabplus {
-  int nstreams = 0, nsub = 0;
-  DeviceBuffer<int32_t> subch;
+  EtiLanes lanes{"dabplus"};                        // its host copy: the lanes' first superframes (lane_sf_base)
   DeviceBuffer<DabPlusSync> sync;
   DeviceBuffer<int64_t> counters;
   DeviceBuffer<uint8_t> carry[2];
@@ -41,32 +39,23 @@ struct dabhip_dabplus {
   DeviceBuffer<dabhip_dabplus_sf> recs;
   int64_t nsf = 0, ncw = 0;
   // host copies of the last push's records, fetched on first use
-  mutable bool fetched = false;
   mutable std::vector<dabhip_dabplus_sf> h_recs;
-  mutable std::vector<int> h_lane_base;
   mutable std::vector<int64_t> h_data_base;   // per superframe, and the total at the end
   StageFrame<5> f{"dabplus", kStages};
 
-  bool fetch() const
+  // lane l's superframes of the last push, [a, a + n) of h_recs
+  bool lane_range(int stream, int sub, int64_t& a, int64_t& n) const
   {
-    if (fetched) return true;
-    if (!f.use_device()) return false;
-    const int nlanes = nstreams * nsub;
-    h_recs.resize(static_cast<size_t>(nsf));
-    h_lane_base.assign(static_cast<size_t>(nlanes) + 1, 0);
-    if (nsf > 0) {
-      if (!f.ok(blocking_copy(h_recs.data(), recs.get(), sizeof(dabhip_dabplus_sf) * static_cast<size_t>(nsf), hipMemcpyDeviceToHost), "records")) return false;
-      if (!f.ok(blocking_copy(h_lane_base.data(), lane_sf_base.get(), sizeof(int) * (static_cast<size_t>(nlanes) + 1), hipMemcpyDeviceToHost), "records")) return false;
+    if (!lanes.lane_ok(stream, sub)) return false;
+    if (!lanes.fetched) {
+      if (!f.use_device()) return false;
+      h_recs.resize(static_cast<size_t>(nsf));
+      if (nsf > 0 && !f.ok(blocking_copy(h_recs.data(), recs.get(), sizeof(dabhip_dabplus_sf) * static_cast<size_t>(nsf), hipMemcpyDeviceToHost), "records")) return false;
+      h_data_base.assign(static_cast<size_t>(nsf) + 1, 0);
+      for (int64_t i = 0; i < nsf; ++i) h_data_base[i + 1] = h_data_base[i] + static_cast<int64_t>(kRsK) * h_recs[i].s;
+      if (!lanes.fetch(f, lane_sf_base.get(), nsf > 0)) return false;
     }
-    h_data_base.assign(static_cast<size_t>(nsf) + 1, 0);
-    for (int64_t i = 0; i < nsf; ++i) h_data_base[i + 1] = h_data_base[i] + static_cast<int64_t>(kRsK) * h_recs[i].s;
-    fetched = true;
-    return true;
-  }
-
-  bool lane_ok(int s, int q) const
-  {
-    if (s < 0 || s >= nstreams || q < 0 || q >= nsub) { set_error("dabplus: no such stream / sub-channel"); return false; }
+    lanes.range(stream, sub, a, n);
     return true;
   }
 };
@@ -77,15 +66,9 @@ extern "C" dabhip_dabplus* dabhip_dabplus_create(int device, int nstreams, const
   StageFrame<5>& f = d->f;
   if (!f.open(device, "no HIP device: the DAB+ stage runs on the GPU only", "dabplus_create: device index out of range")) return nullptr;
   const auto ok = [&f](hipError_t e, const char* what) { return f.ok(e, what); };
-  if (nstreams <= 0 || nsub <= 0 || nsub > 64 || !subch_ids) { set_error("dabplus_create: bad arguments"); return nullptr; }
-  for (int q = 0; q < nsub; ++q)
-    if (subch_ids[q] < 0 || subch_ids[q] > 63) { set_error("dabplus_create: SubChId out of range"); return nullptr; }
-  d->nstreams = nstreams;
-  d->nsub = nsub;
+  if (!d->lanes.create(f, nstreams, subch_ids, nsub, true, 0)) return nullptr;
   d->ncarry.assign(static_cast<size_t>(nstreams), 0);
-  const size_t nlanes = static_cast<size_t>(nstreams) * nsub;
-  GfRs<kRsRoots> gf;
-  rs_tables_fill(gf);
+  const size_t nlanes = d->lanes.count();
   std::vector<uint16_t> crc(256 + kRsK * kMaxS);
   for (int v = 0; v < 256; ++v) {
     const uint8_t b = static_cast<uint8_t>(v);
@@ -97,13 +80,11 @@ extern "C" dabhip_dabplus* dabhip_dabplus_create(int device, int nstreams, const
     crc[256 + n] = static_cast<uint16_t>(r);
     for (int b = 0; b < 8; ++b) r = (r & 0x8000u) ? ((r << 1) ^ 0x1021u) & 0xffffu : (r << 1) & 0xffffu;
   }
-  bool good = d->subch.reserve(nsub) && d->sync.reserve(nlanes) && d->counters.reserve(nlanes * kCntN) && d->gf.reserve(sizeof gf) && d->crc_tab.reserve(crc.size()) &&
+  bool good = d->sync.reserve(nlanes) && d->counters.reserve(nlanes * kCntN) && d->crc_tab.reserve(crc.size()) &&
          d->carry[0].reserve(static_cast<size_t>(nstreams) * 4 * DABHIP_ETI_BYTES) && d->carry[1].reserve(static_cast<size_t>(nstreams) * 4 * DABHIP_ETI_BYTES) &&
          d->totals.reserve(2);
-  good = good && ok(hipMemcpy(d->subch.get(), subch_ids, sizeof(int32_t) * nsub, hipMemcpyHostToDevice), "upload") &&
-         ok(hipMemset(d->sync.get(), 0, sizeof(DabPlusSync) * nlanes), "clear") && ok(hipMemset(d->counters.get(), 0, sizeof(int64_t) * nlanes * kCntN), "clear") &&
-         ok(hipMemcpy(d->gf.get(), &gf, sizeof gf, hipMemcpyHostToDevice), "upload") &&
-         ok(hipMemcpy(d->crc_tab.get(), crc.data(), crc.size() * 2, hipMemcpyHostToDevice), "upload");
+  good = good && ok(hipMemset(d->sync.get(), 0, sizeof(DabPlusSync) * nlanes), "clear") && ok(hipMemset(d->counters.get(), 0, sizeof(int64_t) * nlanes * kCntN), "clear") &&
+         upload_rs_tables<kRsRoots>(f, d->gf) && ok(hipMemcpy(d->crc_tab.get(), crc.data(), crc.size() * 2, hipMemcpyHostToDevice), "upload");
   return good ? d.release() : nullptr;
 }
 
@@ -115,49 +96,21 @@ extern "C" int64_t dabhip_dabplus_push(dabhip_dabplus* d, const uint8_t* frames,
   StageFrame<5>& f = d->f;
   const auto ok = [&f](hipError_t e, const char* what) { return f.ok(e, what); };
   if (!f.use_device()) return -1;
-  const int ns = d->nstreams, nsub = d->nsub;
-  std::vector<int64_t> base(static_cast<size_t>(ns));
-  int64_t total = 0;
-  int maxv = 0;
-  for (int s = 0; s < ns; ++s) {
-    if (counts[s] < 0 || counts[s] > (1 << 24)) { set_error("dabplus_push: bad frame count"); return -1; }
-    base[s] = total;
-    total += counts[s];
-    maxv = std::max<int>(maxv, d->ncarry[s] + static_cast<int>(counts[s]));
-  }
-  if (total > 0 && !frames) { set_error("dabplus_push: null frames"); return -1; }
-  const uint8_t* src = frames;
-  if (total > 0 && !on_device) {
-    const size_t bytes = static_cast<size_t>(total) * DABHIP_ETI_BYTES;
-    if (!d->staging.reserve(bytes) || !ok(hipMemcpyAsync(d->staging.get(), frames, bytes, hipMemcpyHostToDevice, f.stream), "upload")) return -1;
-    src = d->staging.get();
-  }
-  // per-stream metadata in one upload: base | nnew | ncarry
-  std::vector<uint8_t> meta(static_cast<size_t>(ns) * 16);
-  std::memcpy(meta.data(), base.data(), sizeof(int64_t) * ns);
-  for (int s = 0; s < ns; ++s) {
-    const int n = static_cast<int>(counts[s]);
-    std::memcpy(meta.data() + 8 * ns + 4 * s, &n, 4);
-    std::memcpy(meta.data() + 12 * ns + 4 * s, &d->ncarry[s], 4);
-  }
-  const size_t nlanes = static_cast<size_t>(ns) * nsub;
-  const int cap = maxv / kSfFrames + 1;
-  if (!d->meta.reserve(meta.size()) || !d->loc.reserve(static_cast<size_t>(ns) * std::max(maxv, 1) * nsub) || !d->cand.reserve(nlanes * cap) ||
-      !d->jobs.reserve(nlanes * cap) || !d->ncand.reserve(nlanes) || !d->lane_cw.reserve(nlanes) || !d->lane_sf_base.reserve(nlanes + 1) || !d->lane_cw_base.reserve(nlanes))
+  const int ns = d->lanes.nstreams, nsub = d->lanes.nsub;
+  const EtiPush p = plan_eti_push("dabplus_push", counts, ns, !frames, 1 << 24, kEtiNoTotalBound, d->ncarry.data());
+  if (!p.refusal.empty()) { set_error(p.refusal); return -1; }
+  EtiFrames e;
+  const int* ncarry = nullptr;
+  if (!f.place(p, frames, on_device, d->staging, d->meta, e, &ncarry)) return -1;
+  const DabPlusFrames fr{e.frames, d->carry[d->cur].get(), e.base, e.nnew, ncarry, (reinterpret_cast<uintptr_t>(e.frames) & 15) == 0};
+  const size_t nlanes = d->lanes.count();
+  const int maxv = p.maxv, cap = maxv / kSfFrames + 1;
+  if (!d->loc.reserve(static_cast<size_t>(ns) * std::max(maxv, 1) * nsub) || !d->cand.reserve(nlanes * cap) || !d->jobs.reserve(nlanes * cap) || !d->ncand.reserve(nlanes) ||
+      !d->lane_cw.reserve(nlanes) || !d->lane_sf_base.reserve(nlanes + 1) || !d->lane_cw_base.reserve(nlanes))
     return -1;
-  // the host copy of meta must outlive the asynchronous copy: hipMemcpy from pageable memory returns once the bytes are staged
-  if (!ok(hipMemcpyAsync(d->meta.get(), meta.data(), meta.size(), hipMemcpyHostToDevice, f.stream), "upload") || !ok(hipStreamSynchronize(f.stream), "upload"))
-    return -1;
-  DabPlusFrames fr;
-  fr.frames = src;
-  fr.carry = d->carry[d->cur].get();
-  fr.base = reinterpret_cast<const int64_t*>(d->meta.get());
-  fr.nnew = reinterpret_cast<const int*>(d->meta.get() + 8 * ns);
-  fr.ncarry = reinterpret_cast<const int*>(d->meta.get() + 12 * ns);
-  fr.aligned = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
   hipStream_t st = f.stream;
   int totals[2] = {0, 0};
-  bool good = f.mark(0) && ok(launch_dabplus_locate(fr, d->subch.get(), nsub, ns, maxv, d->loc.get(), st), "locate") &&
+  bool good = f.mark(0) && ok(launch_dabplus_locate(fr, d->lanes.subch.get(), nsub, ns, maxv, d->loc.get(), st), "locate") &&
               f.mark(1) &&
               ok(launch_dabplus_sync(fr, ns, nsub, maxv, d->loc.get(), d->sync.get(), d->cand.get(), cap, d->ncand.get(), d->lane_cw.get(), d->counters.get(), d->jobs.get(),
                                      d->lane_sf_base.get(), d->lane_cw_base.get(), d->totals.get(), st), "sync") &&
@@ -166,7 +119,7 @@ extern "C" int64_t dabhip_dabplus_push(dabhip_dabplus* d, const uint8_t* frames,
   if (!good) return -1;
   d->nsf = totals[0];
   d->ncw = totals[1];
-  d->fetched = false;
+  d->lanes.fetched = false;
   good = d->data.reserve(static_cast<size_t>(d->ncw) * kRsK + 16) && d->cw_status.reserve(static_cast<size_t>(d->ncw ? d->ncw : 1)) && d->recs.reserve(static_cast<size_t>(d->nsf ? d->nsf : 1)) &&
          d->syn.reserve(static_cast<size_t>(d->ncw ? d->ncw * 4 : 1)) &&
          ok(launch_dabplus_rs(d->jobs.get(), d->totals.get(), static_cast<int>(d->ncw), d->loc.get(), maxv, nsub, d->gf.get(), d->data.get(), d->cw_status.get(), d->syn.get(), st),
@@ -184,9 +137,8 @@ extern "C" int64_t dabhip_dabplus_push(dabhip_dabplus* d, const uint8_t* frames,
 
 extern "C" int64_t dabhip_dabplus_superframes(const dabhip_dabplus* d, int stream, int sub, dabhip_dabplus_sf* out, int64_t cap)
 {
-  if (!d || !d->lane_ok(stream, sub) || !d->fetch()) return -1;
-  const int l = stream * d->nsub + sub;
-  const int64_t a = d->h_lane_base[l], n = d->h_lane_base[l + 1] - a;
+  int64_t a = 0, n = 0;
+  if (!d || !d->lane_range(stream, sub, a, n)) return -1;
   if (out && cap > 0) std::memcpy(out, d->h_recs.data() + a, sizeof(dabhip_dabplus_sf) * static_cast<size_t>(std::min(n, cap)));
   return n;
 }
@@ -195,10 +147,7 @@ namespace {
 // the corrected bytes of one (stream, sub-channel) of the last push, on the host
 bool lane_data(const dabhip_dabplus* d, int stream, int sub, std::vector<uint8_t>& out, int64_t* first_sf, int64_t* nsf)
 {
-  if (!d || !d->lane_ok(stream, sub) || !d->fetch()) return false;
-  const int l = stream * d->nsub + sub;
-  *first_sf = d->h_lane_base[l];
-  *nsf = d->h_lane_base[l + 1] - *first_sf;
+  if (!d || !d->lane_range(stream, sub, *first_sf, *nsf)) return false;
   const int64_t a = d->h_data_base[*first_sf], b = d->h_data_base[*first_sf + *nsf];
   out.resize(static_cast<size_t>(b - a));
   return b == a || d->f.ok(blocking_copy(out.data(), d->data.get() + a, static_cast<size_t>(b - a), hipMemcpyDeviceToHost), "data");
@@ -237,12 +186,7 @@ extern "C" int64_t dabhip_dabplus_au_bytes(const dabhip_dabplus* d, int stream, 
 extern "C" int dabhip_dabplus_stats(const dabhip_dabplus* d, int stream, int sub, int64_t* counters7)
 {
   if (!d || !counters7) { set_error("dabplus_stats: null argument"); return -1; }
-  if (!d->lane_ok(stream, sub)) return -1;
-  if (!d->f.use_device()) return -1;
-  int64_t c[kCntN];
-  if (!d->f.ok(blocking_copy(c, d->counters.get() + (static_cast<size_t>(stream) * d->nsub + sub) * kCntN, sizeof c, hipMemcpyDeviceToHost), "counters")) return -1;
-  std::memcpy(counters7, c, 7 * sizeof(int64_t));
-  return 0;
+  return d->lanes.lane_counters(d->f, stream, sub, d->counters.get(), kCntN, counters7, 7);
 }
 
 extern "C" int dabhip_dabplus_stage_ms(const dabhip_dabplus* d, const char** names, float* ms, int cap)

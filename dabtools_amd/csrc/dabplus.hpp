@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "../../include/dabhip.h"
+#include "eti_push.hpp"
 
 namespace dabhip {
 
@@ -85,7 +86,8 @@ struct DabPlusCand {
 };
 
 // the frames of one push: stream s's virtual frames are its ncarry[s] carried frames (carry + (4 s + v) 6144), then its nnew[s] new ones
-// (frames + (base[s] + v - ncarry[s]) 6144)
+// (frames + (base[s] + v - ncarry[s]) 6144).  An EtiFrames (eti_push.hpp) with the carry beside it; the fields keep the order the kernels'
+// arguments were compiled with
 struct DabPlusFrames {
   const uint8_t* frames;
   const uint8_t* carry;

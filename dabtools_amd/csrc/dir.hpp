@@ -8,6 +8,7 @@
 
 #include "../../include/dabhip.h"
 #include "dir_figs.hpp"
+#include "eti_push.hpp"
 
 namespace dabhip {
 
@@ -51,12 +52,5 @@ struct DirStream {
 };
 constexpr size_t kDirTablesBytes = sizeof(DirEntry) * kDirEntries + 8;
 static_assert(sizeof(DirStream) == kDirTablesBytes + 8 * kDirCntN && sizeof(DirStream) % 8 == 0, "DirStream layout");
-
-// the frames of a push: stream s has nnew[s] frames from frame base[s] of `frames` on
-struct DirFrames {
-  const uint8_t* frames;
-  const int64_t* base;
-  const int* nnew;
-};
 
 }  // namespace dabhip

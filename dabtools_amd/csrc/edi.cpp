@@ -84,40 +84,14 @@ extern "C" int64_t dabhip_edi_push(dabhip_edi* d, const uint8_t* frames, const i
   const auto ok = [&f](hipError_t e, const char* what) { return f.ok(e, what); };
   if (!f.use_device()) return -1;
   const int ns = d->nstreams;
-  std::vector<int64_t> base(static_cast<size_t>(ns));
-  int64_t total = 0;
-  int maxv = 0;
-  for (int s = 0; s < ns; ++s) {
-    if (counts[s] < 0 || counts[s] > kMaxPushFrames) { set_error("edi_push: bad frame count"); return -1; }
-    base[s] = total;
-    total += counts[s];
-    maxv = std::max<int>(maxv, static_cast<int>(counts[s]));
-  }
-  if (total > kMaxPushFrames) { set_error("edi_push: too many frames for one push"); return -1; }
-  if (total > 0 && !frames) { set_error("edi_push: null frames"); return -1; }
-  const uint8_t* src = frames;
-  if (total > 0 && !on_device) {
-    const size_t bytes = static_cast<size_t>(total) * DABHIP_ETI_BYTES;
-    if (!d->staging.reserve(bytes) || !ok(hipMemcpyAsync(d->staging.get(), frames, bytes, hipMemcpyHostToDevice, f.stream), "upload")) return -1;
-    src = d->staging.get();
-  }
-  std::vector<uint8_t> meta(static_cast<size_t>(ns) * 12);
-  std::memcpy(meta.data(), base.data(), sizeof(int64_t) * ns);
-  for (int s = 0; s < ns; ++s) {
-    const int n = static_cast<int>(counts[s]);
-    std::memcpy(meta.data() + 8 * ns + 4 * s, &n, 4);
-  }
+  const EtiPush p = plan_eti_push("edi_push", counts, ns, !frames, kMaxPushFrames, kMaxPushFrames);
+  if (!p.refusal.empty()) { set_error(p.refusal); return -1; }
+  EtiFrames fr;
+  if (!f.place(p, frames, on_device, d->staging, d->meta, fr)) return -1;
+  const int64_t total = p.total;
+  const int maxv = p.maxv;
   const size_t nf = static_cast<size_t>(std::max<int64_t>(total, 1));
-  if (!d->meta.reserve(meta.size()) || !d->frames.reserve(nf) || !d->work.reserve(nf * kEdiWorkStride) ||
-      (d->cfg.mode == 2 && !d->parity.reserve(nf * kEdiMaxChunks * kEdiRsP)))
-    return -1;
-  // the host copy of meta must outlive the asynchronous copy
-  if (!ok(hipMemcpyAsync(d->meta.get(), meta.data(), meta.size(), hipMemcpyHostToDevice, f.stream), "upload") || !ok(hipStreamSynchronize(f.stream), "upload"))
-    return -1;
-  EdiFrames fr;
-  fr.frames = src;
-  fr.base = reinterpret_cast<const int64_t*>(d->meta.get());
-  fr.nnew = reinterpret_cast<const int*>(d->meta.get() + 8 * ns);
+  if (!d->frames.reserve(nf) || !d->work.reserve(nf * kEdiWorkStride) || (d->cfg.mode == 2 && !d->parity.reserve(nf * kEdiMaxChunks * kEdiRsP))) return -1;
   hipStream_t st = f.stream;
   std::vector<int64_t>& hb = d->h_bases;
   bool good = f.mark(0) && ok(launch_edi_plan(fr, d->cfg, ns, maxv, d->frames.get(), st), "plan") && f.mark(1) &&

@@ -8,15 +8,9 @@
 
 #include "../../include/dabhip.h"
 #include "edi_plan.hpp"
+#include "eti_push.hpp"
 
 namespace dabhip {
-
-// the frames of a push: stream after stream, base[s] the first frame of stream s, nnew[s] its count
-struct EdiFrames {
-  const uint8_t* frames;
-  const int64_t* base;
-  const int* nnew;
-};
 
 // how the handle was created
 struct EdiConfig {
@@ -55,12 +49,12 @@ constexpr int kEdiRsFrames = kEdiRsWaves;
 // plan: a thread per (stream, new frame) -> EdiFrame.valid, l, p, stream.  scan: a wave per stream -> fcth, seq, pkt_local, byte_local, number,
 // the stream's state and counters, its packets and bytes of this push (sums[2 s], sums[2 s + 1]); then one workgroup: exclusive prefix sums of
 // those over the streams -> bases[2 s], bases[2 s + 1], the totals at s = nstreams.
-hipError_t launch_edi_plan(const EdiFrames& fr, EdiConfig cfg, int nstreams, int maxv, EdiFrame* out, hipStream_t stream);
-hipError_t launch_edi_scan(const EdiFrames& fr, EdiConfig cfg, int nstreams, EdiFrame* frames, EdiState* state, int64_t* counters, int64_t* sums, int64_t* bases,
+hipError_t launch_edi_plan(const EtiFrames& fr, EdiConfig cfg, int nstreams, int maxv, EdiFrame* out, hipStream_t stream);
+hipError_t launch_edi_scan(const EtiFrames& fr, EdiConfig cfg, int nstreams, EdiFrame* frames, EdiState* state, int64_t* counters, int64_t* sums, int64_t* bases,
                            hipStream_t stream);
 // assemble: a workgroup per frame -> its AF packet at work + g kEdiWorkStride, zeros behind it.  rs: a lane per chunk -> parity + (32 g + chunk) 48.
 // fragment: a workgroup per frame -> its packets at out + bases[2 s + 1] + byte_local and their records at recs + bases[2 s] + pkt_local.
-hipError_t launch_edi_assemble(const EdiFrames& fr, int64_t nframes, const EdiFrame* frames, uint8_t* work, hipStream_t stream);
+hipError_t launch_edi_assemble(const EtiFrames& fr, int64_t nframes, const EdiFrame* frames, uint8_t* work, hipStream_t stream);
 hipError_t launch_edi_rs(int64_t nframes, const EdiFrame* frames, const uint8_t* table, const uint8_t* work, uint8_t* parity, hipStream_t stream);
 hipError_t launch_edi_fragment(EdiConfig cfg, int64_t nframes, const EdiFrame* frames, const int64_t* bases, const uint8_t* work, const uint8_t* parity, uint8_t* out,
                                dabhip_edi_rec* recs, hipStream_t stream);

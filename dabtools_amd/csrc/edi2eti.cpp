@@ -16,19 +16,9 @@
 
 #include "../../include/dabhip.h"
 #include "edirx_plan.hpp"
+#include "eti_stdin.hpp"
 
 namespace {
-bool write_all(const uint8_t* p, size_t n)
-{
-  size_t done = 0;
-  while (done < n) {
-    const ssize_t w = write(1, p + done, n - done);
-    if (w <= 0) return false;
-    done += static_cast<size_t>(w);
-  }
-  return true;
-}
-
 bool number(const char* s, long lo, long hi, int* out)
 {
   char* end = nullptr;

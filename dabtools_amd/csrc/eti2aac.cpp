@@ -3,8 +3,6 @@
 // Superframe sync, RS(120,110) correction and the AU CRCs run on the GPU (dabhip_dabplus_*).  Whatever whole frames are on hand after each
 // read are pushed at once, so a live pipe keeps its latency.  Only AUs whose CRC is good are written, each behind a 7-byte ADTS header (AAC LC,
 // the sampling index of the AAC core rate, 1 or 2 channels); --raw writes the bare AUs instead.
-#include <unistd.h>
-
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -12,19 +10,9 @@
 #include <vector>
 
 #include "../../include/dabhip.h"
+#include "eti_stdin.hpp"
 
 namespace {
-bool write_all(const uint8_t* p, size_t n)
-{
-  size_t done = 0;
-  while (done < n) {
-    const ssize_t w = write(1, p + done, n - done);
-    if (w <= 0) return false;
-    done += static_cast<size_t>(w);
-  }
-  return true;
-}
-
 // ADTS fixed + variable header, MPEG-4, no CRC: AAC LC, core sampling rate (dac_rate 48 / 32 kHz, halved with SBR), 1 or 2 channels
 void adts_header(uint8_t* h, int au_len, const dabhip_dabplus_sf& r)
 {
@@ -55,48 +43,35 @@ int main(int argc, char** argv)
   const int32_t id = want;
   dabhip_dabplus* d = dabhip_dabplus_create(0, 1, &id, 1);
   if (!d) { std::fprintf(stderr, "eti2aac: %s\n", dabhip_last_error()); return 2; }
-  constexpr size_t kMaxFrames = 64;
-  std::vector<uint8_t> buf(kMaxFrames * DABHIP_ETI_BYTES), aus;
+  std::vector<uint8_t> aus;
   std::vector<dabhip_dabplus_sf> recs;
-  size_t have = 0;
   long frames = 0;
-  int rc = 0;
-  for (;;) {
-    const ssize_t r = read(0, buf.data() + have, buf.size() - have);
-    if (r < 0) { rc = 3; break; }
-    have += static_cast<size_t>(r);
-    const int64_t n = static_cast<int64_t>(have / DABHIP_ETI_BYTES);
-    if (n > 0) {
-      if (dabhip_dabplus_push(d, buf.data(), &n, 0) < 0) { std::fprintf(stderr, "eti2aac: %s\n", dabhip_last_error()); rc = 2; break; }
-      frames += n;
-      std::memmove(buf.data(), buf.data() + n * DABHIP_ETI_BYTES, have - static_cast<size_t>(n) * DABHIP_ETI_BYTES);
-      have -= static_cast<size_t>(n) * DABHIP_ETI_BYTES;
-      const int64_t nsf = dabhip_dabplus_superframes(d, 0, 0, nullptr, 0);
-      recs.resize(static_cast<size_t>(nsf));
-      const int64_t nb = dabhip_dabplus_au_bytes(d, 0, 0, nullptr, 0);
-      aus.resize(static_cast<size_t>(nb));
-      if (nsf < 0 || nb < 0 || dabhip_dabplus_superframes(d, 0, 0, recs.data(), nsf) != nsf || dabhip_dabplus_au_bytes(d, 0, 0, aus.data(), nb) != nb) {
-        std::fprintf(stderr, "eti2aac: %s\n", dabhip_last_error());
-        rc = 2;
-        break;
-      }
-      size_t off = 0;
-      bool good = true;
-      for (const dabhip_dabplus_sf& s : recs) {
-        if (!s.layout_ok) continue;
-        for (int k = 0; k < s.num_aus && good; ++k) {
-          if (!(s.crc_ok >> k & 1)) continue;
-          const int len = s.au_len[k] - 2;
-          uint8_t h[7];
-          adts_header(h, len, s);
-          good = (raw || write_all(h, 7)) && write_all(aus.data() + off, static_cast<size_t>(len));
-          off += static_cast<size_t>(len);
-        }
-      }
-      if (!good) { rc = 3; break; }
+  const int rc = for_eti_frames(0, 3, [&](const uint8_t* f, int64_t n) {
+    if (dabhip_dabplus_push(d, f, &n, 0) < 0) { std::fprintf(stderr, "eti2aac: %s\n", dabhip_last_error()); return 2; }
+    frames += n;
+    const int64_t nsf = dabhip_dabplus_superframes(d, 0, 0, nullptr, 0);
+    recs.resize(static_cast<size_t>(nsf));
+    const int64_t nb = dabhip_dabplus_au_bytes(d, 0, 0, nullptr, 0);
+    aus.resize(static_cast<size_t>(nb));
+    if (nsf < 0 || nb < 0 || dabhip_dabplus_superframes(d, 0, 0, recs.data(), nsf) != nsf || dabhip_dabplus_au_bytes(d, 0, 0, aus.data(), nb) != nb) {
+      std::fprintf(stderr, "eti2aac: %s\n", dabhip_last_error());
+      return 2;
     }
-    if (r == 0) break;
-  }
+    size_t off = 0;
+    bool good = true;
+    for (const dabhip_dabplus_sf& s : recs) {
+      if (!s.layout_ok) continue;
+      for (int k = 0; k < s.num_aus && good; ++k) {
+        if (!(s.crc_ok >> k & 1)) continue;
+        const int len = s.au_len[k] - 2;
+        uint8_t h[7];
+        adts_header(h, len, s);
+        good = (raw || write_all(h, 7)) && write_all(aus.data() + off, static_cast<size_t>(len));
+        off += static_cast<size_t>(len);
+      }
+    }
+    return good ? 0 : 3;
+  });
   int64_t c[7] = {0};
   dabhip_dabplus_stats(d, 0, 0, c);
   std::fprintf(stderr, "eti2aac: %ld frames, sub-channel %d: %lld superframes, %lld fire-code fails, %lld RS corrected bytes, %lld RS failed codewords, "

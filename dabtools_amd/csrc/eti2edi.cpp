@@ -5,7 +5,6 @@
 // and the interleaver run on the GPU (dabhip_edi_*).  Whatever whole frames are on hand after each read are pushed at once, 64 at most, so a
 // live pipe keeps its latency.  Stdout is the packets concatenated; the six counters go to stderr as one line at the end.
 #include <fcntl.h>
-#include <unistd.h>
 
 #include <cstdint>
 #include <cstdio>
@@ -14,19 +13,9 @@
 #include <vector>
 
 #include "../../include/dabhip.h"
+#include "eti_stdin.hpp"
 
 namespace {
-bool write_all(const uint8_t* p, size_t n)
-{
-  size_t done = 0;
-  while (done < n) {
-    const ssize_t w = write(1, p + done, n - done);
-    if (w <= 0) return false;
-    done += static_cast<size_t>(w);
-  }
-  return true;
-}
-
 bool number(const char* s, long lo, long hi, int* out)
 {
   char* end = nullptr;
@@ -61,30 +50,18 @@ int main(int argc, char** argv)
   if (path && (in = open(path, O_RDONLY)) < 0) { std::fprintf(stderr, "eti2edi: cannot open %s\n", path); return 3; }
   dabhip_edi* d = dabhip_edi_create(0, 1, mode, recover, max_frag, seq0);
   if (!d) { std::fprintf(stderr, "eti2edi: %s\n", dabhip_last_error()); return 2; }
-  constexpr size_t kMaxFrames = 64;
-  std::vector<uint8_t> buf(kMaxFrames * DABHIP_ETI_BYTES), out;
-  size_t have = 0;
+  std::vector<uint8_t> out;
   long frames = 0;
-  int rc = 0;
-  for (;;) {
-    const ssize_t r = read(in, buf.data() + have, buf.size() - have);
-    if (r < 0) { rc = 3; break; }
-    have += static_cast<size_t>(r);
-    const int64_t n = static_cast<int64_t>(have / DABHIP_ETI_BYTES);
-    if (n > 0) {
-      const int64_t np = dabhip_edi_push(d, buf.data(), &n, 0);
-      if (np < 0) { std::fprintf(stderr, "eti2edi: %s\n", dabhip_last_error()); rc = 2; break; }
-      frames += n;
-      std::memmove(buf.data(), buf.data() + n * DABHIP_ETI_BYTES, have - static_cast<size_t>(n) * DABHIP_ETI_BYTES);
-      have -= static_cast<size_t>(n) * DABHIP_ETI_BYTES;
-      const int64_t nb = dabhip_edi_data(d, 0, nullptr, 0);
-      if (nb < 0) { std::fprintf(stderr, "eti2edi: %s\n", dabhip_last_error()); rc = 2; break; }
-      out.resize(static_cast<size_t>(nb));
-      if (nb > 0 && dabhip_edi_data(d, 0, out.data(), nb) != nb) { std::fprintf(stderr, "eti2edi: %s\n", dabhip_last_error()); rc = 2; break; }
-      if (nb > 0 && !write_all(out.data(), out.size())) { rc = 3; break; }
-    }
-    if (r == 0) break;
-  }
+  const auto failed = [] { std::fprintf(stderr, "eti2edi: %s\n", dabhip_last_error()); return 2; };
+  const int rc = for_eti_frames(in, 3, [&](const uint8_t* f, int64_t n) {
+    if (dabhip_edi_push(d, f, &n, 0) < 0) return failed();
+    frames += n;
+    const int64_t nb = dabhip_edi_data(d, 0, nullptr, 0);
+    if (nb < 0) return failed();
+    out.resize(static_cast<size_t>(nb));
+    if (nb > 0 && dabhip_edi_data(d, 0, out.data(), nb) != nb) return failed();
+    return nb > 0 && !write_all(out.data(), out.size()) ? 3 : 0;
+  });
   int64_t c[6] = {0};
   dabhip_edi_stats(d, 0, c);
   std::fprintf(stderr, "eti2edi: %ld frames (%lld skipped, %lld without FIC), %lld packets, %lld bytes, %lld RS chunks encoded\n", frames,

@@ -5,8 +5,6 @@
 // 0x20..0x7E are printed as they are and every other byte as \xHH, the charset number beside; a full EBU Latin table is out of scope.  --json
 // prints the same as one JSON object, labels as hex.  The eleven counters go to stderr as one line.  Exit status 0, or 3 when the input ended
 // before the directory was complete.
-#include <unistd.h>
-
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -15,6 +13,7 @@
 #include <vector>
 
 #include "../../include/dabhip.h"
+#include "eti_stdin.hpp"
 
 namespace {
 const char* const kKinds[] = {"unknown", "mp2", "dabplus", "ts", "stream-data", "packet"};
@@ -72,23 +71,11 @@ int main(int argc, char** argv)
   }
   dabhip_dir* d = dabhip_dir_create(0, 1);
   if (!d) { std::fprintf(stderr, "eti2info: %s\n", dabhip_last_error()); return 2; }
-  constexpr size_t kMaxFrames = 64;
-  std::vector<uint8_t> buf(kMaxFrames * DABHIP_ETI_BYTES);
-  size_t have = 0;
-  int rc = 0, complete = 0;
-  for (;;) {
-    const ssize_t r = read(0, buf.data() + have, buf.size() - have);
-    if (r < 0) { rc = 4; break; }
-    have += static_cast<size_t>(r);
-    const int64_t n = static_cast<int64_t>(have / DABHIP_ETI_BYTES);
-    if (n > 0) {
-      if (dabhip_dir_push(d, buf.data(), &n, 0) < 0) { std::fprintf(stderr, "eti2info: %s\n", dabhip_last_error()); rc = 2; break; }
-      std::memmove(buf.data(), buf.data() + n * DABHIP_ETI_BYTES, have - static_cast<size_t>(n) * DABHIP_ETI_BYTES);
-      have -= static_cast<size_t>(n) * DABHIP_ETI_BYTES;
-      if (first_complete && (complete = dabhip_dir_complete(d, 0)) != 0) break;
-    }
-    if (r == 0) break;
-  }
+  int complete = 0;
+  int rc = for_eti_frames(0, 4, [&](const uint8_t* f, int64_t n) {
+    if (dabhip_dir_push(d, f, &n, 0) < 0) { std::fprintf(stderr, "eti2info: %s\n", dabhip_last_error()); return 2; }
+    return first_complete && dabhip_dir_complete(d, 0) != 0 ? -1 : 0;      // seen enough
+  });
   if (rc == 0) {
     complete = dabhip_dir_complete(d, 0);
     if (complete < 0) { std::fprintf(stderr, "eti2info: %s\n", dabhip_last_error()); rc = 2; }

@@ -5,8 +5,6 @@
 // (dabhip_packet_*); the data groups are put together on the host (dabhip_packet_groups_*).  Whatever whole frames are on hand after each read
 // are pushed at once, so a live pipe keeps its latency.  Every complete data group whose CRC is good or absent is written as its address (2
 // bytes, most significant first), its length (2 bytes) and its bytes; --address keeps one address only.
-#include <unistd.h>
-
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -14,19 +12,7 @@
 #include <vector>
 
 #include "../../include/dabhip.h"
-
-namespace {
-bool write_all(const uint8_t* p, size_t n)
-{
-  size_t done = 0;
-  while (done < n) {
-    const ssize_t w = write(1, p + done, n - done);
-    if (w <= 0) return false;
-    done += static_cast<size_t>(w);
-  }
-  return true;
-}
-}  // namespace
+#include "eti_stdin.hpp"
 
 int main(int argc, char** argv)
 {
@@ -45,52 +31,37 @@ int main(int argc, char** argv)
   dabhip_packet* d = dabhip_packet_create(0, 1, &id, &fec, 1);
   if (!d) { std::fprintf(stderr, "eti2pkt: %s\n", dabhip_last_error()); return 2; }
   dabhip_packet_groups* g = dabhip_packet_groups_create();
-  constexpr size_t kMaxFrames = 64;
-  std::vector<uint8_t> buf(kMaxFrames * DABHIP_ETI_BYTES), data, group;
+  std::vector<uint8_t> data, group;
   std::vector<dabhip_packet_rec> recs;
-  size_t have = 0;
   long frames = 0, written = 0;
-  int rc = 0;
-  for (;;) {
-    const ssize_t r = read(0, buf.data() + have, buf.size() - have);
-    if (r < 0) { rc = 3; break; }
-    have += static_cast<size_t>(r);
-    const int64_t n = static_cast<int64_t>(have / DABHIP_ETI_BYTES);
-    if (n > 0) {
-      if (dabhip_packet_push(d, buf.data(), &n, 0) < 0) { std::fprintf(stderr, "eti2pkt: %s\n", dabhip_last_error()); rc = 2; break; }
-      frames += n;
-      std::memmove(buf.data(), buf.data() + n * DABHIP_ETI_BYTES, have - static_cast<size_t>(n) * DABHIP_ETI_BYTES);
-      have -= static_cast<size_t>(n) * DABHIP_ETI_BYTES;
-      const int64_t np = dabhip_packet_records(d, 0, 0, nullptr, 0);
-      const int64_t nb = dabhip_packet_data(d, 0, 0, nullptr, 0);
-      if (np < 0 || nb < 0) { std::fprintf(stderr, "eti2pkt: %s\n", dabhip_last_error()); rc = 2; break; }
-      recs.resize(static_cast<size_t>(np));
-      data.resize(static_cast<size_t>(nb));
-      if (dabhip_packet_records(d, 0, 0, recs.data(), np) != np || dabhip_packet_data(d, 0, 0, data.data(), nb) != nb) {
-        std::fprintf(stderr, "eti2pkt: %s\n", dabhip_last_error());
-        rc = 2;
-        break;
-      }
-      const int64_t ng = dabhip_packet_groups_push(g, recs.data(), np, data.data(), nb);
-      if (ng < 0) { std::fprintf(stderr, "eti2pkt: %s\n", dabhip_last_error()); rc = 2; break; }
-      bool good = true;
-      for (int64_t i = 0; i < ng && good; ++i) {
-        dabhip_packet_group rec;
-        const int64_t len = dabhip_packet_groups_get(g, i, &rec, nullptr, 0);
-        if (len < 0 || (rec.crc_flag && !rec.crc_ok) || (address >= 0 && rec.address != address)) continue;
-        group.resize(static_cast<size_t>(len) + 4);
-        group[0] = static_cast<uint8_t>(rec.address >> 8);
-        group[1] = static_cast<uint8_t>(rec.address & 0xff);
-        group[2] = static_cast<uint8_t>(len >> 8);
-        group[3] = static_cast<uint8_t>(len & 0xff);
-        dabhip_packet_groups_get(g, i, nullptr, group.data() + 4, len);
-        good = write_all(group.data(), group.size());
-        ++written;
-      }
-      if (!good) { rc = 3; break; }
+  const auto failed = [] { std::fprintf(stderr, "eti2pkt: %s\n", dabhip_last_error()); return 2; };
+  const int rc = for_eti_frames(0, 3, [&](const uint8_t* f, int64_t n) {
+    if (dabhip_packet_push(d, f, &n, 0) < 0) return failed();
+    frames += n;
+    const int64_t np = dabhip_packet_records(d, 0, 0, nullptr, 0);
+    const int64_t nb = dabhip_packet_data(d, 0, 0, nullptr, 0);
+    if (np < 0 || nb < 0) return failed();
+    recs.resize(static_cast<size_t>(np));
+    data.resize(static_cast<size_t>(nb));
+    if (dabhip_packet_records(d, 0, 0, recs.data(), np) != np || dabhip_packet_data(d, 0, 0, data.data(), nb) != nb) return failed();
+    const int64_t ng = dabhip_packet_groups_push(g, recs.data(), np, data.data(), nb);
+    if (ng < 0) return failed();
+    bool good = true;
+    for (int64_t i = 0; i < ng && good; ++i) {
+      dabhip_packet_group rec;
+      const int64_t len = dabhip_packet_groups_get(g, i, &rec, nullptr, 0);
+      if (len < 0 || (rec.crc_flag && !rec.crc_ok) || (address >= 0 && rec.address != address)) continue;
+      group.resize(static_cast<size_t>(len) + 4);
+      group[0] = static_cast<uint8_t>(rec.address >> 8);
+      group[1] = static_cast<uint8_t>(rec.address & 0xff);
+      group[2] = static_cast<uint8_t>(len >> 8);
+      group[3] = static_cast<uint8_t>(len & 0xff);
+      dabhip_packet_groups_get(g, i, nullptr, group.data() + 4, len);
+      good = write_all(group.data(), group.size());
+      ++written;
     }
-    if (r == 0) break;
-  }
+    return good ? 0 : 3;
+  });
   int64_t c[8] = {0}, gc[4] = {0};
   dabhip_packet_stats(d, 0, 0, c);
   dabhip_packet_groups_stats(g, gc);

@@ -5,8 +5,6 @@
 // are pushed at once, so a live pipe keeps its latency.  Every packet is written as its 188 bytes; one whose code word was beyond correction is
 // written as received with the transport_error_indicator set (byte 1 |= 0x80), or left out with --drop-failed.  The eight counters go to stderr
 // as one line at the end.
-#include <unistd.h>
-
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -14,19 +12,7 @@
 #include <vector>
 
 #include "../../include/dabhip.h"
-
-namespace {
-bool write_all(const uint8_t* p, size_t n)
-{
-  size_t done = 0;
-  while (done < n) {
-    const ssize_t w = write(1, p + done, n - done);
-    if (w <= 0) return false;
-    done += static_cast<size_t>(w);
-  }
-  return true;
-}
-}  // namespace
+#include "eti_stdin.hpp"
 
 int main(int argc, char** argv)
 {
@@ -44,43 +30,30 @@ int main(int argc, char** argv)
   const int32_t id = want;
   dabhip_ts* d = dabhip_ts_create(0, 1, &id, 1);
   if (!d) { std::fprintf(stderr, "eti2ts: %s\n", dabhip_last_error()); return 2; }
-  constexpr size_t kMaxFrames = 64;
   constexpr int kPacket = 188;
-  std::vector<uint8_t> buf(kMaxFrames * DABHIP_ETI_BYTES), data, out;
+  std::vector<uint8_t> data, out;
   std::vector<dabhip_ts_rec> recs;
-  size_t have = 0;
   long frames = 0, written = 0;
-  int rc = 0;
-  for (;;) {
-    const ssize_t r = read(0, buf.data() + have, buf.size() - have);
-    if (r < 0) { rc = 3; break; }
-    have += static_cast<size_t>(r);
-    const int64_t n = static_cast<int64_t>(have / DABHIP_ETI_BYTES);
-    if (n > 0) {
-      const int64_t np = dabhip_ts_push(d, buf.data(), &n, 0);
-      if (np < 0) { std::fprintf(stderr, "eti2ts: %s\n", dabhip_last_error()); rc = 2; break; }
-      frames += n;
-      std::memmove(buf.data(), buf.data() + n * DABHIP_ETI_BYTES, have - static_cast<size_t>(n) * DABHIP_ETI_BYTES);
-      have -= static_cast<size_t>(n) * DABHIP_ETI_BYTES;
-      recs.resize(static_cast<size_t>(np));
-      data.resize(static_cast<size_t>(np) * kPacket);
-      if (np > 0 && (dabhip_ts_records(d, 0, 0, recs.data(), np) != np || dabhip_ts_data(d, 0, 0, data.data(), np * kPacket) != np * kPacket)) {
-        std::fprintf(stderr, "eti2ts: %s\n", dabhip_last_error());
-        rc = 2;
-        break;
-      }
-      out.clear();
-      for (int64_t i = 0; i < np; ++i) {
-        const bool failed = recs[static_cast<size_t>(i)].flags & DABHIP_TS_RS_FAILED;
-        if (failed && drop_failed) continue;
-        out.insert(out.end(), data.begin() + i * kPacket, data.begin() + (i + 1) * kPacket);
-        if (failed) out[out.size() - kPacket + 1] |= 0x80;
-        ++written;
-      }
-      if (!out.empty() && !write_all(out.data(), out.size())) { rc = 3; break; }
+  const int rc = for_eti_frames(0, 3, [&](const uint8_t* f, int64_t n) {
+    const int64_t np = dabhip_ts_push(d, f, &n, 0);
+    if (np < 0) { std::fprintf(stderr, "eti2ts: %s\n", dabhip_last_error()); return 2; }
+    frames += n;
+    recs.resize(static_cast<size_t>(np));
+    data.resize(static_cast<size_t>(np) * kPacket);
+    if (np > 0 && (dabhip_ts_records(d, 0, 0, recs.data(), np) != np || dabhip_ts_data(d, 0, 0, data.data(), np * kPacket) != np * kPacket)) {
+      std::fprintf(stderr, "eti2ts: %s\n", dabhip_last_error());
+      return 2;
     }
-    if (r == 0) break;
-  }
+    out.clear();
+    for (int64_t i = 0; i < np; ++i) {
+      const bool failed = recs[static_cast<size_t>(i)].flags & DABHIP_TS_RS_FAILED;
+      if (failed && drop_failed) continue;
+      out.insert(out.end(), data.begin() + i * kPacket, data.begin() + (i + 1) * kPacket);
+      if (failed) out[out.size() - kPacket + 1] |= 0x80;
+      ++written;
+    }
+    return out.empty() || write_all(out.data(), out.size()) ? 0 : 3;
+  });
   int64_t c[8] = {0};
   dabhip_ts_stats(d, 0, 0, c);
   std::fprintf(stderr, "eti2ts: %ld frames, sub-channel %d: %lld packets (%ld written), %lld from missed slots, %lld sync losses, %lld bytes skipped, "

@@ -17,6 +17,7 @@
 #include <cstdint>
 
 #include "dabplus.hpp"
+#include "eti_locate.hpp"
 #include "kernels.hpp"
 #include "rs_code.hpp"
 
@@ -39,28 +40,15 @@ __global__ void __launch_bounds__(256) dabplus_locate_kernel(DabPlusFrames fr, c
   if (v >= c + fr.nnew[s]) return;
   const uint8_t* f = v < c ? fr.carry + (static_cast<int64_t>(s) * 4 + v) * kEti : fr.frames + (fr.base[s] + (v - c)) * kEti;
   const uint8_t fct = f[4];
-  const int ficf = f[5] >> 7, nst = f[5] & 0x7f;
   DabPlusLoc* out = loc + t * nsub;
   for (int q = 0; q < nsub; ++q) out[q] = DabPlusLoc{nullptr, 0, fct, 0, {0, 0}};
-  int off = 12 + 4 * nst + 96 * ficf;
-  uint64_t seen = 0;                                 // a SubChId listed twice in the STC: its first entry counts (nsub <= 64)
-  for (int i = 0; i < nst; ++i) {
-    const int scid = f[8 + 4 * i] >> 2;
-    const int stl = ((f[8 + 4 * i + 2] & 3) << 8) | f[8 + 4 * i + 3];
-    const bool fits = off + 8 * stl <= kEti;
-    for (int q = 0; q < nsub; ++q) {
-      if (subch[q] != scid || (seen >> q & 1)) continue;
-      seen |= uint64_t{1} << q;
-      out[q].stl = stl;
-      if (fits && stl > 0 && stl % 3 == 0 && stl <= 3 * kMaxS) {      // s <= 72: the au kernel's LDS copy of a superframe
-        const uint8_t* p = f + off;
-        out[q].ptr = p;
-        out[q].raw_fire = fire_code(p + 2) == ((p[0] << 8) | p[1]);
-      }
+  eti_stc_walk(f, subch, nsub, [out](int q, int stl, bool fits, const uint8_t* p) {
+    out[q].stl = stl;
+    if (fits && stl > 0 && stl % 3 == 0 && stl <= 3 * kMaxS) {        // s <= 72: the au kernel's LDS copy of a superframe
+      out[q].ptr = p;
+      out[q].raw_fire = fire_code(p + 2) == ((p[0] << 8) | p[1]);
     }
-    off += 8 * stl;
-    if (off > kEti) break;
-  }
+  });
 }
 
 __global__ void __launch_bounds__(64) dabplus_sync_kernel(DabPlusFrames fr, int nstreams, int nsub, int maxv, const DabPlusLoc* loc, DabPlusSync* sync,

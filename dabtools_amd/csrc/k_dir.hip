@@ -17,7 +17,7 @@ namespace {
 
 constexpr int kFibsBlock = 256;
 
-__global__ void __launch_bounds__(kFibsBlock) dir_fibs_kernel(DirFrames fr, int maxv, DirFib* fibs, DirFact* facts)
+__global__ void __launch_bounds__(kFibsBlock) dir_fibs_kernel(EtiFrames fr, int maxv, DirFib* fibs, DirFact* facts)
 {
   const int s = blockIdx.x;
   const int t = blockIdx.y * kFibsBlock + threadIdx.x;
@@ -56,7 +56,7 @@ __device__ inline int64_t wave_sum(int64_t x)
   return x;
 }
 
-__global__ void __launch_bounds__(64) dir_merge_kernel(DirFrames fr, const DirFib* fibs, const DirFact* facts, DirStream* state, int* ok_fibs)
+__global__ void __launch_bounds__(64) dir_merge_kernel(EtiFrames fr, const DirFib* fibs, const DirFact* facts, DirStream* state, int* ok_fibs)
 {
   __shared__ DirEntry tab[kDirEntries];
   const int s = blockIdx.x, lane = threadIdx.x;
@@ -174,7 +174,7 @@ __global__ void __launch_bounds__(64) dir_merge_kernel(DirFrames fr, const DirFi
 
 }  // namespace
 
-hipError_t launch_dir_fibs(const DirFrames& fr, int nstreams, int maxv, DirFib* fibs, DirFact* facts, hipStream_t stream)
+hipError_t launch_dir_fibs(const EtiFrames& fr, int nstreams, int maxv, DirFib* fibs, DirFact* facts, hipStream_t stream)
 {
   if (nstreams <= 0 || maxv <= 0) return hipSuccess;
   const dim3 grid(static_cast<unsigned>(nstreams), static_cast<unsigned>((3 * maxv + kFibsBlock - 1) / kFibsBlock));
@@ -182,7 +182,7 @@ hipError_t launch_dir_fibs(const DirFrames& fr, int nstreams, int maxv, DirFib* 
   return hipGetLastError();
 }
 
-hipError_t launch_dir_merge(const DirFrames& fr, int nstreams, const DirFib* fibs, const DirFact* facts, DirStream* state, int* ok_fibs, hipStream_t stream)
+hipError_t launch_dir_merge(const EtiFrames& fr, int nstreams, const DirFib* fibs, const DirFact* facts, DirStream* state, int* ok_fibs, hipStream_t stream)
 {
   if (nstreams <= 0) return hipSuccess;
   hipLaunchKernelGGL(dir_merge_kernel, dim3(static_cast<unsigned>(nstreams)), dim3(64), 0, stream, fr, fibs, facts, state, ok_fibs);

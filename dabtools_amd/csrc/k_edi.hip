@@ -24,7 +24,7 @@ namespace {
 constexpr int kEti = DABHIP_ETI_BYTES;
 constexpr int kWorkWords = kEdiWorkStride / 4;
 
-__global__ void __launch_bounds__(256) edi_plan_kernel(EdiFrames fr, EdiConfig cfg, int nstreams, int maxv, EdiFrame* out)
+__global__ void __launch_bounds__(256) edi_plan_kernel(EtiFrames fr, EdiConfig cfg, int nstreams, int maxv, EdiFrame* out)
 {
   const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (t >= static_cast<int64_t>(nstreams) * maxv) return;
@@ -56,7 +56,7 @@ __device__ inline T wave_scan(T x, int l)
   return x;
 }
 
-__global__ void __launch_bounds__(64 * kEdiScanWaves) edi_scan_kernel(EdiFrames fr, EdiConfig cfg, int nstreams, EdiFrame* frames, EdiState* state, int64_t* counters,
+__global__ void __launch_bounds__(64 * kEdiScanWaves) edi_scan_kernel(EtiFrames fr, EdiConfig cfg, int nstreams, EdiFrame* frames, EdiState* state, int64_t* counters,
                                                                       int64_t* sums)
 {
   const int s = blockIdx.x * kEdiScanWaves + (threadIdx.x >> 6);
@@ -166,7 +166,7 @@ __global__ void __launch_bounds__(1024) edi_bases_kernel(int nstreams, const int
 // one byte into the CRC register through the 256-entry table of edi_crc_byte(0, .)
 __device__ inline uint32_t crc_step(const uint16_t* table, uint32_t reg, uint32_t b) { return ((reg << 8) & 0xFFFF) ^ table[(reg >> 8) ^ b]; }
 
-__global__ void __launch_bounds__(256) edi_assemble_kernel(EdiFrames fr, const EdiFrame* frames, uint8_t* work)
+__global__ void __launch_bounds__(256) edi_assemble_kernel(EtiFrames fr, const EdiFrame* frames, uint8_t* work)
 {
   __shared__ uint32_t pk_w[kWorkWords];
   __shared__ int item_at[kEdiMaxNst], src_at[kEdiMaxNst], item_stl[kEdiMaxNst];
@@ -336,14 +336,14 @@ __global__ void __launch_bounds__(256) edi_fragment_kernel(EdiConfig cfg, const 
 
 }  // namespace
 
-hipError_t launch_edi_plan(const EdiFrames& fr, EdiConfig cfg, int nstreams, int maxv, EdiFrame* out, hipStream_t stream)
+hipError_t launch_edi_plan(const EtiFrames& fr, EdiConfig cfg, int nstreams, int maxv, EdiFrame* out, hipStream_t stream)
 {
   const int64_t n = static_cast<int64_t>(nstreams) * maxv;
   if (n > 0) edi_plan_kernel<<<static_cast<unsigned>((n + 255) / 256), 256, 0, stream>>>(fr, cfg, nstreams, maxv, out);
   return hipGetLastError();
 }
 
-hipError_t launch_edi_scan(const EdiFrames& fr, EdiConfig cfg, int nstreams, EdiFrame* frames, EdiState* state, int64_t* counters, int64_t* sums, int64_t* bases,
+hipError_t launch_edi_scan(const EtiFrames& fr, EdiConfig cfg, int nstreams, EdiFrame* frames, EdiState* state, int64_t* counters, int64_t* sums, int64_t* bases,
                            hipStream_t stream)
 {
   edi_scan_kernel<<<(nstreams + kEdiScanWaves - 1) / kEdiScanWaves, 64 * kEdiScanWaves, 0, stream>>>(fr, cfg, nstreams, frames, state, counters, sums);
@@ -351,7 +351,7 @@ hipError_t launch_edi_scan(const EdiFrames& fr, EdiConfig cfg, int nstreams, Edi
   return hipGetLastError();
 }
 
-hipError_t launch_edi_assemble(const EdiFrames& fr, int64_t nframes, const EdiFrame* frames, uint8_t* work, hipStream_t stream)
+hipError_t launch_edi_assemble(const EtiFrames& fr, int64_t nframes, const EdiFrame* frames, uint8_t* work, hipStream_t stream)
 {
   if (nframes > 0) edi_assemble_kernel<<<static_cast<unsigned>(nframes), 256, 0, stream>>>(fr, frames, work);
   return hipGetLastError();

@@ -20,6 +20,7 @@
 
 #include <cstdint>
 
+#include "eti_locate.hpp"
 #include "kernels.hpp"
 #include "packet.hpp"
 #include "rs_code.hpp"
@@ -30,31 +31,19 @@ namespace {
 constexpr int kEti = DABHIP_ETI_BYTES;
 constexpr int kCarryBytes = kPkCarry * kPkCell;
 
-__global__ void __launch_bounds__(256) packet_locate_kernel(PacketFrames fr, const int32_t* subch, int nsub, int nstreams, int maxv, PacketLoc* loc)
+__global__ void __launch_bounds__(256) packet_locate_kernel(EtiFrames fr, const int32_t* subch, int nsub, int nstreams, int maxv, PacketLoc* loc)
 {
   const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (t >= static_cast<int64_t>(nstreams) * maxv) return;
   const int s = static_cast<int>(t / maxv), v = static_cast<int>(t % maxv);
   if (v >= fr.nnew[s]) return;
   const uint8_t* f = fr.frames + (fr.base[s] + v) * kEti;
-  const int ficf = f[5] >> 7, nst = f[5] & 0x7f;
   PacketLoc* out = loc + t * nsub;
   for (int q = 0; q < nsub; ++q) out[q] = PacketLoc{nullptr, 0, 0};
-  int off = 12 + 4 * nst + 96 * ficf;
-  uint64_t seen = 0;                                 // a SubChId listed twice in the STC: its first entry counts (nsub <= 64)
-  for (int i = 0; i < nst; ++i) {
-    const int scid = f[8 + 4 * i] >> 2;
-    const int stl = ((f[8 + 4 * i + 2] & 3) << 8) | f[8 + 4 * i + 3];
-    const bool fits = off + 8 * stl <= kEti;
-    for (int q = 0; q < nsub; ++q) {
-      if (subch[q] != scid || (seen >> q & 1)) continue;
-      seen |= uint64_t{1} << q;
-      out[q].stl = stl;
-      if (fits && stl > 0 && stl % 3 == 0) out[q].ptr = f + off;
-    }
-    off += 8 * stl;
-    if (off > kEti) break;
-  }
+  eti_stc_walk(f, subch, nsub, [out](int q, int stl, bool fits, const uint8_t* p) {
+    out[q].stl = stl;
+    if (fits && stl > 0 && stl % 3 == 0) out[q].ptr = p;
+  });
 }
 
 __device__ inline PacketLoc& loc_at(PacketLoc* loc, int stream, int v, int sub, int maxv, int nsub)
@@ -76,7 +65,7 @@ __device__ inline const uint8_t* cell_ptr(const PacketLoc* loc, int stream, int 
   return l.ptr + (u - l.cell0) * kPkCell;
 }
 
-__global__ void __launch_bounds__(64) packet_sync_kernel(PacketFrames fr, int nstreams, int nsub, int maxv, const uint8_t* fec, PacketLoc* loc, PacketSync* sync,
+__global__ void __launch_bounds__(64) packet_sync_kernel(EtiFrames fr, int nstreams, int nsub, int maxv, const uint8_t* fec, PacketLoc* loc, PacketSync* sync,
                                                          const uint8_t* carry, PacketSlot* slots, int cap, int* nunits, int* lane_buf, int* ncar_in, int* ncar_out,
                                                          int* lo_out, int64_t* counters, int* totals)
 {
@@ -219,7 +208,7 @@ __device__ inline int unit_of(const PacketUnit* units, int nunits, int c)
   return lo;
 }
 
-__global__ void __launch_bounds__(256) packet_gather_kernel(PacketFrames fr, const PacketUnit* units, const int* totals, const PacketLoc* loc, int maxv, int nsub,
+__global__ void __launch_bounds__(256) packet_gather_kernel(EtiFrames fr, const PacketUnit* units, const int* totals, const PacketLoc* loc, int maxv, int nsub,
                                                            const uint8_t* carry, const int* ncar_in, uint8_t* cells)
 {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -378,7 +367,7 @@ __global__ void __launch_bounds__(64) packet_walk_kernel(const PacketUnit* units
 }
 
 // a lane's unconsumed cells (virtual cells lo .. lo + ncar_out - 1) into the other carry buffer
-__global__ void __launch_bounds__(128) packet_carry_kernel(PacketFrames fr, const PacketLoc* loc, int maxv, int nsub, const uint8_t* carry, const int* ncar_in,
+__global__ void __launch_bounds__(128) packet_carry_kernel(EtiFrames fr, const PacketLoc* loc, int maxv, int nsub, const uint8_t* carry, const int* ncar_in,
                                                           const int* ncar_out, const int* lo, uint8_t* carry_next)
 {
   const int lane = blockIdx.x, i = threadIdx.x;
@@ -391,14 +380,14 @@ __global__ void __launch_bounds__(128) packet_carry_kernel(PacketFrames fr, cons
 
 }  // namespace
 
-hipError_t launch_packet_locate(const PacketFrames& fr, const int32_t* subch, int nsub, int nstreams, int maxv, PacketLoc* loc, hipStream_t stream)
+hipError_t launch_packet_locate(const EtiFrames& fr, const int32_t* subch, int nsub, int nstreams, int maxv, PacketLoc* loc, hipStream_t stream)
 {
   const int64_t n = static_cast<int64_t>(nstreams) * maxv;
   if (n > 0) packet_locate_kernel<<<static_cast<unsigned>((n + 255) / 256), 256, 0, stream>>>(fr, subch, nsub, nstreams, maxv, loc);
   return hipGetLastError();
 }
 
-hipError_t launch_packet_sync(const PacketFrames& fr, int nstreams, int nsub, int maxv, const uint8_t* fec, PacketLoc* loc, PacketSync* sync, const uint8_t* carry,
+hipError_t launch_packet_sync(const EtiFrames& fr, int nstreams, int nsub, int maxv, const uint8_t* fec, PacketLoc* loc, PacketSync* sync, const uint8_t* carry,
                               PacketSlot* slots, int cap, int* nunits, int* lane_buf, int* ncar_in, int* ncar_out, int* lo, int64_t* counters, PacketUnit* units,
                               int* lane_unit_base, int* lane_buf_base, int* totals, hipStream_t stream)
 {
@@ -409,7 +398,7 @@ hipError_t launch_packet_sync(const PacketFrames& fr, int nstreams, int nsub, in
   return hipGetLastError();
 }
 
-hipError_t launch_packet_gather(const PacketFrames& fr, const PacketUnit* units, const int* totals, int ncells, const PacketLoc* loc, int maxv, int nsub,
+hipError_t launch_packet_gather(const EtiFrames& fr, const PacketUnit* units, const int* totals, int ncells, const PacketLoc* loc, int maxv, int nsub,
                                 const uint8_t* carry, const int* ncar_in, uint8_t* cells, hipStream_t stream)
 {
   if (ncells > 0) packet_gather_kernel<<<(ncells + 255) / 256, 256, 0, stream>>>(fr, units, totals, loc, maxv, nsub, carry, ncar_in, cells);
@@ -440,7 +429,7 @@ hipError_t launch_packet_walk(const PacketUnit* units, const int* totals, int nu
   return hipGetLastError();
 }
 
-hipError_t launch_packet_carry(const PacketFrames& fr, int nlanes, const PacketLoc* loc, int maxv, int nsub, const uint8_t* carry, const int* ncar_in,
+hipError_t launch_packet_carry(const EtiFrames& fr, int nlanes, const PacketLoc* loc, int maxv, int nsub, const uint8_t* carry, const int* ncar_in,
                                const int* ncar_out, const int* lo, uint8_t* carry_next, hipStream_t stream)
 {
   if (nlanes > 0) packet_carry_kernel<<<nlanes, 128, 0, stream>>>(fr, loc, maxv, nsub, carry, ncar_in, ncar_out, lo, carry_next);

@@ -25,6 +25,7 @@
 
 #include <cstdint>
 
+#include "eti_locate.hpp"
 #include "kernels.hpp"
 #include "rs_code.hpp"
 #include "ts.hpp"
@@ -35,31 +36,19 @@ namespace {
 constexpr int kEti = DABHIP_ETI_BYTES;
 constexpr int kSyncWaves = kTsSyncWaves;
 
-__global__ void __launch_bounds__(256) ts_locate_kernel(PacketFrames fr, const int32_t* subch, int nsub, int nstreams, int maxv, TsLoc* loc)
+__global__ void __launch_bounds__(256) ts_locate_kernel(EtiFrames fr, const int32_t* subch, int nsub, int nstreams, int maxv, TsLoc* loc)
 {
   const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (t >= static_cast<int64_t>(nstreams) * maxv) return;
   const int s = static_cast<int>(t / maxv), v = static_cast<int>(t % maxv);
   if (v >= fr.nnew[s]) return;
   const uint8_t* f = fr.frames + (fr.base[s] + v) * kEti;
-  const int ficf = f[5] >> 7, nst = f[5] & 0x7f;
   TsLoc* out = loc + t * nsub;
   for (int q = 0; q < nsub; ++q) out[q] = TsLoc{nullptr, 0, 0, 0, 0};
-  int off = 12 + 4 * nst + 96 * ficf;
-  uint64_t seen = 0;                                 // a SubChId listed twice in the STC: its first entry counts (nsub <= 64)
-  for (int i = 0; i < nst; ++i) {
-    const int scid = f[8 + 4 * i] >> 2;
-    const int stl = ((f[8 + 4 * i + 2] & 3) << 8) | f[8 + 4 * i + 3];
-    const bool fits = off + 8 * stl <= kEti;
-    for (int q = 0; q < nsub; ++q) {
-      if (subch[q] != scid || (seen >> q & 1)) continue;
-      seen |= uint64_t{1} << q;
-      out[q].stl = stl;
-      if (fits && stl > 0) out[q].ptr = f + off;
-    }
-    off += 8 * stl;
-    if (off > kEti) break;
-  }
+  eti_stc_walk(f, subch, nsub, [out](int q, int stl, bool fits, const uint8_t* p) {
+    out[q].stl = stl;
+    if (fits && stl > 0) out[q].ptr = p;
+  });
 }
 
 // the lane of this wave (kSyncWaves waves to a workgroup), or -1
@@ -82,7 +71,7 @@ __device__ inline int wave_scan(int x, int l)
 
 // A frame breaks the stream in front of it when it gives no bytes, or when its STL differs from that of the frame before it (which gave
 // bytes).  So the breaks and the frames' first positions are prefix sums, taken 64 frames at a time.
-__global__ void __launch_bounds__(64 * kSyncWaves) ts_layout_kernel(PacketFrames fr, int nlanes, int nsub, int maxv, TsLoc* loc, const TsSync* sync, TsLane* lanes,
+__global__ void __launch_bounds__(64 * kSyncWaves) ts_layout_kernel(EtiFrames fr, int nlanes, int nsub, int maxv, TsLoc* loc, const TsSync* sync, TsLane* lanes,
                                                                     int flag_cap, int* totals)
 {
   const int lane = wave_lane(nlanes);
@@ -133,7 +122,7 @@ struct TsView {
   int nsub, nnew, ncar;
 };
 
-__device__ inline TsView ts_view(const PacketFrames& fr, const TsLoc* loc, int lane, int nsub, int maxv, const uint8_t* carry, int ncar)
+__device__ inline TsView ts_view(const EtiFrames& fr, const TsLoc* loc, int lane, int nsub, int maxv, const uint8_t* carry, int ncar)
 {
   const int s = lane / nsub, q = lane % nsub;
   return TsView{loc + static_cast<int64_t>(s) * maxv * nsub + q, carry + static_cast<int64_t>(lane) * kTsCarryStride, nsub, fr.nnew[s], ncar};
@@ -164,7 +153,7 @@ __device__ inline uint8_t view_byte_seg(const TsView& v, int u, int& seg)
 }
 
 // Workgroup b works on lane b / per_lane; its 4 waves take words (b % per_lane) * 4 + wave, then 4 per_lane further, ...
-__global__ void __launch_bounds__(256) ts_runs_kernel(PacketFrames fr, int nlanes, int nsub, int maxv, int per_lane, const TsLoc* loc, const TsLane* lanes,
+__global__ void __launch_bounds__(256) ts_runs_kernel(EtiFrames fr, int nlanes, int nsub, int maxv, int per_lane, const TsLoc* loc, const TsLane* lanes,
                                                      const uint8_t* carry, const int* totals, unsigned long long* flags)
 {
   if (totals[kTsTotOverflow]) return;
@@ -187,7 +176,7 @@ __global__ void __launch_bounds__(256) ts_runs_kernel(PacketFrames fr, int nlane
   }
 }
 
-__global__ void __launch_bounds__(64 * kSyncWaves) ts_sync_kernel(PacketFrames fr, int nlanes, int nsub, int maxv, const TsLoc* loc, TsSync* sync, TsLane* lanes,
+__global__ void __launch_bounds__(64 * kSyncWaves) ts_sync_kernel(EtiFrames fr, int nlanes, int nsub, int maxv, const TsLoc* loc, TsSync* sync, TsLane* lanes,
                                                                   const uint8_t* carry, const unsigned long long* flags, TsSlot* slots, int cap, int* nunits,
                                                                   int64_t* counters, int* totals)
 {
@@ -345,7 +334,7 @@ __global__ void __launch_bounds__(256) ts_jobs_kernel(const TsSlot* slots, int c
 }
 
 // Thread t writes byte t of the word buffer: in group g = t / 13056, byte k = 4 ((t % 13056) / 256) + t % 4 of word 64 g + (t % 256) / 4.
-__global__ void __launch_bounds__(256) ts_gather_kernel(PacketFrames fr, const TsUnit* units, const int* totals, const TsLoc* loc, int maxv, int nsub,
+__global__ void __launch_bounds__(256) ts_gather_kernel(EtiFrames fr, const TsUnit* units, const int* totals, const TsLoc* loc, int maxv, int nsub,
                                                        const uint8_t* carry, const TsLane* lanes, uint8_t* words)
 {
   const int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -446,7 +435,7 @@ __global__ void __launch_bounds__(256) ts_parse_kernel(const TsUnit* units, cons
 }
 
 // a lane's unconsumed bytes (positions lo .. nv - 1) into the other carry buffer
-__global__ void __launch_bounds__(256) ts_carry_kernel(PacketFrames fr, const TsLoc* loc, int maxv, int nsub, const uint8_t* carry, const TsLane* lanes, const int* totals,
+__global__ void __launch_bounds__(256) ts_carry_kernel(EtiFrames fr, const TsLoc* loc, int maxv, int nsub, const uint8_t* carry, const TsLane* lanes, const int* totals,
                                                       uint8_t* carry_next)
 {
   if (totals[kTsTotOverflow]) return;
@@ -461,7 +450,7 @@ __global__ void __launch_bounds__(256) ts_carry_kernel(PacketFrames fr, const Ts
 
 }  // namespace
 
-hipError_t launch_ts_locate(const PacketFrames& fr, const int32_t* subch, int nsub, int nstreams, int maxv, TsLoc* loc, const TsSync* sync, TsLane* lanes, int flag_cap,
+hipError_t launch_ts_locate(const EtiFrames& fr, const int32_t* subch, int nsub, int nstreams, int maxv, TsLoc* loc, const TsSync* sync, TsLane* lanes, int flag_cap,
                             int* totals, hipStream_t stream)
 {
   const int64_t n = static_cast<int64_t>(nstreams) * maxv;
@@ -471,7 +460,7 @@ hipError_t launch_ts_locate(const PacketFrames& fr, const int32_t* subch, int ns
   return hipGetLastError();
 }
 
-hipError_t launch_ts_runs(const PacketFrames& fr, int nlanes, int nsub, int maxv, int per_lane, const TsLoc* loc, const TsLane* lanes, const uint8_t* carry,
+hipError_t launch_ts_runs(const EtiFrames& fr, int nlanes, int nsub, int maxv, int per_lane, const TsLoc* loc, const TsLane* lanes, const uint8_t* carry,
                           const int* totals, uint64_t* flags, hipStream_t stream)
 {
   ts_runs_kernel<<<static_cast<unsigned>(static_cast<int64_t>(nlanes) * per_lane), 256, 0, stream>>>(fr, nlanes, nsub, maxv, per_lane, loc, lanes, carry, totals,
@@ -479,7 +468,7 @@ hipError_t launch_ts_runs(const PacketFrames& fr, int nlanes, int nsub, int maxv
   return hipGetLastError();
 }
 
-hipError_t launch_ts_sync(const PacketFrames& fr, int nlanes, int nsub, int maxv, const TsLoc* loc, TsSync* sync, TsLane* lanes, const uint8_t* carry,
+hipError_t launch_ts_sync(const EtiFrames& fr, int nlanes, int nsub, int maxv, const TsLoc* loc, TsSync* sync, TsLane* lanes, const uint8_t* carry,
                           const uint64_t* flags, TsSlot* slots, int cap, int* nunits, int64_t* counters, int* totals, hipStream_t stream)
 {
   ts_sync_kernel<<<(nlanes + kSyncWaves - 1) / kSyncWaves, 64 * kSyncWaves, 0, stream>>>(fr, nlanes, nsub, maxv, loc, sync, lanes, carry,
@@ -496,7 +485,7 @@ hipError_t launch_ts_jobs(int nlanes, const TsSlot* slots, int cap, const int* n
   return hipGetLastError();
 }
 
-hipError_t launch_ts_gather(const PacketFrames& fr, const TsUnit* units, const int* totals, int64_t nunits, const TsLoc* loc, int maxv, int nsub, const uint8_t* carry,
+hipError_t launch_ts_gather(const EtiFrames& fr, const TsUnit* units, const int* totals, int64_t nunits, const TsLoc* loc, int maxv, int nsub, const uint8_t* carry,
                             const TsLane* lanes, uint8_t* words, hipStream_t stream)
 {
   const int64_t n = ts_word_buffer_bytes(nunits);
@@ -523,7 +512,7 @@ hipError_t launch_ts_parse(const TsUnit* units, const int* totals, int64_t nunit
   return hipGetLastError();
 }
 
-hipError_t launch_ts_carry(const PacketFrames& fr, int nlanes, const TsLoc* loc, int maxv, int nsub, const uint8_t* carry, const TsLane* lanes, const int* totals,
+hipError_t launch_ts_carry(const EtiFrames& fr, int nlanes, const TsLoc* loc, int maxv, int nsub, const uint8_t* carry, const TsLane* lanes, const int* totals,
                            uint8_t* carry_next, hipStream_t stream)
 {
   if (nlanes > 0) ts_carry_kernel<<<nlanes, 256, 0, stream>>>(fr, loc, maxv, nsub, carry, lanes, totals, carry_next);

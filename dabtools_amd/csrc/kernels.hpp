@@ -209,18 +209,18 @@ hipError_t launch_dabplus_carry(const DabPlusFrames& fr, int nstreams, uint8_t* 
 // syn: 16 bytes of scratch per code word); cand: per
 // buffer cell, the length of the packet the walk may take there (crc_tab: the CRC-16 byte table); walk: a record per buffer cell (length 0: none)
 // and the counters; carry: every lane's unconsumed cells (at most 102).
-hipError_t launch_packet_locate(const PacketFrames& fr, const int32_t* subch, int nsub, int nstreams, int maxv, PacketLoc* loc, hipStream_t stream);
-hipError_t launch_packet_sync(const PacketFrames& fr, int nstreams, int nsub, int maxv, const uint8_t* fec, PacketLoc* loc, PacketSync* sync, const uint8_t* carry,
+hipError_t launch_packet_locate(const EtiFrames& fr, const int32_t* subch, int nsub, int nstreams, int maxv, PacketLoc* loc, hipStream_t stream);
+hipError_t launch_packet_sync(const EtiFrames& fr, int nstreams, int nsub, int maxv, const uint8_t* fec, PacketLoc* loc, PacketSync* sync, const uint8_t* carry,
                               PacketSlot* slots, int cap, int* nunits, int* lane_buf, int* ncar_in, int* ncar_out, int* lo, int64_t* counters, PacketUnit* units,
                               int* lane_unit_base, int* lane_buf_base, int* totals, hipStream_t stream);
-hipError_t launch_packet_gather(const PacketFrames& fr, const PacketUnit* units, const int* totals, int ncells, const PacketLoc* loc, int maxv, int nsub,
+hipError_t launch_packet_gather(const EtiFrames& fr, const PacketUnit* units, const int* totals, int ncells, const PacketLoc* loc, int maxv, int nsub,
                                 const uint8_t* carry, const int* ncar_in, uint8_t* cells, hipStream_t stream);
 hipError_t launch_packet_rs(const PacketUnit* units, const int* totals, int nunits, const uint8_t* gf_tables, uint8_t* cells, uint8_t* cw_status, uint32_t* syn,
                             hipStream_t stream);
 hipError_t launch_packet_cand(const PacketUnit* units, const int* totals, int ncells, const uint16_t* crc_tab, const uint8_t* cells, uint8_t* cand, hipStream_t stream);
 hipError_t launch_packet_walk(const PacketUnit* units, const int* totals, int nunits, const uint8_t* cells, const uint8_t* cand, const uint8_t* cw_status,
                               dabhip_packet_rec* recs, int64_t* counters, int* npackets, hipStream_t stream);
-hipError_t launch_packet_carry(const PacketFrames& fr, int nlanes, const PacketLoc* loc, int maxv, int nsub, const uint8_t* carry, const int* ncar_in,
+hipError_t launch_packet_carry(const EtiFrames& fr, int nlanes, const PacketLoc* loc, int maxv, int nsub, const uint8_t* carry, const int* ncar_in,
                                const int* ncar_out, const int* lo, uint8_t* carry_next, hipStream_t stream);
 
 // k_ts.hip: MPEG-2 TS packets out of ETI frames (ts.hpp has the types, ts_sync.hpp the sync rule and the position map, dabhip.h the rules in
@@ -230,29 +230,29 @@ hipError_t launch_packet_carry(const PacketFrames& fr, int nlanes, const PacketL
 // buffer (ts_word_byte); syndrome / decode: the code words, corrected in place (cw_status: symbols corrected, 0xff = failed; syn: 16 bytes of
 // scratch per code word; gf_tables as the packet stage's); parse: a record and 188 bytes per unit, the counters; carry: every lane's
 // unconsumed bytes (at most 2447).
-hipError_t launch_ts_locate(const PacketFrames& fr, const int32_t* subch, int nsub, int nstreams, int maxv, TsLoc* loc, const TsSync* sync, TsLane* lanes, int flag_cap,
+hipError_t launch_ts_locate(const EtiFrames& fr, const int32_t* subch, int nsub, int nstreams, int maxv, TsLoc* loc, const TsSync* sync, TsLane* lanes, int flag_cap,
                             int* totals, hipStream_t stream);
-hipError_t launch_ts_runs(const PacketFrames& fr, int nlanes, int nsub, int maxv, int per_lane, const TsLoc* loc, const TsLane* lanes, const uint8_t* carry,
+hipError_t launch_ts_runs(const EtiFrames& fr, int nlanes, int nsub, int maxv, int per_lane, const TsLoc* loc, const TsLane* lanes, const uint8_t* carry,
                           const int* totals, uint64_t* flags, hipStream_t stream);
-hipError_t launch_ts_sync(const PacketFrames& fr, int nlanes, int nsub, int maxv, const TsLoc* loc, TsSync* sync, TsLane* lanes, const uint8_t* carry,
+hipError_t launch_ts_sync(const EtiFrames& fr, int nlanes, int nsub, int maxv, const TsLoc* loc, TsSync* sync, TsLane* lanes, const uint8_t* carry,
                           const uint64_t* flags, TsSlot* slots, int cap, int* nunits, int64_t* counters, int* totals, hipStream_t stream);
 hipError_t launch_ts_jobs(int nlanes, const TsSlot* slots, int cap, const int* nunits, int* lane_unit_base, const TsSync* sync, const TsLane* lanes, TsUnit* units,
                           int64_t unit_cap, int* totals, hipStream_t stream);
-hipError_t launch_ts_gather(const PacketFrames& fr, const TsUnit* units, const int* totals, int64_t nunits, const TsLoc* loc, int maxv, int nsub, const uint8_t* carry,
+hipError_t launch_ts_gather(const EtiFrames& fr, const TsUnit* units, const int* totals, int64_t nunits, const TsLoc* loc, int maxv, int nsub, const uint8_t* carry,
                             const TsLane* lanes, uint8_t* words, hipStream_t stream);
 hipError_t launch_ts_syndrome(const int* totals, int64_t nunits, const uint8_t* gf_tables, const uint8_t* words, uint8_t* cw_status, uint32_t* syn, hipStream_t stream);
 hipError_t launch_ts_decode(const int* totals, int64_t nunits, const uint8_t* gf_tables, uint8_t* words, uint8_t* cw_status, const uint32_t* syn, hipStream_t stream);
 hipError_t launch_ts_parse(const TsUnit* units, const int* totals, int64_t nunits, const uint8_t* words, const uint8_t* cw_status, dabhip_ts_rec* recs, uint8_t* data,
                            int64_t* counters, hipStream_t stream);
-hipError_t launch_ts_carry(const PacketFrames& fr, int nlanes, const TsLoc* loc, int maxv, int nsub, const uint8_t* carry, const TsLane* lanes, const int* totals,
+hipError_t launch_ts_carry(const EtiFrames& fr, int nlanes, const TsLoc* loc, int maxv, int nsub, const uint8_t* carry, const TsLane* lanes, const int* totals,
                            uint8_t* carry_next, hipStream_t stream);
 
 // k_dir.hip: the ensemble directory out of ETI frames (dir.hpp has the types, dir_figs.hpp the rules, dabhip.h the rules in words).  fibs: a thread
 // per (stream, new frame, FIB): frame header, CRC, FIG walk; its facts into the FIB's kDirFactSlots slots of `facts` and its DirFib record, both
 // indexed by (base[s] + frame) * 3 + fib.  merge: a wave per stream applies the stream's facts in order to its tables (staged in LDS), adds its
 // counters and leaves the FIBs of this push whose CRC held in ok_fibs[s].
-hipError_t launch_dir_fibs(const DirFrames& fr, int nstreams, int maxv, DirFib* fibs, DirFact* facts, hipStream_t stream);
-hipError_t launch_dir_merge(const DirFrames& fr, int nstreams, const DirFib* fibs, const DirFact* facts, DirStream* state, int* ok_fibs, hipStream_t stream);
+hipError_t launch_dir_fibs(const EtiFrames& fr, int nstreams, int maxv, DirFib* fibs, DirFact* facts, hipStream_t stream);
+hipError_t launch_dir_merge(const EtiFrames& fr, int nstreams, const DirFib* fibs, const DirFact* facts, DirStream* state, int* ok_fibs, hipStream_t stream);
 
 // k_probe.hip: streaming rates of this device (fill, copy, K2's read/write mix) in GB/s -- bench.py's yardstick beside the K2 figure
 int stream_ceiling(int device, size_t bytes, int reps, double* gbs);

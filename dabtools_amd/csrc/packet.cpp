@@ -10,11 +10,10 @@
 
 #include "../../include/dabhip.h"
 #include "dab_bits.hpp"
+#include "eti_lanes.hpp"
 #include "kernels.hpp"
-#include "rs_code.hpp"
 #include "packet.hpp"
 #include "packet_groups.hpp"
-#include "stage_frame.hpp"
 
 using namespace dabhip;
 
@@ -23,8 +22,7 @@ const char* const kStages[7] = {"locate", "sync", "gather", "rs", "cand", "walk"
 }
 
 struct dabhip_packet {
-  int nstreams = 0, nsub = 0;
-  DeviceBuffer<int32_t> subch;
+  EtiLanes lanes{"packet"};                         // its host copy: the lanes' first cells in the cell buffer (lane_buf_base)
   DeviceBuffer<uint8_t> fec;
   DeviceBuffer<PacketSync> sync;
   DeviceBuffer<int64_t> counters;
@@ -41,34 +39,14 @@ struct dabhip_packet {
   DeviceBuffer<uint16_t> crc_tab;
   DeviceBuffer<dabhip_packet_rec> recs;
   int64_t n_units = 0, n_cells = 0;
-  // host copies of the last push's lane bases, fetched on first use
-  mutable bool fetched = false;
-  mutable std::vector<int> h_buf_base;
   StageFrame<7> f{"packet", kStages};
-
-  bool fetch() const
-  {
-    if (fetched) return true;
-    if (!f.use_device()) return false;
-    const size_t nlanes = static_cast<size_t>(nstreams) * nsub;
-    h_buf_base.assign(nlanes + 1, 0);
-    if (n_cells > 0 && !f.ok(blocking_copy(h_buf_base.data(), lane_buf_base.get(), sizeof(int) * (nlanes + 1), hipMemcpyDeviceToHost), "records")) return false;
-    fetched = true;
-    return true;
-  }
-
-  bool lane_ok(int s, int q) const
-  {
-    if (s < 0 || s >= nstreams || q < 0 || q >= nsub) { set_error("packet: no such stream / sub-channel"); return false; }
-    return true;
-  }
 
   // the per-cell records of one lane of the last push, and its cells when asked for
   bool lane_cells(int stream, int sub, std::vector<dabhip_packet_rec>& r, std::vector<uint8_t>* bytes) const
   {
-    if (!lane_ok(stream, sub) || !fetch()) return false;
-    const int l = stream * nsub + sub;
-    const int64_t a = h_buf_base[l], n = h_buf_base[l + 1] - a;
+    if (!lanes.lane_ok(stream, sub) || !lanes.fetch(f, lane_buf_base.get(), n_cells > 0)) return false;
+    int64_t a = 0, n = 0;
+    lanes.range(stream, sub, a, n);
     r.resize(static_cast<size_t>(n));
     if (bytes) bytes->resize(static_cast<size_t>(n) * kPkCell);
     if (n == 0) return true;
@@ -83,30 +61,21 @@ extern "C" dabhip_packet* dabhip_packet_create(int device, int nstreams, const i
   StageFrame<7>& f = d->f;
   if (!f.open(device, "no HIP device: the packet-mode stage runs on the GPU only", "packet_create: device index out of range")) return nullptr;
   const auto ok = [&f](hipError_t e, const char* what) { return f.ok(e, what); };
-  if (nstreams <= 0 || nsub <= 0 || nsub > 64 || !subch_ids || !fec_flags) { set_error("packet_create: bad arguments"); return nullptr; }
-  for (int q = 0; q < nsub; ++q)
-    if (subch_ids[q] < 0 || subch_ids[q] > 63) { set_error("packet_create: SubChId out of range"); return nullptr; }
-  if (static_cast<int64_t>(nstreams) * nsub > (1 << 24)) { set_error("packet_create: too many (stream, sub-channel) pairs"); return nullptr; }
-  d->nstreams = nstreams;
-  d->nsub = nsub;
-  const size_t nlanes = static_cast<size_t>(nstreams) * nsub;
-  GfRs<kPkRoots> gf;
-  rs_tables_fill(gf);
+  if (!d->lanes.create(f, nstreams, subch_ids, nsub, fec_flags != nullptr, 1 << 24)) return nullptr;
+  const size_t nlanes = d->lanes.count();
   std::vector<uint16_t> crc(256);
   for (int v = 0; v < 256; ++v) {
     const uint8_t b = static_cast<uint8_t>(v);
     crc[v] = crc16_ccitt(&b, 1, 0);   // the CRC register after byte v from 0: the kernel's table-driven step
   }
   const size_t carry_bytes = nlanes * kPkCarry * kPkCell;
-  bool good = d->subch.reserve(nsub) && d->fec.reserve(nsub) && d->sync.reserve(nlanes) && d->counters.reserve(nlanes * kPkCntN) && d->gf.reserve(sizeof gf) &&
-              d->crc_tab.reserve(crc.size()) && d->carry[0].reserve(carry_bytes) && d->carry[1].reserve(carry_bytes) && d->totals.reserve(4) &&
+  bool good = d->fec.reserve(nsub) && d->sync.reserve(nlanes) && d->counters.reserve(nlanes * kPkCntN) && d->crc_tab.reserve(crc.size()) &&
+              d->carry[0].reserve(carry_bytes) && d->carry[1].reserve(carry_bytes) && d->totals.reserve(4) &&
               d->nunits.reserve(nlanes) && d->lane_buf.reserve(nlanes) && d->ncar_in.reserve(nlanes) && d->ncar_out.reserve(nlanes) && d->lo.reserve(nlanes) &&
               d->lane_unit_base.reserve(nlanes + 1) && d->lane_buf_base.reserve(nlanes + 1);
-  good = good && ok(hipMemcpy(d->subch.get(), subch_ids, sizeof(int32_t) * nsub, hipMemcpyHostToDevice), "upload") &&
-         ok(hipMemcpy(d->fec.get(), fec_flags, static_cast<size_t>(nsub), hipMemcpyHostToDevice), "upload") &&
+  good = good && ok(hipMemcpy(d->fec.get(), fec_flags, static_cast<size_t>(nsub), hipMemcpyHostToDevice), "upload") &&
          ok(hipMemset(d->sync.get(), 0, sizeof(PacketSync) * nlanes), "clear") && ok(hipMemset(d->counters.get(), 0, sizeof(int64_t) * nlanes * kPkCntN), "clear") &&
-         ok(hipMemcpy(d->gf.get(), &gf, sizeof gf, hipMemcpyHostToDevice), "upload") &&
-         ok(hipMemcpy(d->crc_tab.get(), crc.data(), crc.size() * 2, hipMemcpyHostToDevice), "upload");
+         upload_rs_tables<kPkRoots>(f, d->gf) && ok(hipMemcpy(d->crc_tab.get(), crc.data(), crc.size() * 2, hipMemcpyHostToDevice), "upload");
   return good ? d.release() : nullptr;
 }
 
@@ -118,49 +87,23 @@ extern "C" int64_t dabhip_packet_push(dabhip_packet* d, const uint8_t* frames, c
   StageFrame<7>& f = d->f;
   const auto ok = [&f](hipError_t e, const char* what) { return f.ok(e, what); };
   if (!f.use_device()) return -1;
-  const int ns = d->nstreams, nsub = d->nsub;
-  std::vector<int64_t> base(static_cast<size_t>(ns));
-  int64_t total = 0;
-  int maxv = 0;
-  for (int s = 0; s < ns; ++s) {
-    if (counts[s] < 0 || counts[s] > (1 << 16)) { set_error("packet_push: bad frame count"); return -1; }
-    base[s] = total;
-    total += counts[s];
-    maxv = std::max<int>(maxv, static_cast<int>(counts[s]));
-  }
-  if (total > 0 && !frames) { set_error("packet_push: null frames"); return -1; }
-  const uint8_t* src = frames;
-  if (total > 0 && !on_device) {
-    const size_t bytes = static_cast<size_t>(total) * DABHIP_ETI_BYTES;
-    if (!d->staging.reserve(bytes) || !ok(hipMemcpyAsync(d->staging.get(), frames, bytes, hipMemcpyHostToDevice, f.stream), "upload")) return -1;
-    src = d->staging.get();
-  }
-  // per-stream metadata in one upload: base | nnew
-  std::vector<uint8_t> meta(static_cast<size_t>(ns) * 12);
-  std::memcpy(meta.data(), base.data(), sizeof(int64_t) * ns);
-  for (int s = 0; s < ns; ++s) {
-    const int n = static_cast<int>(counts[s]);
-    std::memcpy(meta.data() + 8 * ns + 4 * s, &n, 4);
-  }
-  const size_t nlanes = static_cast<size_t>(ns) * nsub;
+  const int ns = d->lanes.nstreams, nsub = d->lanes.nsub;
+  const EtiPush p = plan_eti_push("packet_push", counts, ns, !frames, 1 << 16, kEtiNoTotalBound);
+  if (!p.refusal.empty()) { set_error(p.refusal); return -1; }
+  EtiFrames fr;
+  if (!f.place(p, frames, on_device, d->staging, d->meta, fr)) return -1;
+  const size_t nlanes = d->lanes.count();
+  const int maxv = p.maxv;
   // the units a lane can give in one push: its frames without FEC; with it, a frame per 103 of its carried and new cells (256 per ETI frame at
   // most) and one more for the frame a first run completes.  (Units never share a cell, so a lane gives floor((102 + 255 maxv) / 103) at most:
   // cap - 2 or less.  tests/host_sanitize/packet_units.cpp reaches exactly that over every rate, carried count and maxv of 1, 2, 3 and 64: at
   // worst 159 units in 162 slots, 0.981.)  The sync kernel flags a lane that passes cap all the same.
   const int cap = std::max(maxv, (kPkCarry + maxv * 256) / kPkFrameCells + 1) + 1;
-  if (!d->meta.reserve(meta.size()) || !d->loc.reserve(static_cast<size_t>(ns) * std::max(maxv, 1) * nsub) || !d->slots.reserve(nlanes * cap) || !d->units.reserve(nlanes * cap))
-    return -1;
-  // the host copy of meta must outlive the asynchronous copy: hipMemcpy from pageable memory returns once the bytes are staged
-  if (!ok(hipMemcpyAsync(d->meta.get(), meta.data(), meta.size(), hipMemcpyHostToDevice, f.stream), "upload") || !ok(hipStreamSynchronize(f.stream), "upload"))
-    return -1;
-  PacketFrames fr;
-  fr.frames = src;
-  fr.base = reinterpret_cast<const int64_t*>(d->meta.get());
-  fr.nnew = reinterpret_cast<const int*>(d->meta.get() + 8 * ns);
+  if (!d->loc.reserve(static_cast<size_t>(ns) * std::max(maxv, 1) * nsub) || !d->slots.reserve(nlanes * cap) || !d->units.reserve(nlanes * cap)) return -1;
   hipStream_t st = f.stream;
   const uint8_t* carry = d->carry[d->cur].get();
   int totals[4] = {0, 0, 0, 0};
-  bool good = f.mark(0) && ok(launch_packet_locate(fr, d->subch.get(), nsub, ns, maxv, d->loc.get(), st), "locate") &&
+  bool good = f.mark(0) && ok(launch_packet_locate(fr, d->lanes.subch.get(), nsub, ns, maxv, d->loc.get(), st), "locate") &&
               f.mark(1) && ok(hipMemsetAsync(d->totals.get(), 0, sizeof totals, st), "clear") &&
               ok(launch_packet_sync(fr, ns, nsub, maxv, d->fec.get(), d->loc.get(), d->sync.get(), carry, d->slots.get(), cap, d->nunits.get(), d->lane_buf.get(),
                                     d->ncar_in.get(), d->ncar_out.get(), d->lo.get(), d->counters.get(), d->units.get(), d->lane_unit_base.get(),
@@ -171,7 +114,7 @@ extern "C" int64_t dabhip_packet_push(dabhip_packet* d, const uint8_t* frames, c
   if (totals[3]) { set_error("packet_push: a lane gave more units than its slots hold; the handle's state is lost"); return -1; }
   d->n_units = totals[0];
   d->n_cells = totals[1];
-  d->fetched = false;
+  d->lanes.fetched = false;
   const int nu = totals[0], nc = totals[1];
   const size_t cu = static_cast<size_t>(nu ? nu : 1), cc = static_cast<size_t>(nc ? nc : 1);
   good = d->cells.reserve(cc * kPkCell) && d->cand.reserve(cc) && d->recs.reserve(cc) && d->cw_status.reserve(cu * kPkRows) && d->syn.reserve(cu * kPkRows * 4) &&
@@ -221,10 +164,7 @@ extern "C" int64_t dabhip_packet_data(const dabhip_packet* d, int stream, int su
 extern "C" int dabhip_packet_stats(const dabhip_packet* d, int stream, int sub, int64_t* counters8)
 {
   if (!d || !counters8) { set_error("packet_stats: null argument"); return -1; }
-  if (!d->lane_ok(stream, sub)) return -1;
-  if (!d->f.use_device()) return -1;
-  return d->f.ok(blocking_copy(counters8, d->counters.get() + (static_cast<size_t>(stream) * d->nsub + sub) * kPkCntN, sizeof(int64_t) * kPkCntN, hipMemcpyDeviceToHost),
-                 "counters") ? 0 : -1;
+  return d->lanes.lane_counters(d->f, stream, sub, d->counters.get(), kPkCntN, counters8, kPkCntN);
 }
 
 extern "C" int dabhip_packet_stage_ms(const dabhip_packet* d, const char** names, float* ms, int cap)

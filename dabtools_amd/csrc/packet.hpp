@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "../../include/dabhip.h"
+#include "eti_push.hpp"
 #include "packet_sync.hpp"
 
 namespace dabhip {
@@ -37,13 +38,6 @@ struct PacketUnit {
   int64_t cell_index;
 };
 static_assert(sizeof(PacketSlot) == 16 && sizeof(PacketUnit) == 32, "packet unit layout");
-
-// the frames of one push: stream s's new frames are frames + (base[s] + v) 6144, v < nnew[s]
-struct PacketFrames {
-  const uint8_t* frames;
-  const int64_t* base;
-  const int* nnew;
-};
 
 enum PacketCounter : int { kPkCntFrames, kPkCntMisses, kPkCntSyncLosses, kPkCntSkipped, kPkCntBadCells, kPkCntPackets, kPkCntRsCorrected, kPkCntRsFailed, kPkCntN = 8 };
 

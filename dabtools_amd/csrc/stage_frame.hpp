@@ -1,11 +1,15 @@
-// stage_frame.hpp — what the handle of a side stage (dabhip_ingest, dabhip_scan, dabhip_dabplus) is made of besides its own buffers: the device, a
-// non-blocking stream of its own, the events around its N timed stages and their times.  A handle declares its frame LAST, so that the frame goes
-// first: the stream is idle and gone before the buffers are freed.
+// stage_frame.hpp — what the handle of a side stage is made of besides its own buffers: the device, a non-blocking stream of its own, the events
+// around its N timed stages and their times.  The stages of raw samples (dabhip_ingest, dabhip_scan), of ETI frames (dabhip_dabplus,
+// dabhip_packet, dabhip_ts, dabhip_dir, dabhip_edi) and of EDI packets (dabhip_edirx) all have one; the first two kinds also take their push's
+// host-side plan (sample_push.hpp, eti_push.hpp) to the device here.  A handle declares its frame LAST, so that the frame goes first: the stream
+// is idle and gone before the buffers are freed.
 #pragma once
 
 #include <algorithm>
 #include <utility>
 
+#include "../../include/dabhip.h"
+#include "eti_push.hpp"
 #include "hip_util.hpp"
 #include "sample_push.hpp"
 
@@ -13,7 +17,7 @@ namespace dabhip {
 
 template <int N>
 struct StageFrame {
-  const char* const prefix;                        // in front of every HIP error: "ingest", "scan", "dabplus"
+  const char* const prefix;                        // in front of every HIP error: "ingest", "scan", "dabplus", ...
   const char* const* const names;                  // the N stages
   int device = 0;
   hipStream_t stream = nullptr;
@@ -77,6 +81,26 @@ struct StageFrame {
       dev[b] = stage.get() + p.offset[b];
       if (p.upload[b] && !ok(hipMemcpyAsync(stage.get() + p.offset[b], src[b], p.upload[b], hipMemcpyHostToDevice, stream), "upload")) return false;
     }
+    return true;
+  }
+  // the device side of a push of ETI frames (eti_push.hpp): the host frames to `staging`, unless they lie on the device already, and the plan's
+  // block to `meta`.  fr: the frames as the kernels take them; ncarry: where the block's third column lies (DAB+)
+  bool place(const EtiPush& p, const uint8_t* frames, int on_device, DeviceBuffer<uint8_t>& staging, DeviceBuffer<uint8_t>& meta, EtiFrames& fr, const int** ncarry = nullptr)
+  {
+    fr.frames = frames;
+    if (p.total > 0 && !on_device) {
+      const size_t bytes = static_cast<size_t>(p.total) * DABHIP_ETI_BYTES;
+      if (!staging.reserve(bytes) || !ok(hipMemcpyAsync(staging.get(), frames, bytes, hipMemcpyHostToDevice, stream), "upload")) return false;
+      fr.frames = staging.get();
+    }
+    // the plan must outlive the asynchronous copy of its block: hipMemcpy from pageable memory returns once the bytes are staged
+    if (!meta.reserve(p.meta.size()) || !ok(hipMemcpyAsync(meta.get(), p.meta.data(), p.meta.size(), hipMemcpyHostToDevice, stream), "upload") ||
+        !ok(hipStreamSynchronize(stream), "upload"))
+      return false;
+    const size_t ns = static_cast<size_t>(p.nstreams);
+    fr.base = reinterpret_cast<const int64_t*>(meta.get());
+    fr.nnew = reinterpret_cast<const int*>(meta.get() + 8 * ns);
+    if (ncarry) *ncarry = p.carries ? reinterpret_cast<const int*>(meta.get() + 12 * ns) : nullptr;
     return true;
   }
 };

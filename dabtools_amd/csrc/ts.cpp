@@ -9,9 +9,8 @@
 #include <vector>
 
 #include "../../include/dabhip.h"
+#include "eti_lanes.hpp"
 #include "kernels.hpp"
-#include "rs_code.hpp"
-#include "stage_frame.hpp"
 #include "ts.hpp"
 
 using namespace dabhip;
@@ -22,10 +21,9 @@ const char* const kStages[kNStages] = {"locate", "runs", "sync", "jobs", "gather
 }
 
 struct dabhip_ts {
-  int nstreams = 0, nsub = 0;
-  DeviceBuffer<int32_t> subch;
+  EtiLanes lanes{"ts"};                             // its host copy: the lanes' first units (lane_unit_base)
   DeviceBuffer<TsSync> sync;
-  DeviceBuffer<TsLane> lanes;
+  DeviceBuffer<TsLane> lane_state;
   DeviceBuffer<int64_t> counters;
   DeviceBuffer<uint8_t> carry[2];
   int cur = 0;
@@ -40,35 +38,13 @@ struct dabhip_ts {
   DeviceBuffer<uint32_t> syn;
   DeviceBuffer<dabhip_ts_rec> recs;
   int64_t n_units = 0;
-  // host copy of the last push's lane bases, fetched on first use
-  mutable bool fetched = false;
-  mutable std::vector<int> h_base;
   StageFrame<kNStages> f{"ts", kStages};
-
-  bool fetch() const
-  {
-    if (fetched) return true;
-    if (!f.use_device()) return false;
-    const size_t nlanes = static_cast<size_t>(nstreams) * nsub;
-    h_base.assign(nlanes + 1, 0);
-    if (n_units > 0 && !f.ok(blocking_copy(h_base.data(), lane_unit_base.get(), sizeof(int) * (nlanes + 1), hipMemcpyDeviceToHost), "records")) return false;
-    fetched = true;
-    return true;
-  }
-
-  bool lane_ok(int s, int q) const
-  {
-    if (s < 0 || s >= nstreams || q < 0 || q >= nsub) { set_error("ts: no such stream / sub-channel"); return false; }
-    return true;
-  }
 
   // the units of one lane of the last push: [a, a + n) of the push's list
   bool lane_range(int stream, int sub, int64_t& a, int64_t& n) const
   {
-    if (!lane_ok(stream, sub) || !fetch()) return false;
-    const int l = stream * nsub + sub;
-    a = h_base[l];
-    n = h_base[l + 1] - a;
+    if (!lanes.lane_ok(stream, sub) || !lanes.fetch(f, lane_unit_base.get(), n_units > 0)) return false;
+    lanes.range(stream, sub, a, n);
     return true;
   }
 };
@@ -79,22 +55,13 @@ extern "C" dabhip_ts* dabhip_ts_create(int device, int nstreams, const int32_t* 
   StageFrame<kNStages>& f = d->f;
   if (!f.open(device, "no HIP device: the MPEG-2 TS stage runs on the GPU only", "ts_create: device index out of range")) return nullptr;
   const auto ok = [&f](hipError_t e, const char* what) { return f.ok(e, what); };
-  if (nstreams <= 0 || nsub <= 0 || nsub > 64 || !subch_ids) { set_error("ts_create: bad arguments"); return nullptr; }
-  for (int q = 0; q < nsub; ++q)
-    if (subch_ids[q] < 0 || subch_ids[q] > 63) { set_error("ts_create: SubChId out of range"); return nullptr; }
-  if (static_cast<int64_t>(nstreams) * nsub > (1 << 18)) { set_error("ts_create: too many (stream, sub-channel) pairs"); return nullptr; }
-  d->nstreams = nstreams;
-  d->nsub = nsub;
-  const size_t nlanes = static_cast<size_t>(nstreams) * nsub;
-  GfRs<kPkRoots> gf;
-  rs_tables_fill(gf);
+  if (!d->lanes.create(f, nstreams, subch_ids, nsub, true, 1 << 18)) return nullptr;
+  const size_t nlanes = d->lanes.count();
   const size_t carry_bytes = nlanes * kTsCarryStride;
-  bool good = d->subch.reserve(nsub) && d->sync.reserve(nlanes) && d->lanes.reserve(nlanes) && d->counters.reserve(nlanes * kTsCntN) && d->gf.reserve(sizeof gf) &&
-              d->carry[0].reserve(carry_bytes) && d->carry[1].reserve(carry_bytes) && d->totals.reserve(kTsTotN) && d->nunits.reserve(nlanes) &&
-              d->lane_unit_base.reserve(nlanes + 1);
-  good = good && ok(hipMemcpy(d->subch.get(), subch_ids, sizeof(int32_t) * nsub, hipMemcpyHostToDevice), "upload") &&
-         ok(hipMemset(d->sync.get(), 0, sizeof(TsSync) * nlanes), "clear") && ok(hipMemset(d->counters.get(), 0, sizeof(int64_t) * nlanes * kTsCntN), "clear") &&
-         ok(hipMemcpy(d->gf.get(), &gf, sizeof gf, hipMemcpyHostToDevice), "upload");
+  bool good = d->sync.reserve(nlanes) && d->lane_state.reserve(nlanes) && d->counters.reserve(nlanes * kTsCntN) && d->carry[0].reserve(carry_bytes) &&
+              d->carry[1].reserve(carry_bytes) && d->totals.reserve(kTsTotN) && d->nunits.reserve(nlanes) && d->lane_unit_base.reserve(nlanes + 1);
+  good = good && ok(hipMemset(d->sync.get(), 0, sizeof(TsSync) * nlanes), "clear") && ok(hipMemset(d->counters.get(), 0, sizeof(int64_t) * nlanes * kTsCntN), "clear") &&
+         upload_rs_tables<kPkRoots>(f, d->gf);
   return good ? d.release() : nullptr;
 }
 
@@ -106,31 +73,13 @@ extern "C" int64_t dabhip_ts_push(dabhip_ts* d, const uint8_t* frames, const int
   StageFrame<kNStages>& f = d->f;
   const auto ok = [&f](hipError_t e, const char* what) { return f.ok(e, what); };
   if (!f.use_device()) return -1;
-  const int ns = d->nstreams, nsub = d->nsub;
-  std::vector<int64_t> base(static_cast<size_t>(ns));
-  int64_t total = 0;
-  int maxv = 0;
-  for (int s = 0; s < ns; ++s) {
-    if (counts[s] < 0 || counts[s] > (1 << 16)) { set_error("ts_push: bad frame count"); return -1; }
-    base[s] = total;
-    total += counts[s];
-    maxv = std::max<int>(maxv, static_cast<int>(counts[s]));
-  }
-  if (total > 0 && !frames) { set_error("ts_push: null frames"); return -1; }
-  const uint8_t* src = frames;
-  if (total > 0 && !on_device) {
-    const size_t bytes = static_cast<size_t>(total) * DABHIP_ETI_BYTES;
-    if (!d->staging.reserve(bytes) || !ok(hipMemcpyAsync(d->staging.get(), frames, bytes, hipMemcpyHostToDevice, f.stream), "upload")) return -1;
-    src = d->staging.get();
-  }
-  // per-stream metadata in one upload: base | nnew
-  std::vector<uint8_t> meta(static_cast<size_t>(ns) * 12);
-  std::memcpy(meta.data(), base.data(), sizeof(int64_t) * ns);
-  for (int s = 0; s < ns; ++s) {
-    const int n = static_cast<int>(counts[s]);
-    std::memcpy(meta.data() + 8 * ns + 4 * s, &n, 4);
-  }
-  const int64_t nlanes = static_cast<int64_t>(ns) * nsub;
+  const int ns = d->lanes.nstreams, nsub = d->lanes.nsub;
+  const EtiPush p = plan_eti_push("ts_push", counts, ns, !frames, 1 << 16, kEtiNoTotalBound);
+  if (!p.refusal.empty()) { set_error(p.refusal); return -1; }
+  EtiFrames fr;
+  if (!f.place(p, frames, on_device, d->staging, d->meta, fr)) return -1;
+  const int64_t nlanes = static_cast<int64_t>(d->lanes.count()), total = p.total;
+  const int maxv = p.maxv;
   // What the push can hold at most.  The sub-channels of one frame do not overlap, so the lanes of a stream share its frames' 6144 bytes: all
   // lanes together have their carried bytes and the frames' bytes.  A flag word covers 64 positions of one lane (one more for its ragged end); a
   // unit needs 204 bytes of its own lane.  One lane alone can give ts_unit_bound of its carried bytes and maxv frames at the largest STL.
@@ -139,16 +88,9 @@ extern "C" int64_t dabhip_ts_push(dabhip_ts* d, const uint8_t* frames, const int
   const int64_t unit_cap = all_bytes / kTsSlot + 1;
   const int cap = static_cast<int>(ts_unit_bound(kTsCarry, maxv, kTsStlMax)) + 1;
   if (all_bytes >= (int64_t{1} << 31) || flag_cap >= (int64_t{1} << 31) || nlanes * cap >= (int64_t{1} << 31)) { set_error("ts_push: too many frames for one push"); return -1; }
-  if (!d->meta.reserve(meta.size()) || !d->loc.reserve(static_cast<size_t>(ns) * std::max(maxv, 1) * nsub) || !d->flags.reserve(static_cast<size_t>(flag_cap)) ||
+  if (!d->loc.reserve(static_cast<size_t>(ns) * std::max(maxv, 1) * nsub) || !d->flags.reserve(static_cast<size_t>(flag_cap)) ||
       !d->slots.reserve(static_cast<size_t>(nlanes) * cap) || !d->units.reserve(static_cast<size_t>(unit_cap)))
     return -1;
-  // the host copy of meta must outlive the asynchronous copy: hipMemcpy from pageable memory returns once the bytes are staged
-  if (!ok(hipMemcpyAsync(d->meta.get(), meta.data(), meta.size(), hipMemcpyHostToDevice, f.stream), "upload") || !ok(hipStreamSynchronize(f.stream), "upload"))
-    return -1;
-  PacketFrames fr;
-  fr.frames = src;
-  fr.base = reinterpret_cast<const int64_t*>(d->meta.get());
-  fr.nnew = reinterpret_cast<const int*>(d->meta.get() + 8 * ns);
   hipStream_t st = f.stream;
   const uint8_t* carry = d->carry[d->cur].get();
   // the runs kernel's workgroups per lane: about 8 words of flags per wave for a lane at the largest rate, 64 at most
@@ -156,13 +98,13 @@ extern "C" int64_t dabhip_ts_push(dabhip_ts* d, const uint8_t* frames, const int
   int totals[kTsTotN] = {0, 0, 0, 0};
   const int nl = static_cast<int>(nlanes);
   bool good = ok(hipMemsetAsync(d->totals.get(), 0, sizeof totals, st), "clear") && f.mark(0) &&
-              ok(launch_ts_locate(fr, d->subch.get(), nsub, ns, maxv, d->loc.get(), d->sync.get(), d->lanes.get(), static_cast<int>(flag_cap), d->totals.get(), st), "locate") &&
-              f.mark(1) && ok(launch_ts_runs(fr, nl, nsub, maxv, per_lane, d->loc.get(), d->lanes.get(), carry, d->totals.get(), d->flags.get(), st), "runs") &&
+              ok(launch_ts_locate(fr, d->lanes.subch.get(), nsub, ns, maxv, d->loc.get(), d->sync.get(), d->lane_state.get(), static_cast<int>(flag_cap), d->totals.get(), st), "locate") &&
+              f.mark(1) && ok(launch_ts_runs(fr, nl, nsub, maxv, per_lane, d->loc.get(), d->lane_state.get(), carry, d->totals.get(), d->flags.get(), st), "runs") &&
               f.mark(2) &&
-              ok(launch_ts_sync(fr, nl, nsub, maxv, d->loc.get(), d->sync.get(), d->lanes.get(), carry, d->flags.get(), d->slots.get(), cap, d->nunits.get(),
+              ok(launch_ts_sync(fr, nl, nsub, maxv, d->loc.get(), d->sync.get(), d->lane_state.get(), carry, d->flags.get(), d->slots.get(), cap, d->nunits.get(),
                                 d->counters.get(), d->totals.get(), st), "sync") &&
               f.mark(3) &&
-              ok(launch_ts_jobs(nl, d->slots.get(), cap, d->nunits.get(), d->lane_unit_base.get(), d->sync.get(), d->lanes.get(), d->units.get(), unit_cap,
+              ok(launch_ts_jobs(nl, d->slots.get(), cap, d->nunits.get(), d->lane_unit_base.get(), d->sync.get(), d->lane_state.get(), d->units.get(), unit_cap,
                                 d->totals.get(), st), "jobs") &&
               f.mark(4) && ok(hipMemcpyAsync(totals, d->totals.get(), sizeof totals, hipMemcpyDeviceToHost, st), "totals") && ok(hipStreamSynchronize(st), "sync stage");
   if (!good) return -1;
@@ -172,16 +114,16 @@ extern "C" int64_t dabhip_ts_push(dabhip_ts* d, const uint8_t* frames, const int
   }
   const int64_t nu = totals[kTsTotUnits];
   d->n_units = nu;
-  d->fetched = false;
+  d->lanes.fetched = false;
   const size_t cu = static_cast<size_t>(nu ? nu : 1);
   good = d->words.reserve(static_cast<size_t>(ts_word_buffer_bytes(static_cast<int64_t>(cu)))) && d->data.reserve(cu * kTsData) && d->recs.reserve(cu) &&
          d->cw_status.reserve(cu) && d->syn.reserve(cu * 4) &&
-         ok(launch_ts_gather(fr, d->units.get(), d->totals.get(), nu, d->loc.get(), maxv, nsub, carry, d->lanes.get(), d->words.get(), st), "gather") &&
+         ok(launch_ts_gather(fr, d->units.get(), d->totals.get(), nu, d->loc.get(), maxv, nsub, carry, d->lane_state.get(), d->words.get(), st), "gather") &&
          f.mark(5) && ok(launch_ts_syndrome(d->totals.get(), nu, d->gf.get(), d->words.get(), d->cw_status.get(), d->syn.get(), st), "syndrome") &&
          f.mark(6) && ok(launch_ts_decode(d->totals.get(), nu, d->gf.get(), d->words.get(), d->cw_status.get(), d->syn.get(), st), "decode") &&
          f.mark(7) &&
          ok(launch_ts_parse(d->units.get(), d->totals.get(), nu, d->words.get(), d->cw_status.get(), d->recs.get(), d->data.get(), d->counters.get(), st), "parse") &&
-         f.mark(8) && ok(launch_ts_carry(fr, nl, d->loc.get(), maxv, nsub, carry, d->lanes.get(), d->totals.get(), d->carry[d->cur ^ 1].get(), st), "carry") &&
+         f.mark(8) && ok(launch_ts_carry(fr, nl, d->loc.get(), maxv, nsub, carry, d->lane_state.get(), d->totals.get(), d->carry[d->cur ^ 1].get(), st), "carry") &&
          f.mark(9) && f.finish();
   if (!good) return -1;
   d->cur ^= 1;
@@ -209,10 +151,7 @@ extern "C" int64_t dabhip_ts_data(const dabhip_ts* d, int stream, int sub, uint8
 extern "C" int dabhip_ts_stats(const dabhip_ts* d, int stream, int sub, int64_t* counters8)
 {
   if (!d || !counters8) { set_error("ts_stats: null argument"); return -1; }
-  if (!d->lane_ok(stream, sub)) return -1;
-  if (!d->f.use_device()) return -1;
-  return d->f.ok(blocking_copy(counters8, d->counters.get() + (static_cast<size_t>(stream) * d->nsub + sub) * kTsCntN, sizeof(int64_t) * kTsCntN, hipMemcpyDeviceToHost),
-                 "counters") ? 0 : -1;
+  return d->lanes.lane_counters(d->f, stream, sub, d->counters.get(), kTsCntN, counters8, kTsCntN);
 }
 
 extern "C" int dabhip_ts_stage_ms(const dabhip_ts* d, const char** names, float* ms, int cap)

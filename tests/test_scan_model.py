@@ -257,3 +257,9 @@ def test_push_front_under_sanitizers():
     """tests/host_sanitize/push_units.cpp: the front of the ingest's and the scan's push (csrc/sample_push.hpp), the scan's upload clamp and the
     packed mixer table."""
     run_unit("push")
+
+
+def test_eti_push_front_under_sanitizers():
+    """tests/host_sanitize/eti_push_units.cpp: the front of the five pushes of ETI frames (csrc/eti_push.hpp: counts, bounds, refusals, the packed
+    per-stream block) and the STC walk of the three locate kernels (csrc/eti_locate.hpp) against a restatement, on hand-built headers."""
+    run_unit("eti_push")
