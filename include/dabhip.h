@@ -133,7 +133,10 @@ int64_t dabhip_engine_eti_count(const dabhip_engine *e, int stream);      /* fra
  * good: the reference only ever adds sub-channels, misc.c:14-21); lock rule, CIF ring and frame counter move on as they would; every other stream
  * of the batch decodes exactly as if it were alone.  0 = fine; 0xffffffff = no such stream.
  * A multiplex that raises none of the flags is decoded whatever the sizes of its sub-channels, one that fills all 864 capacity units included; above
- * 13,824 data bits per code word the reference's decoder is past its own allocation (dab.c:29) and parity is with the oracle and the transmitted payload. */
+ * 13,824 data bits per code word the reference's decoder is past its own allocation (dab.c:29) and parity is with the oracle and the transmitted payload.
+ * Under a sub-channel filter (dabhip_engine_set_subchannels) the flags describe the CARRIED multiplex, the listed sub-channels alone: a sub-channel
+ * that is not listed is neither decoded nor placed in the frame, so what the FIC says of it raises no flag and silences nothing -- the stream's status
+ * stays 0 and its frames keep coming, with the FIC passed on as received.  Listed, the same sub-channel raises the flags of the unfiltered decode. */
 #define DABHIP_STREAM_MUX_OVERFLOW 1u       /* header + FIC + sub-channel bytes + trailer exceed 6144 bytes */
 #define DABHIP_STREAM_SUBCH_OUTSIDE_CIF 2u  /* a sub-channel's transmitted bits end beyond capacity unit 863 */
 #define DABHIP_STREAM_EEP_OPTION 4u         /* EEP protection option > 1: outside ETSI EN 300 401 and past the reference's table */
@@ -277,7 +280,11 @@ int dabhip_host_stream_state_bytes(void);
 /* Sub-channel filter (the reference's TODO.md:28-31, "save CPU time by not decoding data which will later be discarded"):
  * only the listed SubChIds (0..63) are decoded and carried; the ETI frames then list exactly those in their STC (NST, FL,
  * HCRC and EOF CRC follow; the FIC is passed on unchanged), each one's payload identical to the unfiltered frame's.
- * n <= 0 = all (default, the reference's frames).  Takes effect with the next decode. */
+ * n <= 0 = all (default, the reference's frames).  Takes effect with the next decode.
+ * Ids outside 0..63 are ignored, and so is a repeated id; a list with no valid id (n > 0) carries nothing: every frame has NST 0 and the FIC alone, and
+ * no MSC code word is decoded.  A listed id the ensemble does not signal (yet) is simply absent from the STC until it is.
+ * The fault flags of dabhip_engine_stream_status describe the carried multiplex (see there); lock, the CIF counter and the operator log
+ * (dabhip_engine_stream_log: it dumps the whole ensemble) do not depend on the filter. */
 int dabhip_engine_set_subchannels(dabhip_engine *e, const int32_t *ids, int n);
 
 /* OFDM stage variant.  enable != 0 (default): the 2048-point transforms and the DQPSK demap / de-interleave scatter run as

@@ -182,6 +182,15 @@ static void control_and_worklist(int nstreams, int ntf, int64_t max_rows, unsign
         CHECK(n1 == n2 && std::memcmp(fast, slow, static_cast<size_t>(n1)) == 0);
       }
     }
+    if (planes[sb].locked() && b % 7 == 5) {                     // a filter set while a header is cached (the engine sets it on a new plane only): the cache goes
+      const uint64_t before = planes[sb].filter();
+      for (const uint64_t keep : {uint64_t(0x4), uint64_t(0), before}) {
+        uint8_t fast[kEtiHeaderMax], slow[kEtiHeaderMax];
+        planes[sb].set_filter(keep);
+        const int n1 = planes[sb].frame_header(fast), n2 = build_eti_header(slow, planes[sb].ensemble(), keep);
+        CHECK(n1 == n2 && std::memcmp(fast, slow, static_cast<size_t>(n1)) == 0);
+      }
+    }
   });
   std::vector<const ControlPlane*> plane_ptrs;
   std::vector<const JobList*> job_ptrs;

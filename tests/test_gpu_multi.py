@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import dabtools_amd as dab
+import eti_filter_model
 import oracle_lib as ol
 from dabtools_amd import shard
 
@@ -66,6 +67,8 @@ def test_eight_slices_on_one_gpu_equal_single_engine_and_oracle():
     single.decode(caps[:9])
     for b in range(9):
         assert np.array_equal(multi.eti(b), single.eti(b)), b
+    for b in (0, 4, 8):                                                     # and against the rewrite of the reference's frames (tests/eti_filter_model.py)
+        assert np.array_equal(multi.eti(b), eti_filter_model.filter_frames(ol.or_replay(caps[b])[0], [2])), b
     multi.close()
     single.close()
 

@@ -717,6 +717,8 @@ def test_subchannel_filter_carries_exactly_the_selected_payload():
     eng.decode([cap])
     part = eng.eti(0)
     assert len(part) == len(full)
+    import eti_filter_model
+    assert np.array_equal(part, eti_filter_model.filter_frames(ol.or_replay(cap)[0], [5, 9, 40]))       # whole frames: the rewrite of the reference's
     for f, p in zip(full, part):
         a, b = eti_check.parse(f), eti_check.parse(p)
         assert [s[0] for s in b["stc"]] == [5, 9] and b["fct"] == a["fct"] and np.array_equal(a["fic"], b["fic"])
